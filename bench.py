@@ -2,15 +2,20 @@
 """Headline benchmark: play-sequences/sec/node of the HULC++ low-level policy training step on MI355X.
 
   python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run, one rank / GPU)
+  python bench.py --gpus N --steps K --warmup W --full   (+ everything beyond the headline, listed below)
+  python bench.py ... --dump-outputs DIR                 (+ what the last timed step computed, as DIR/<name>.npy)
 
 A "step" = one full optimizer step of `Hulc2.training_step` (forward + backward + gradient all-reduce + Adam) over
 one device-resident synthetic CALVIN-shaped batch: 2 modalities x 32 play sequences x 32 timesteps, 200x200 static +
 84x84 gripper RGB, random (B,384) language embeddings (BASELINE.json configs[1]/[2]).  Weak scaling:
 each rank processes its own 64 sequences per step.
 
-Prints ONE JSON line (rank 0) with the contract fields plus
-  roofline     — the dominant kernel's algorithmic FLOP/s from HIP events recorded live on the launch stream
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the contract fields.  --full adds
+  roofline     — the dominant kernel's algorithmic FLOP/s from HIP events recorded live on the launch stream (3 more eager steps)
+  roofline_txl — the transformer trunk's launches inside the step and alone at 256 / 1024 sequences
+  secondary*   — the step in the other arithmetic modes and the Lightning-style loop (--no-secondary skips them)
   cpu_baseline — the CPU oracle (fp32 torch restatement, kind "port") timed on this box's host cores on a bounded sample
+                 (--no-cpu-baseline skips it)
 """
 import argparse
 import json
@@ -489,6 +494,53 @@ def lightning_loop(args, dev):
     return res
 
 
+def roofline_leg(args, trainer, model, batch, dev, peak):
+    """--full: per-launch HIP events on the launch stream over 3 more eager steps (outside the timed region) -> (the per-kernel table, the
+    dominant kernel's roofline entry, the transformer trunk's entry or None).
+    The dominant kernel = the (entry point, shape) with the largest summed time.  Its bound is whichever roof needs longer for
+    the launch's ALGORITHMIC work (kernels.py annotates flops = 2 x MACs and bytes = every operand / result touched once):
+    bytes / 8 TB/s vs flops / dense MFMA peak.  achieved = that work / the measured average launch duration.
+    (one stream for this leg: with the camera encoders on two streams the gripper camera's kernels run INSIDE the static camera's launches and
+    every per-launch duration would include its neighbour's share of the chip)"""
+    from hulc2_amd import kernels as kn
+    prev_streams, prev_fork = os.environ.get("HULC_ENC_STREAMS"), os.environ.get("HULC_FORK")
+    os.environ["HULC_ENC_STREAMS"] = "0"
+    os.environ["HULC_FORK"] = "0"                           # (round 6: one chain here — the forked branches overlap launches; the timed region ran the forked graph)
+    trainer.step(batch, 0)                                  # untimed: the one-chain arrangement's per-stream workspaces exist before the timed launches (a first use read 238 us for the trunk's backward instead of 117)
+    kn.start_timing()
+    for i in range(3):
+        trainer.step(batch, i)
+    table = kn.stop_timing()
+    for k_, v_ in (("HULC_ENC_STREAMS", prev_streams), ("HULC_FORK", prev_fork)):
+        if v_ is None:
+            os.environ.pop(k_, None)
+        else:
+            os.environ[k_] = v_
+    total_ms = sum(v[1] for v in table.values())
+    dom_key, (dom_n, dom_t, dom_flops, dom_bytes) = max(table.items(), key=lambda kv: kv[1][1])
+    avg_s = dom_t / dom_n * 1e-3
+    hbm_bound = dom_bytes / PEAK_HBM >= dom_flops / peak
+    if hbm_bound:
+        rl = {"bound": "hbm", "achieved": round(dom_bytes / avg_s / 1e9, 1), "peak": PEAK_HBM / 1e9, "unit": "GB/s",
+              "frac": round(dom_bytes / avg_s / PEAK_HBM, 4)}
+    else:
+        rl = {"bound": "mfma", "achieved": round(dom_flops / avg_s / 1e12, 2), "peak": peak / 1e12, "unit": "TFLOP/s",
+              "frac": round(dom_flops / avg_s / peak, 4)}
+    rl["traffic"] = pmc_traffic(dom_key)
+    rl.update({"kernel": "/".join(str(k) for k in dom_key),
+               "algorithmic_bytes_per_launch": dom_bytes, "algorithmic_flops_per_launch": dom_flops,
+               "launches_per_step": dom_n // 3, "avg_launch_ms": round(dom_t / dom_n, 4),
+               "kernel_share_of_step": round(dom_t / max(total_ms, 1e-9), 3),
+               "gpu_kernel_ms_per_step": round(total_ms / 3, 3)})
+    rl_txl = None
+    if not (args.affordance or args.real_world) and args.compute == "bf16":
+        try:
+            rl_txl = txl_roofline(table, model, dev, peak, 2 * args.batch, alone=not args.no_secondary)
+        except Exception as e:                              # noqa: BLE001
+            rl_txl = {"error": f"{type(e).__name__}: {e}"}
+    return table, rl, rl_txl
+
+
 TXL_FLOP_PER_SEQ = 229.6e6        # SURVEY §8d: the two transformer layers, forward + backward, per 32-step play sequence (2 x 598 016 MAC per token and layer)
 
 
@@ -534,6 +586,32 @@ def txl_roofline(table, model, dev, peak, seqs_in_step, alone=True):
     for prm in net.parameters():
         prm.grad = None
     return out
+
+
+DUMP_SAMPLE = 16384               # --dump-outputs: elements kept per tensor (108 parameters + their gradients: at most 14 MB in all)
+
+
+def dump_outputs(path, model, loss) -> None:
+    """What the timed path hands its caller after its last step: the loss, every trainable parameter after the optimizer update and the
+    gradient that update consumed, as float32 / float64 .npy files.  A tensor of more than DUMP_SAMPLE elements is written as a fixed
+    sample: the indices come from a generator seeded with the tensor's name, so two builds compare element for element."""
+    import zlib
+
+    import numpy as np
+    out = Path(path)
+    out.mkdir(parents=True, exist_ok=True)
+    np.save(out / "loss.npy", np.array([float(loss)], dtype=np.float64))
+    for name, p in model.named_parameters():
+        if not p.requires_grad:
+            continue
+        for kind, t in (("param", p), ("grad", p.grad)):
+            if t is None:
+                continue
+            flat = t.detach().reshape(-1)
+            if flat.numel() > DUMP_SAMPLE:
+                idx = np.random.RandomState(zlib.crc32(name.encode())).randint(0, flat.numel(), DUMP_SAMPLE)
+                flat = flat[torch.from_numpy(idx).to(flat.device)]
+            np.save(out / f"{kind}.{name}.npy", flat.float().cpu().numpy())
 
 
 def _free_port():
@@ -608,9 +686,15 @@ def main():
     ap.add_argument("--batch", type=int, default=32, help="play sequences per modality per GPU")
     ap.add_argument("--seq-len", type=int, default=32)
     ap.add_argument("--compute", default="bf16", choices=["bf16", "fp32", "mixed"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the per-kernel roofline leg, the secondary arithmetic modes and the Lightning-style loop (unless "
+                         "--no-secondary) and the CPU baseline (unless --no-cpu-baseline); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (loss, parameters after the update, their gradients; a fixed sample of "
+                         "large tensors) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel eagerly instead of replaying captured HIP graphs")
-    ap.add_argument("--breakdown", action="store_true", help="print the per-kernel time table to stderr")
+    ap.add_argument("--breakdown", action="store_true", help="print the per-kernel time table to stderr (runs the roofline leg, as --full does)")
     ap.add_argument("--affordance", action="store_true", help="BASELINE configs[4] (secondary): one training step of the affordance model "
                     "(PixelAffLangDetector, r3m variant) on --batch images of 224 x 224; the metric becomes images per second")
     ap.add_argument("--trunk-mode", default="frozen", choices=["frozen", "reference"],
@@ -626,7 +710,7 @@ def main():
     ap.add_argument("--real-world", action="store_true",
                     help="secondary measurement, BASELINE configs[3] (cfg_low_level_rw): static camera 150x200 in [0,255] through the frozen R3M "
                          "ResNet-18 trunk, whole-embedding decoder input, world-frame actions, no CLIP loss")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the fp32-compute (1e-3 parity mode) throughput leg")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the fp32-compute (1e-3 parity mode) throughput leg")
     ap.add_argument("--force-dist", action="store_true",
                     help="with one rank: still create the process group and run the multi-rank control flow (split graphs, comm stream, "
                          "collectives) — executes the RCCL path on a one-GPU box")
@@ -809,50 +893,19 @@ def main():
     kn.check_faults(dev)                                    # a barrier-kernel timeout inside the timed region ends the run (non-zero exit), not a NaN line
     if final_loss != final_loss:
         raise SystemExit("[bench] the loss is NaN after the timed region")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss)        # before anything else steps the model
 
-    # ---- roofline leg: per-launch HIP events on the launch stream over 3 more eager steps (outside the timed region) ----
-    # The dominant kernel = the (entry point, shape) with the largest summed time.  Its bound is whichever roof needs longer for
-    # the launch's ALGORITHMIC work (kernels.py annotates flops = 2 x MACs and bytes = every operand / result touched once):
-    # bytes / 8 TB/s vs flops / dense MFMA peak.  achieved = that work / the measured average launch duration.
-    # (one stream for this leg: with the camera encoders on two streams the gripper camera's kernels run INSIDE the static camera's launches and
-    # every per-launch duration would include its neighbour's share of the chip)
-    prev_streams, prev_fork = os.environ.get("HULC_ENC_STREAMS"), os.environ.get("HULC_FORK")
-    os.environ["HULC_ENC_STREAMS"] = "0"
-    os.environ["HULC_FORK"] = "0"                           # (round 6: one chain here — the forked branches overlap launches; the timed region above ran the forked graph)
-    trainer.step(batch, 0)                                  # untimed: the one-chain arrangement's per-stream workspaces exist before the timed launches (a first use read 238 us for the trunk's backward instead of 117)
-    kn.start_timing()
-    for i in range(3):
-        trainer.step(batch, i)
-    table = kn.stop_timing()
-    for k_, v_ in (("HULC_ENC_STREAMS", prev_streams), ("HULC_FORK", prev_fork)):
-        if v_ is None:
-            os.environ.pop(k_, None)
-        else:
-            os.environ[k_] = v_
-    total_ms = sum(v[1] for v in table.values())
+    rl = rl_txl = None
     peak = PEAK_F32 if args.compute == "fp32" else PEAK_BF16
-    dom_key, (dom_n, dom_t, dom_flops, dom_bytes) = max(table.items(), key=lambda kv: kv[1][1])
-    avg_s = dom_t / dom_n * 1e-3
-    hbm_bound = dom_bytes / PEAK_HBM >= dom_flops / peak
-    if hbm_bound:
-        rl = {"bound": "hbm", "achieved": round(dom_bytes / avg_s / 1e9, 1), "peak": PEAK_HBM / 1e9, "unit": "GB/s",
-              "frac": round(dom_bytes / avg_s / PEAK_HBM, 4)}
-    else:
-        rl = {"bound": "mfma", "achieved": round(dom_flops / avg_s / 1e12, 2), "peak": peak / 1e12, "unit": "TFLOP/s",
-              "frac": round(dom_flops / avg_s / peak, 4)}
-    rl["traffic"] = pmc_traffic(dom_key)
-    rl_txl = None
-    if not (args.affordance or args.real_world) and args.compute == "bf16":
-        try:
-            rl_txl = txl_roofline(table, model, dev, peak, 2 * args.batch, alone=not args.no_secondary)
-        except Exception as e:                              # noqa: BLE001
-            rl_txl = {"error": f"{type(e).__name__}: {e}"}
-    if args.breakdown and rank == 0:
-        rows = int(os.environ.get("HULC_BREAKDOWN_ROWS", "25"))
-        for key, (n, t, f, b) in sorted(table.items(), key=lambda kv: -kv[1][1])[:rows]:
-            a = t / n * 1e-3
-            print(f"  {t / 3:9.3f} ms/step  {n // 3:4d} launches  {f / a / 1e12:8.1f} TFLOP/s  {b / a / 1e9:8.0f} GB/s  {key}", file=sys.stderr)
-        print(f"  sum of kernel time: {total_ms / 3:.3f} ms/step", file=sys.stderr)
+    if args.full or args.breakdown:
+        table, rl, rl_txl = roofline_leg(args, trainer, model, batch, dev, peak)
+        if args.breakdown and rank == 0:
+            rows = int(os.environ.get("HULC_BREAKDOWN_ROWS", "25"))
+            for key, (n, t, f, b) in sorted(table.items(), key=lambda kv: -kv[1][1])[:rows]:
+                a = t / n * 1e-3
+                print(f"  {t / 3:9.3f} ms/step  {n // 3:4d} launches  {f / a / 1e12:8.1f} TFLOP/s  {b / a / 1e9:8.0f} GB/s  {key}", file=sys.stderr)
+            print(f"  sum of kernel time: {rl['gpu_kernel_ms_per_step']:.3f} ms/step", file=sys.stderr)
 
     seqs = (1 if args.affordance else 2) * args.batch * world * args.steps
     ms_per_step = elapsed / args.steps * 1e3
@@ -904,21 +957,18 @@ def main():
                                          if dist.is_initialized() else "none (one rank, no process group)",
                    "exact_forward_sites": (",".join(sorted(kn.fp32_sites())) or "none") if args.compute == "bf16" and not args.affordance else None,
                    "final_loss": round(final_loss, 4)},
-        # step_frac = the WHOLE step against the dense MFMA roof (SURVEY §8d: the roof that bounds this path), on the algorithmic
-        # 14.13 GFLOP / sequence; frac / achieved below describe the single dominant kernel only
-        "roofline": {"step_frac": step_frac, **rl, "kernel": "/".join(str(k) for k in dom_key),
-                     "algorithmic_bytes_per_launch": dom_bytes, "algorithmic_flops_per_launch": dom_flops,
-                     "launches_per_step": dom_n // 3, "avg_launch_ms": round(dom_t / dom_n, 4),
-                     "kernel_share_of_step": round(dom_t / max(total_ms, 1e-9), 3),
-                     "step_frac_of_mfma_peak": step_frac,
-                     "gpu_kernel_ms_per_step": round(total_ms / 3, 3)},
     }
+    if rl is not None:
+        # step_frac = the WHOLE step against the dense MFMA roof (SURVEY §8d: the roof that bounds this path), on the algorithmic
+        # 14.13 GFLOP / sequence; frac / achieved describe the single dominant kernel only
+        kernel_ms = rl.pop("gpu_kernel_ms_per_step")
+        out["roofline"] = {"step_frac": step_frac, **rl, "step_frac_of_mfma_peak": step_frac, "gpu_kernel_ms_per_step": kernel_ms}
     if rl_txl is not None:
         out["roofline_txl"] = rl_txl
     if comm_info is not None:
         out["comm"] = comm_info
     plain = not (args.real_world or args.uint8_frames or args.episode_store or args.no_graph or args.affordance)
-    if world == 1 and args.compute == "bf16" and plain and not args.no_secondary:
+    if args.full and world == 1 and args.compute == "bf16" and plain and not args.no_secondary:
         del trainer, model
         import gc
         gc.collect()
@@ -936,7 +986,7 @@ def main():
         gc.collect()
         torch.cuda.empty_cache()
         out["secondary_lightning_loop"] = lightning_loop(args, dev)
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+    if args.full and rank == 0 and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline_affordance() if args.affordance else cpu_baseline()
     if rank == 0:
         emit(out)

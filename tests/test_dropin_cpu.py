@@ -11,7 +11,6 @@ from pathlib import Path
 import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
-REFERENCE = Path("/root/reference")
 
 # every `_target_` under conf/model/** + conf/affordance/aff_detection/r3m.yaml this build implements
 # (reference yaml:line -> class); the rest of conf/model/** (CLIP / ResNet encoders, BiLSTM, GCBC ...) stays the reference's own.
@@ -200,18 +199,62 @@ STUBS = '''
 '''
 
 
-@pytest.mark.skipif(not (REFERENCE / "hulc2" / "training.py").exists(), reason="build container only: /root/reference is not on the GPU box")
+def make_reference_tree(tmp_path):
+    """a `hulc2/` package laid out like the reference's at every module path the next test names: the entry point hulc2/training.py with
+    its third-party imports (hydra, omegaconf, pytorch_lightning: served by the STUBS) and its hulc2.utils.utils import; hulc2/models/__init__.py
+    importing aliased leaves at package import time; a reference model class subclassing an aliased one (gcbc); a reference-side leaf under
+    every parent package of OURS, and the aliased leaves themselves as reference classes (the alias must win over them)"""
+    files = {
+        "hulc2/__init__.py": "",
+        "hulc2/training.py": "import hydra\nfrom omegaconf import DictConfig, OmegaConf\nfrom pytorch_lightning import Callback, LightningModule, Trainer\n"
+                             "from pytorch_lightning.strategies import DDPStrategy\n"
+                             "from hulc2.utils.utils import get_git_commit_hash, get_last_checkpoint, initialize_pretrained_weights, print_system_env_info\n",
+        "hulc2/utils/utils.py": "".join(f"def {f}(*a, **k):\n    return None\n" for f in ("get_git_commit_hash", "get_last_checkpoint",
+                                                                                          "initialize_pretrained_weights", "print_system_env_info")),
+        "hulc2/utils/kl_callbacks.py": "from pytorch_lightning import Callback\nclass KLConstantSchedule(Callback):\n    pass\n",
+        "hulc2/utils/transforms.py": "import torch\nclass ScaleImageTensor:\n    pass\n",
+        "hulc2/utils/tensor_utils.py": "import torch\n",
+        "hulc2/utils/data_utils.py": "import numpy as np\n",
+        "hulc2/datasets/hulc2_sim_data_module.py": "import pytorch_lightning as pl\nclass Hulc2SimdDataModule(pl.LightningDataModule):\n    pass\n",
+        "hulc2/datasets/shm_dataset.py": "class ShmDataset:\n    pass\n",
+        "hulc2/datasets/utils/shared_memory_loader.py": "from pytorch_lightning import Callback\nclass SignalCallback(Callback):\n    pass\n",
+        "hulc2/rollout/rollout.py": "from pytorch_lightning import Callback\nclass Rollout(Callback):\n    pass\n",
+        "hulc2/models/__init__.py": "from hulc2.affordance.models.language_encoders.bert_lang_encoder import BERTLang\n"
+                                    "from hulc2.affordance.models.language_encoders.sbert_lang_encoder import SBertLang\n"
+                                    "lang_encoders = {'bert': BERTLang, 'sbert': SBertLang}\n",
+        "hulc2/models/gcbc.py": "from hulc2.models.hulc2 import Hulc2\nclass GCBC(Hulc2):\n    pass\n",
+        "hulc2/models/encoders/language_network.py": "class SBert:\n    pass\n",
+        "hulc2/models/decoders/deterministic_decoder.py": "class DeterministicDecoder:\n    pass\n",
+        "hulc2/models/perceptual_encoders/proprio_encoder.py": "class IdentityEncoder:\n    pass\n",
+        "hulc2/affordance/models/language_encoders/bert_lang_encoder.py": "class BERTLang:\n    pass\n",
+    }
+    for path in OURS:
+        mod, _, cls = path.rpartition(".")
+        files[mod.replace(".", "/") + ".py"] = f"class {cls}:\n    WHO = 'reference'\n"
+    for rel, text in files.items():
+        f = tmp_path / rel
+        f.parent.mkdir(parents=True, exist_ok=True)
+        f.write_text(text)
+    for d in (tmp_path / "hulc2").rglob("*"):                      # every directory a package, as in the reference
+        if d.is_dir() and not (d / "__init__.py").exists():
+            (d / "__init__.py").write_text("")
+    return tmp_path
+
+
 @pytest.mark.parametrize("order", ["before", "after"])
-def test_with_the_reference_tree_on_sys_path(order):
-    """the imports of /root/reference/hulc2/training.py:20-25 and the `_target_`s Hydra instantiates at :40 / :95
+def test_with_the_reference_tree_on_sys_path(order, tmp_path):
+    """the imports of the reference's hulc2/training.py:20-25 and the `_target_`s Hydra instantiates at :40 / :95
     (conf/datamodule/calvin_default.yaml:6, conf/callbacks/kl_schedule/constant.yaml:1, conf/callbacks/rollout/default.yaml:3) still come
-    from the reference; the model classes of conf/model/** come from this package."""
+    from the reference; the model classes of conf/model/** come from this package.  The reference tree is the stand-in above, laid out as
+    the reference's at every path named here."""
+    tree = make_reference_tree(tmp_path)
+    ref = f"{tree}/hulc2/"
     pre = "import hulc2.utils.distributions, hulc2.models.hulc2, hulc2.models\n" if order == "after" else ""
     code = f'''
         from hulc2_amd.compat import install_as_hulc2
         install_as_hulc2()
         import hulc2
-        assert hulc2.__file__.startswith("/root/reference/")
+        assert hulc2.__file__.startswith({ref!r})
         from hulc2.utils.utils import get_git_commit_hash, get_last_checkpoint, initialize_pretrained_weights, print_system_env_info
         assert get_last_checkpoint.__module__ == "hulc2.utils.utils"
         for path in ("hulc2.datasets.hulc2_sim_data_module.Hulc2SimdDataModule", "hulc2.utils.kl_callbacks.KLConstantSchedule",
@@ -219,7 +262,7 @@ def test_with_the_reference_tree_on_sys_path(order):
                      "hulc2.datasets.utils.shared_memory_loader.SignalCallback", "hulc2.utils.tensor_utils", "hulc2.utils.data_utils"):
             obj = locate(path)
             f = sys.modules[getattr(obj, "__module__", None) or obj.__name__].__file__
-            assert f.startswith("/root/reference/hulc2/"), (path, f)
+            assert f.startswith({ref!r}), (path, f)
         for path in {sorted(OURS)!r}:
             cls = locate(path)
             assert cls.__module__.startswith("hulc2_amd."), (path, cls.__module__)
@@ -228,14 +271,14 @@ def test_with_the_reference_tree_on_sys_path(order):
             assert locate(path).__module__.startswith("hulc2_amd.")
         for path in ("hulc2.models.encoders.language_network.SBert", "hulc2.models.decoders.deterministic_decoder.DeterministicDecoder",
                      "hulc2.models.perceptual_encoders.proprio_encoder.IdentityEncoder"):
-            assert sys.modules[locate(path).__module__].__file__.startswith("/root/reference/hulc2/"), path
+            assert sys.modules[locate(path).__module__].__file__.startswith({ref!r}), path
         import hulc2.training                      # the entry point itself imports (its module-level imports = training.py:1-25)
-        assert hulc2.training.__file__ == "/root/reference/hulc2/training.py"
+        assert hulc2.training.__file__ == {ref + "training.py"!r}
         import hulc2.models.gcbc, hulc2_amd.models.hulc2
         assert issubclass(hulc2.models.gcbc.GCBC, hulc2_amd.models.hulc2.Hulc2)
         import hulc2.models
-        assert hulc2.models.__file__.startswith("/root/reference/") and hulc2.models.lang_encoders["sbert"].__module__.startswith("hulc2_amd.")
+        assert hulc2.models.__file__.startswith({ref!r}) and hulc2.models.lang_encoders["sbert"].__module__.startswith("hulc2_amd.")
         print("ok")
     '''
-    out = run(STUBS, pre, code, paths=[REFERENCE])
+    out = run(STUBS, pre, code, paths=[tree])
     assert out.strip().endswith("ok")
