@@ -355,22 +355,20 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gather_bf16_kernel(GatherP p
 
 template <typename CT> bool launch_gather_raw(const GatherP&, hipStream_t) { return false; }
 template <> bool launch_gather_raw<bf16_t>(const GatherP& p, hipStream_t s) {
-    if (p.x_dtype != HULC_BF16 || p.w_dtype != HULC_BF16 || p.Cout <= 32 || getenv("HULC_GATHER_GENERIC")) return false;
+    if (p.x_dtype != HULC_BF16 || p.w_dtype != HULC_BF16 || p.Cout <= 32) return false;
     const long Mtot = (long)p.Nimg * p.OH * p.OW;
     const bool wide = p.Cout % 128 == 0;
     // every wave owns 64 pixels x 64 channels (8 MFMAs per 32-wide k tile): 128 x 128 tiles for wide layers, 256 pixels x 64 channels else
-    const bool tall = !wide && p.Cout % 64 == 0 && Mtot >= 256 * 512 && !getenv("HULC_GATHER_M128");
+    const bool tall = !wide && p.Cout % 64 == 0 && Mtot >= 256 * 512;
     dim3 grid((unsigned)((Mtot + (tall ? 255 : 127)) / (tall ? 256 : 128)), wide ? p.Cout / 128 : (p.Cout + 63) / 64);
     // few 128 x 128 tiles (the trunk's 128 / 256 / 512-channel stages at 32 images: 196, 98 and 52 workgroups on 256 CUs; measured 5.02 -> 4.80 ms per affordance step): 64 x 64 tiles, four times the
     // workgroups — twice the LDS bytes per MFMA, but the chip is filled
-    static const long small_thr = getenv("HULC_GATHER_SMALL") ? atol(getenv("HULC_GATHER_SMALL")) : 256;
-    if (wide && p.inner_log2 >= 5 && (long)grid.x * grid.y < small_thr) {
+    if (wide && p.inner_log2 >= 5 && (long)grid.x * grid.y < 256) {
         dim3 g64((unsigned)((Mtot + 63) / 64), p.Cout / 64);
         // 128- / 64-wide k tiles where a tap holds them: these launches are a chain of (load, LDS write, barrier, 2 MFMAs per wave) steps — a quarter /
         // half as many (affordance step, 32 images: 4.81 ms with 32-wide tiles, 4.67 with 64, 4.57 with 128)
-        static const int kt64 = getenv("HULC_GATHER_SMALL_KT64") ? atoi(getenv("HULC_GATHER_SMALL_KT64")) : 2;
-        if (kt64 >= 2 && p.inner_log2 >= 7) conv_gather_bf16_kernel<1, 1, 2, 2, true, 128><<<g64, 256, 0, s>>>(p);
-        else if (kt64 && p.inner_log2 >= 6) conv_gather_bf16_kernel<1, 1, 2, 2, true, 64><<<g64, 256, 0, s>>>(p);
+        if (p.inner_log2 >= 7) conv_gather_bf16_kernel<1, 1, 2, 2, true, 128><<<g64, 256, 0, s>>>(p);
+        else if (p.inner_log2 >= 6) conv_gather_bf16_kernel<1, 1, 2, 2, true, 64><<<g64, 256, 0, s>>>(p);
         else conv_gather_bf16_kernel<1, 1, 2, 2, true><<<g64, 256, 0, s>>>(p);
         return true;
     }
@@ -393,7 +391,7 @@ void launch_gather(const GatherP& p, hipStream_t s) {
     if (p.Cout <= 32) {
         dim3 grid((unsigned)((Mtot + 127) / 128), 1);
         conv_gather_kernel<CT, 1, 1, 4, 1><<<grid, 256, 0, s>>>(p);
-    } else if (p.Cout % 128 == 0 && sizeof(CT) == 2 && !getenv("HULC_GATHER_N64")) {
+    } else if (p.Cout % 128 == 0 && sizeof(CT) == 2) {
         // the ResNet trunk's wide layers: a 128 x 128 tile halves the LDS bytes per MFMA (each wave owns 64 x 64)
         dim3 grid((unsigned)((Mtot + 127) / 128), p.Cout / 128);
         conv_gather_kernel<CT, 2, 2, 2, 2><<<grid, 256, 0, s>>>(p);
@@ -764,7 +762,7 @@ extern "C" int hulc_conv2d_padded_fwd(const hulc_conv_desc* d, int pad, const vo
     g.ldw = (long)g.ntaps << g.inner_log2;
     // 64 -> 64, 3 x 3, stride 1 (ResNet layer1): the LDS-band kernel stages every input row once instead of gathering it nine times
     if (d->compute == HULC_BF16 && d->Cin == 64 && d->Cout == 64 && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->x_dtype == HULC_BF16 &&
-        d->y_dtype == HULC_BF16 && d->w_dtype == HULC_BF16 && !getenv("HULC_NO_BAND_PADDED")) {
+        d->y_dtype == HULC_BF16 && d->w_dtype == HULC_BF16) {
         int cOH[4], cOW[4], cco[4]; long cyo[4], cw0[4], ctap[4 * 16];
         for (int c = 0; c < 2; ++c) {
             cOH[c] = g.OH; cOW[c] = g.OW; cyo[c] = 0; cco[c] = 32 * c; cw0[c] = 32 * c;
@@ -819,7 +817,7 @@ extern "C" int hulc_conv2d_bwd_data(const hulc_conv_desc* d, const void* dy, con
     const int OH = (d->H - d->KH) / d->stride + 1, OW = (d->W - d->KW) / d->stride + 1, s = d->stride;
     const int xsz = d->x_dtype == HULC_F32 ? 4 : 2;
     // LDS-band kernel: all stride^2 parity classes x Cin/32 channel tiles in ONE launch sharing one staged dY band
-    if (d->compute == HULC_BF16 && !getenv("HULC_NO_BAND_DGRAD") && d->Cin % 32 == 0 && d->KH % s == 0 && d->KW % s == 0) {
+    if (d->compute == HULC_BF16 && d->Cin % 32 == 0 && d->KH % s == 0 && d->KW % s == 0) {
         const int U = d->KH / s, V = d->KW / s, tiles = d->Cin / 32, nset = s * s * tiles;
         if (nset <= 4 && U * V <= 16) {
             int cOH[4], cOW[4], cco[4]; long cyo[4], cw0[4], ctap[4 * 16];

@@ -22,9 +22,7 @@ struct C1P {
     int w_dtype, y_dtype, relu;
     int Nimg, H, W, OH, OW, R;
     unsigned* bits;                              // optional ReLU sign plane: one dword per output pixel (bit c = channel c > 0)
-    int sweep;                                   // unit order: 0 = a workgroup walks whole frames, 1 = the grid sweeps memory in address order
     long ldw;
-    int dbg;
     int u8, pad; const int* shift; const int* fidx;   // uint8 NHWC source with the shift / scale / normalise transforms applied while staging
     const void* X2; int nsplit;                  // fp32 frames: frames n >= nsplit come from X2 (pre-offset by -nsplit frames); X2 == X when unused
     const void* const* xs; const void* const* xs2;   // optional device slots holding the frame tensors' addresses (fp32 frames; xs2 un-offset): read at kernel start
@@ -58,11 +56,7 @@ __global__ __launch_bounds__(512, X3 ? 2 : 4) void conv1_band_kernel(C1P p) {   
     }
     // a workgroup walks whole frames (blockIdx, blockIdx + grid, ...), band after band: the 4 halo rows a band shares with its
     // predecessor were read by this CU a moment ago and come back from L2, so small bands (few staging registers) cost no HBM traffic
-    // sweep order (HULC_CONV1_SWEEP=1, experiment): unit u of the launch = (frame u / bands, band u % bands), workgroup w takes w, w + grid, ...
-    // — at any moment the grid reads one compact window of a few dozen frames instead of one stream per workgroup 480 KB apart
-    const int total_units = p.Nimg * bands;
-    const int nunits = p.sweep ? (total_units - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x
-                               : ((p.Nimg - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x) * bands;     // this workgroup's units
+    const int nunits = ((p.Nimg - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x) * bands;     // this workgroup's units
     const int rows_max = (p.R - 1) * S + TH;
     const int PP = (rows_max * p.W + 7) / 8 * 8;                 // plane pitch (elements)
 
@@ -88,9 +82,8 @@ __global__ __launch_bounds__(512, X3 ? 2 : 4) void conv1_band_kernel(C1P p) {   
     uint32_t uraw[U8 ? XCH * 8 : 1];                          // (uint8 frames: plain dwords — packing a dwordx3 + dword into float4 tuples made the compiler
                                                              //  copy registers right behind the loads, i.e. wait for every load where it was issued)
     auto unit_geom = [&](int unit, int& n, int& r0, int& R, int& rows) {
-        int b = unit % bands;
+        const int b = unit % bands;
         n = blockIdx.x + (unit / bands) * gridDim.x;
-        if (p.sweep) { const int g = blockIdx.x + unit * gridDim.x; n = g / bands; b = g - n * bands; }
         r0 = b * p.R; R = (r0 + p.R <= p.OH) ? p.R : p.OH - r0; rows = (R - 1) * S + TH;
     };
     // (uint8 frames) per-frame parameters — augmentation shift, frame index — of this workgroup's first MAXU units, read once into LDS: as global
@@ -114,11 +107,10 @@ __global__ __launch_bounds__(512, X3 ? 2 : 4) void conv1_band_kernel(C1P p) {   
         __syncthreads();
     }
     // a unit's geometry is carried from unit to unit (next band of the frame, or the first band of the workgroup's next frame): as
-    // unit / bands and unit % bands it was two scalar division sequences in front of every unit's loads (sweep order keeps the divisions)
+    // unit / bands and unit % bands it was two scalar division sequences in front of every unit's loads
     struct Geo { int n, r0, R, rows; };
     auto geo_next = [&](int unit_next, const Geo& g) -> Geo {
         Geo o;
-        if (p.sweep) { unit_geom(unit_next, o.n, o.r0, o.R, o.rows); return o; }
         const int b1 = g.r0 + p.R;
         const bool wrapf = b1 >= p.OH;
         o.n = wrapf ? g.n + (int)gridDim.x : g.n;
@@ -234,8 +226,8 @@ __global__ __launch_bounds__(512, X3 ? 2 : 4) void conv1_band_kernel(C1P p) {   
         // (uint8 frames: the prefetch is unconditional — after the last unit it re-reads that unit's band, from L2, into registers nobody uses.  With
         //  the previous unit's values flowing around a skipped prefetch the register allocator copied loaded dwords into the loop-carried registers
         //  right behind each load: a wait for the load where it was issued)
-        if (U8) { if (!(p.dbg & 2)) { if (next < nunits) stage_load(next, gn); else stage_load(unit, gc); } }
-        else if (next < nunits && !(p.dbg & 2)) stage_load(next, gn);
+        if (U8) { if (next < nunits) stage_load(next, gn); else stage_load(unit, gc); }
+        else if (next < nunits) stage_load(next, gn);
         // this lane's A-operand fragments (output channel r, half h of every k-step) live in registers over the unit's tiles only: re-read per
         // unit (12 LDS reads against 36+ fragment reads), they do not sit on the register budget while the next band is converted
         // this lane's A-operand fragments (output channel r, half h of every k-step) live in registers over the unit's tiles only: re-read per
@@ -247,7 +239,7 @@ __global__ __launch_bounds__(512, X3 ? 2 : 4) void conv1_band_kernel(C1P p) {   
         }
         const int n = gc.n, r0 = gc.r0, R = gc.R;
         const int npix = R * p.OW, ntiles = (npix + 31) / 32;
-        for (int t = wave; t < ((p.dbg & 1) ? 0 : ntiles); t += 8) {
+        for (int t = wave; t < ntiles; t += 8) {
             const int q = t * 32 + r;
             const int qc = q < npix ? q : npix - 1;
             const int oy = fast_div(qc, inv_OW), ox = qc - oy * p.OW;
@@ -334,7 +326,7 @@ __global__ __launch_bounds__(512, X3 ? 2 : 4) void conv1_band_kernel(C1P p) {   
             }
         }
         __syncthreads();
-        if (next < nunits && !(p.dbg & 2)) stage_store(next, gn);
+        if (next < nunits) stage_store(next, gn);
         __syncthreads();
         gc = gn;
     }
@@ -346,8 +338,7 @@ int launch_conv1(C1P& p, hipStream_t s) {
     auto lds_of = [&](int R) -> long { const long rows = (R - 1) * 4 + 8; return (1 + x3) * 32 * (192 * 2 + 16) + 128 + (1 + x3) * 3 * ((rows * p.W + 7) / 8 * 8) * 2 + 64 + (p.u8 ? 256 * 16 : 0); };
     auto fits = [&](int R) -> bool {
         const long rows = (R - 1) * 4 + 8;
-        static const bool tall = !(getenv("HULC_CONV1_U8_TALL") && atoi(getenv("HULC_CONV1_U8_TALL")) == 0);
-        return lds_of(R) <= (160 * 1024 - 256) / 2 && (rows * p.W + 7) / 8 * ((p.u8 && tall) ? 1 : 3) <= (long)(p.u8 ? UX : XCH) * 512;
+        return lds_of(R) <= (160 * 1024 - 256) / 2 && (rows * p.W + 7) / 8 * (p.u8 ? 1 : 3) <= (long)(p.u8 ? UX : XCH) * 512;
     };
     int R = p.OH;
     while (R > 1 && !fits(R)) --R;
@@ -359,9 +350,7 @@ int launch_conv1(C1P& p, hipStream_t s) {
     // table of per-frame parameters holds and the direct loads behind the table are exercised
     const int slots = getenv("HULC_CONV1_SLOTS") && atoi(getenv("HULC_CONV1_SLOTS")) > 0 ? atoi(getenv("HULC_CONV1_SLOTS")) : 512;
     const int per = (p.Nimg + slots - 1) / slots;                // frames per workgroup
-    int grid = (p.Nimg + per - 1) / per;
-    { static const char* e = getenv("HULC_CONV1_SWEEP"); p.sweep = e ? atoi(e) : 0; }
-    if (p.sweep) { const long tu = (long)p.Nimg * bands; grid = (int)(tu < slots ? tu : slots); }
+    const int grid = (p.Nimg + per - 1) / per;
     static bool attr_set = false;
     if (!attr_set) {
         if (hipFuncSetAttribute((const void*)conv1_band_kernel<XCH, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess ||
@@ -381,14 +370,12 @@ int launch_conv1(C1P& p, hipStream_t s) {
 int hulc_conv1_band_dispatch(const float* x, const void* w, int w_dtype, long ldw, const float* bias, void* y, int y_dtype, int relu,
                              int N, int H, int W, int u8, int pad, const int* shift, const int* fidx, unsigned* relu_bits, const void* w_lo,
                              const void* x2, int n_split, const void* x_slot, const void* x2_slot, hipStream_t s) {
-    if (getenv("HULC_NO_BAND_CONV1") && !u8) return 1;
     if (w_dtype != HULC_BF16 || ((uintptr_t)w % 16) || ldw % 8) return u8 ? hulc_fail(-6, "conv1 band: bf16 weights, 16-byte aligned rows") : 1;
     if (W % 4 || ((uintptr_t)x % (u8 ? 4 : 16)) || (bias && ((uintptr_t)bias % 16)) || (H - 8) % 4 || (W - 8) % 4) return 1;
     C1P p;
     if (relu_bits && (y_dtype != HULC_BF16 || !relu)) return 1;       // (planes describe the stored bf16 ReLU output)
     if (w_lo && (u8 || (uintptr_t)w_lo % 16)) return hulc_fail(-6, "conv1 band: split operands need fp32 frames and 16-byte aligned remainders");
     p.u8 = u8; p.pad = pad; p.shift = shift; p.fidx = fidx; p.bits = relu_bits; p.Wlo = w_lo;
-    { static const char* e = getenv("HULC_C1_DBG"); p.dbg = e ? atoi(e) : 0; }
     p.X = x; p.Wt = w; p.bias = bias; p.Y = y; p.w_dtype = w_dtype; p.y_dtype = y_dtype; p.relu = relu;
     p.X2 = x; p.nsplit = N;
     p.xs = (const void* const*)x_slot; p.xs2 = (const void* const*)x2_slot;

@@ -1,5 +1,4 @@
-// conv_band.h — launch parameters shared by the LDS-band convolution kernels (conv_band.hip: 8 waves, one weight set per wave;
-// conv_band4.hip: 4 waves, every weight set in every wave).
+// conv_band.h — launch parameters shared by the LDS-band convolution kernels (conv_band.hip, conv_band_planes.hip).
 #pragma once
 #include "hulc_common.h"
 
@@ -30,8 +29,6 @@ struct BandP {
     unsigned* bits_out;             // optional: ReLU sign planes of Y (forward): dword (co / 32) * bplane + pixel, bit = channel % 32
     const unsigned* bits_in;        // optional: sign planes used as the mask (data gradient) instead of `mask`
     int bshift; long bplane;        // log2(channels of the tensor the planes describe), pixels of that tensor: planes are [channels / 32][pixels]
-    int lds_band;                   // bytes of one LDS band (the second one of the double-buffered instances starts there)
-    int dbg;                        // timing experiments (HULC_BAND_DBG): 1 skip the MFMA loop, 2 skip the output stores, 4 skip band staging
     BandCls cls[BAND_MAXCLS];
 };
 
@@ -48,8 +45,6 @@ HULC_DEVICE uint4 band_load_x(const void* X, long off) {
     return make_uint4(pack_bf16x2(a.x, a.y), pack_bf16x2(a.z, a.w), pack_bf16x2(c.x, c.y), pack_bf16x2(c.z, c.w));
 }
 
-// conv_band4.hip: 0 = launched, -1 = geometry / options not covered (the caller tries the other kernels), -2 = LDS limit could not be raised
-int launch_band4(BandP& p, int C, int NSET, int TH, int TW, int S, hipStream_t s);
 // conv_band_planes.hip (direct-to-LDS loads into a chunk-major band, 64 input channels, the static camera's frame sizes): 0 = launched, -1 = not covered
 int launch_band_planes(BandP& p, int NSET, int TH, int TW, hipStream_t s);
 

@@ -26,12 +26,7 @@ namespace {
 // C: input channels, NSET: weight sets (32 output channels each), TH x TW taps, S: input stride, MAXCH: band chunks/thread
 // BITS: 0 = no sign planes, 1 = written from the epilogue (forward), 2 = read as the ReLU mask (data gradient) — compile-time: the kernel sits
 // at the 256-VGPR limit and a run-time switch cost every instance 20-60 bytes of scratch per lane
-// DB: two LDS bands (round 4).  A unit's band is written while the PREVIOUS unit is still being multiplied — by every wave between the MFMA
-// loop and the epilogue of one of its tiles, i.e. before that tile's stores: the wait the compiler puts in front of the LDS write (vmcnt(0):
-// vector memory returns in order and the stores of the tile loop are counted with the loads) then covers the prefetch and stores that are a
-// tile old, not the write acknowledgements of the stores just issued (single band: +1.4 us per unit, HULC_BAND_DBG=2) — and one workgroup
-// barrier per unit instead of two.
-template <int C, int NSET, int TH, int TW, int S, int MAXCH, bool MULTI, bool XF32, int BITS, bool DB, bool STAMP = false>
+template <int C, int NSET, int TH, int TW, int S, int MAXCH, bool MULTI, bool XF32, int BITS, bool STAMP = false>
 __global__ __launch_bounds__(512) void conv_band_kernel(BandP p, unsigned long long* stamps = nullptr) {
     constexpr int NT = 512;
     constexpr int K = TH * TW * C, KSTEPS = K / 16;
@@ -89,8 +84,8 @@ __global__ __launch_bounds__(512) void conv_band_kernel(BandP p, unsigned long l
     auto stage_store = [&](int unit, char* band) {
         int n, fu, r0, R, rows; band_rows(unit, n, fu, r0, R, rows);
         const int npx = fu * rows * Wb;
-        // the thread id is made opaque here: inside the tile loop (double band) the compiler would otherwise compute the MAXCH LDS addresses
-        // and predicates once per unit and keep them in registers across the MFMA loops (spills at the 256-VGPR budget)
+        // the thread id is made opaque here: the compiler would otherwise compute the MAXCH LDS addresses and predicates once per unit and
+        // keep them in registers across the MFMA loops (spills at the 256-VGPR budget; found with the round-4 double-band instances)
         int t2 = tid;
         asm volatile("" : "+v"(t2));
         const int px0 = t2 / CPP, c2 = t2 % CPP;
@@ -104,7 +99,7 @@ __global__ __launch_bounds__(512) void conv_band_kernel(BandP p, unsigned long l
     // ---- prologue (round 4).  Was: every wave fetched its own 32 x K weight tile straight into registers, lane r = row r — 36 load
     // instructions per wave that each touch 32 rows (32 tag lookups for 1 KB), the same tile by every wave of a set, and the per-class tap
     // offsets as vector loads in front of them: 288 KB through the CU's L1 per workgroup and ~9.5 us before the first MFMA of a launch
-    // (HULC_BAND_DBG=32 in round 3's build; twelve such launches per step).  Now the workgroup copies the NSET x 32 x K weights ONCE,
+    // (measured in round 3 with the MFMA loop skipped; twelve such launches per step).  Now the workgroup copies the NSET x 32 x K weights ONCE,
     // coalesced (a load instruction = 64 / CPP rows of one tap, whole 64 / 128-byte runs; tap and set are wave-uniform, so the offsets
     // are scalar loads), through registers into the (still empty) band area of the LDS, rows padded by 16 bytes, and every wave picks its
     // fragments up with ds_read_b128; the first band's loads are requested in between and land while that happens.
@@ -156,17 +151,15 @@ __global__ __launch_bounds__(512) void conv_band_kernel(BandP p, unsigned long l
     unsigned long long t_ph[4] = {0, 0, 0, 0}, t_units = 0, c0 = 0, c1 = 0, c2 = 0, c3 = 0;
     for (; unit < nunits; unit += gridDim.x) {
         const int next = unit + gridDim.x;
-        const bool have_next = next < nunits && !(p.dbg & 4);
+        const bool have_next = next < nunits;
         if (STAMP) c0 = __builtin_readcyclecounter();
         // (round 6, single band) the next band's loads leave WAVE BY WAVE over the tile loop, each wave in front of its own tile slot, instead
         // of as one burst of 8 x MAXCH load instructions queueing at the CU's vector-memory path while no wave multiplies (the weight-gradient
-        // kernels' finding, tools/study/wband_stamps.py).  HULC_BAND_DBG bit 64: the burst.  With two bands the band is written early: burst.
+        // kernels' finding, tools/study/wband_stamps.py).
         // Measured: the gripper camera's small maps (several frames per unit) gain (conv2 forward 42 -> 35 us per 2048 frames, conv3 29 -> 25); the
         // static camera's conv2 forward does not (probe 170 / 170 us, inside the step 143 -> 148): staggered for the packed-frame instances only.
-        const bool stagger = MULTI && !DB && BITS != 2 && !(p.dbg & 64);
+        const bool stagger = MULTI && BITS != 2;
         if (have_next && !stagger) stage_load(next);                         // in flight during the MFMA loop below
-        char* band_next = DB ? (band == band0 ? band0 + p.lds_band : band0) : band;
-        bool staged = !DB || !have_next;
 
         int n, fu, r0, R, rows; band_rows(unit, n, fu, r0, R, rows);
         const int Rc = r0 < cl_OH ? ((r0 + R <= cl_OH) ? R : cl_OH - r0) : 0;   // this class may have fewer rows/cols
@@ -214,7 +207,6 @@ __global__ __launch_bounds__(512) void conv_band_kernel(BandP p, unsigned long l
             bf16x8_t pf[RD];
 #pragma unroll
             for (int i = 0; i < RD; ++i) pf[i] = frag(i);
-            if (!(p.dbg & 1))
 #pragma unroll
             for (int ks = 0; ks < KSTEPS; ++ks) {
                 const bf16x8_t px = pf[ks % RD];
@@ -244,9 +236,6 @@ __global__ __launch_bounds__(512) void conv_band_kernel(BandP p, unsigned long l
                     }
                     pk[g] = make_uint2(max_s16x2(pack_bf16x2(v[0], v[1]), floor2), max_s16x2(pack_bf16x2(v[2], v[3]), floor2));
                 }
-                // (double band) the next band goes to LDS here — behind the wave's SECOND MFMA loop, with the tile packed into 8 registers and
-                // BEFORE its stores: the vmcnt(0) in front of the LDS write covers the prefetch and the previous tile's stores only
-                if (DB && !staged && tile >= part + WPS) { stage_store(next, band_next); staged = true; }
 #pragma unroll
                 for (int gp = 0; gp < 2; ++gp) {
                     const auto sx = __builtin_amdgcn_permlane32_swap(pk[2 * gp].x, pk[2 * gp + 1].x, false, false);
@@ -269,7 +258,7 @@ __global__ __launch_bounds__(512) void conv_band_kernel(BandP p, unsigned long l
                         const unsigned a = nonzero_u16x2(o[0]) | (nonzero_u16x2(o[1]) << 2) | (nonzero_u16x2(o[2]) << 4) | (nonzero_u16x2(o[3]) << 6);
                         mb_out |= ((a | (a >> 15)) & 0xffu) << (16 * gp);         // even bits from the low halves, odd bits from the high halves
                     }
-                    if (live && !(p.dbg & 2)) *(uint4*)((uint16_t*)p.Y + off) = make_uint4(o[0], o[1], o[2], o[3]);
+                    if (live) *(uint4*)((uint16_t*)p.Y + off) = make_uint4(o[0], o[1], o[2], o[3]);
                 }
                 if (BITS == 1) {
                     mb_out <<= 8 * h;
@@ -278,7 +267,6 @@ __global__ __launch_bounds__(512) void conv_band_kernel(BandP p, unsigned long l
                     if (live && h == 0) p.bits_out[(long)(cl_co >> 5) * p.bplane + ((off0 - cl_co) >> p.bshift)] = mb_out;   // 32 lanes: 128 contiguous bytes
                 }
             } else {
-              if (DB && !staged && tile >= part + WPS) { stage_store(next, band_next); staged = true; }
               if (live) {
                 const long off = off0 + 4 * h;
 #pragma unroll
@@ -304,16 +292,10 @@ __global__ __launch_bounds__(512) void conv_band_kernel(BandP p, unsigned long l
         }
         if (!issued) stage_load(next);                       // (a wave without a tile in this unit)
         if (STAMP) c2 = __builtin_readcyclecounter();
-        if (DB) {
-            if (!staged) stage_store(next, band_next);       // (a wave with fewer than two tiles in this unit)
-            __syncthreads();                                 // every wave is done reading this band and has written its part of the next
-            band = band_next;
-        } else {
-            __syncthreads();                                 // every wave is done reading this band
-            if (STAMP) c3 = __builtin_readcyclecounter();
-            if (have_next) stage_store(next, band);
-            __syncthreads();
-        }
+        __syncthreads();                                     // every wave is done reading this band
+        if (STAMP) c3 = __builtin_readcyclecounter();
+        if (have_next) stage_store(next, band);
+        __syncthreads();
         if (STAMP) {
             const unsigned long long c4 = __builtin_readcyclecounter();
             t_ph[0] += c1 - c0; t_ph[1] += c2 - c1; t_ph[2] += c3 - c2; t_ph[3] += c4 - c3; t_units += 1;
@@ -327,11 +309,11 @@ __global__ __launch_bounds__(512) void conv_band_kernel(BandP p, unsigned long l
     }
 }
 
-template <int C, int NSET, int TH, int TW, int S, int MAXCH, bool XF32, int BITS, bool DB>
+template <int C, int NSET, int TH, int TW, int S, int MAXCH, bool XF32, int BITS>
 int launch_band_x(BandP& p, hipStream_t s) {
     constexpr int PS = C * 2 + 16, CPP = C / 8;
     const int Wb = (p.OWmax - 1) * S + TW;
-    const long budget = (160 * 1024 - 1024) / (DB ? 2 : 1) / 16 * 16;   // (512 B of static LDS: the bias table)
+    const long budget = (160 * 1024 - 1024) / 16 * 16;       // (512 B of static LDS: the bias table)
     const long max_px = (long)MAXCH * (512 / CPP);           // pixels one register-staged band can hold
     int R = p.OHmax;
     auto px_of = [&](int rr) { return (long)((rr - 1) * S + TH) * Wb; };
@@ -348,14 +330,13 @@ int launch_band_x(BandP& p, hipStream_t s) {
     }
     p.R = R; p.F = F;
     if ((long)F * R * p.OWmax < 128) return -1;              // a unit that cannot feed 8 waves: the gather kernel is faster
-    p.lds_band = (int)(((size_t)px_of(R) * F * PS + 15) / 16 * 16);
-    size_t lds = (size_t)p.lds_band * (DB ? 2 : 1);
+    size_t lds = ((size_t)px_of(R) * F * PS + 15) / 16 * 16;
     const size_t wbytes = (size_t)NSET * 32 * (TH * TW * C * 2 + 16);     // the prologue parks the weights in the band area
     if (lds < wbytes) lds = wbytes;
     const int per = (nunits + 255) / 256;                    // balanced persistent grid
     const int grid = (nunits + per - 1) / per;
     if (F > 1) {
-        auto kern = conv_band_kernel<C, NSET, TH, TW, S, MAXCH, true, XF32, BITS, DB>;
+        auto kern = conv_band_kernel<C, NSET, TH, TW, S, MAXCH, true, XF32, BITS>;
         static bool attr_set = false;
         if (!attr_set) {
             if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512) != hipSuccess) return -2;
@@ -363,15 +344,15 @@ int launch_band_x(BandP& p, hipStream_t s) {
         }
         kern<<<grid, 512, lds, s>>>(p, nullptr);
     } else {
-        auto kern = conv_band_kernel<C, NSET, TH, TW, S, MAXCH, false, XF32, BITS, DB>;
+        auto kern = conv_band_kernel<C, NSET, TH, TW, S, MAXCH, false, XF32, BITS>;
         static bool attr_set = false;
         if (!attr_set) {
             if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512) != hipSuccess) return -2;
             attr_set = true;
         }
         const char* se = getenv("HULC_BANDK_STAMPS");          // <device address of grid x 8 x 5 uint64>: the instrumented instance (conv2 forward)
-        if (se && *se && C == 32 && !XF32 && !DB && BITS == 1) {
-            auto kst = conv_band_kernel<C, NSET, TH, TW, S, MAXCH, false, XF32, BITS, DB, true>;
+        if (se && *se && C == 32 && !XF32 && BITS == 1) {
+            auto kst = conv_band_kernel<C, NSET, TH, TW, S, MAXCH, false, XF32, BITS, true>;
             static bool st_attr = false;
             if (!st_attr) {
                 if (hipFuncSetAttribute((const void*)kst, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512) != hipSuccess) return -2;
@@ -584,27 +565,15 @@ int launch_band_glds(BandP& p, hipStream_t s) {
 }
 
 // BITS_OK: which sign-plane role this geometry is ever launched with (1: forward conv2 writes them, 2: the data gradients read them)
-template <int C, int NSET, int TH, int TW, int S, int MAXCH, int BITS_OK, bool DB>
-int launch_band_db(BandP& p, hipStream_t s) {
+template <int C, int NSET, int TH, int TW, int S, int MAXCH, int BITS_OK>
+int launch_band(BandP& p, hipStream_t s) {
     const int want = p.bits_out ? 1 : (p.bits_in ? 2 : 0);
     if (want && want != BITS_OK) return -1;
     if (want) {
         constexpr int B = BITS_OK ? BITS_OK : 1;
-        return p.x_dtype == HULC_F32 ? launch_band_x<C, NSET, TH, TW, S, MAXCH, true, B, DB>(p, s) : launch_band_x<C, NSET, TH, TW, S, MAXCH, false, B, DB>(p, s);
+        return p.x_dtype == HULC_F32 ? launch_band_x<C, NSET, TH, TW, S, MAXCH, true, B>(p, s) : launch_band_x<C, NSET, TH, TW, S, MAXCH, false, B>(p, s);
     }
-    return p.x_dtype == HULC_F32 ? launch_band_x<C, NSET, TH, TW, S, MAXCH, true, 0, DB>(p, s) : launch_band_x<C, NSET, TH, TW, S, MAXCH, false, 0, DB>(p, s);
-}
-// MAXCH_DB: staging registers of the double-band instance — its bands are at most half the LDS, so fewer chunks per thread (and the registers
-// they would occupy are what keeps the instance from spilling the prefetch around its MFMA loops)
-template <int C, int NSET, int TH, int TW, int S, int MAXCH, int BITS_OK, int MAXCH_DB>
-int launch_band(BandP& p, hipStream_t s) {
-    static const char* e = getenv("HULC_BAND_DB");
-    const bool db = e ? atoi(e) != 0 : false;               // (measured slower on every geometry of the policy: opt-in)
-    if (db) {
-        const int rc = launch_band_db<C, NSET, TH, TW, S, MAXCH_DB, BITS_OK, true>(p, s);
-        if (rc != -1) return rc;                             // (-1: half the LDS cannot hold a useful band — single band)
-    }
-    return launch_band_db<C, NSET, TH, TW, S, MAXCH, BITS_OK, false>(p, s);
+    return p.x_dtype == HULC_F32 ? launch_band_x<C, NSET, TH, TW, S, MAXCH, true, 0>(p, s) : launch_band_x<C, NSET, TH, TW, S, MAXCH, false, 0>(p, s);
 }
 
 // a ReLU mask that comes as an activation tensor only (no sign planes): the direct-to-LDS instances read planes
@@ -621,7 +590,6 @@ int hulc_conv_band_dispatch(int C, int NSET, int TH, int TW, int S, const void* 
                             const int* cls_OH, const int* cls_OW, const long* cls_yoff, const int* cls_cobase, const long* cls_wrow0,
                             const long* cls_wtap /* [ncls][16] */, const void* add, unsigned* bits_out, const unsigned* bits_in, int bits_channels,
                             void* y16, hipStream_t s) {
-    if (getenv("HULC_NO_BAND")) return 1;
     if (ncls != NSET || ncls > BAND_MAXCLS || TH * TW > 16) return 1;
     if (y16 && ((y_dtype != HULC_F32 && y_dtype != HULC_F16) || mask || add || bits_out || bits_in)) return 1;      // (the copy rides on the plain forward only)
     if (y_dtype == HULC_F16 && !y16) return 1;
@@ -643,7 +611,6 @@ int hulc_conv_band_dispatch(int C, int NSET, int TH, int TW, int S, const void* 
     p.Nimg = N; p.H = H; p.W = W; p.pad_y = pad_y; p.pad_x = pad_x; p.R = 1; p.F = 1;
     p.x_sn = x_sn; p.x_sy = x_sy; p.x_sx = x_sx; p.y_sn = y_sn; p.y_sy = y_sy; p.y_sx = y_sx;
     p.ldw = ldw; p.relu = relu;
-    { static const char* e = getenv("HULC_BAND_DBG"); p.dbg = e ? atoi(e) : 0; }
     p.OHmax = 0; p.OWmax = 0;
     for (int c = 0; c < ncls; ++c) {
         p.cls[c].OH = cls_OH[c]; p.cls[c].OW = cls_OW[c]; p.cls[c].y_off = cls_yoff[c]; p.cls[c].co_base = cls_cobase[c];
@@ -653,42 +620,25 @@ int hulc_conv_band_dispatch(int C, int NSET, int TH, int TW, int S, const void* 
         if (cls_OW[c] > p.OWmax) p.OWmax = cls_OW[c];
     }
     int rc = 1;
-    {   // round 6: four waves per workgroup, every weight set in every wave (conv_band4.hip); HULC_BAND4=0: the kernels below only
-        const char* e4 = getenv("HULC_BAND4");              // (read per launch: the tests switch between the kernels inside one process)
-        const int band4 = e4 ? atoi(e4) : 0;
-        if (band4 && !y16) {
-            const int rc4 = launch_band4(p, C, NSET, TH, TW, S, s);
-            if (rc4 == 0) return 0;
-            if (rc4 == -2) return hulc_fail(-8, "conv band4: could not raise the dynamic LDS limit");
-        }
-    }
     if (y_dtype == HULC_F16 && !(C == 64 && S == 1 && NSET == 2 && TH == 3 && TW == 3)) return 1;
-    if (C == 32 && NSET == 2 && TH == 4 && TW == 4 && S == 2) rc = launch_band<32, 2, 4, 4, 2, 12, 1, 7>(p, s);        // conv2 forward (writes sign planes)
+    if (C == 32 && NSET == 2 && TH == 4 && TW == 4 && S == 2) rc = launch_band<32, 2, 4, 4, 2, 12, 1>(p, s);        // conv2 forward (writes sign planes)
     else if (C == 64 && S == 1 && ((NSET == 2 && TH == 3 && TW == 3) || (NSET == 4 && TH == 2 && TW == 2))) {
-        // conv3 forward / data gradient, conv2 data gradient (4 parity classes).  Frame-sized maps take the direct-to-LDS instances
-        // (conv_band_glds_kernel; HULC_BAND_GLDS=0: the register-staged kernel; small maps pack several frames into a unit there)
-        static const char* ge = getenv("HULC_BAND_GLDS");
+        // conv3 forward / data gradient, conv2 data gradient (4 parity classes).  Frame-sized maps take the direct-to-LDS instances (small
+        // maps pack several frames into a unit of the register-staged kernel).  conv3 tries the chunk-major band first (conv_band_planes.hip:
+        // fragment reads without address arithmetic; forward 70 vs 75 us per 2048 frames, data gradient 89 vs 97); conv2's data gradient
+        // measured the same on both and takes the pixel-major one (conv_band_glds_kernel).
         rc = -1;
-        {   // round 6: the chunk-major direct-to-LDS band (conv_band_planes.hip): fragment reads without address arithmetic
-            // default: conv3's forward (70 vs 75 us per 2048 frames) and data gradient (89 vs 97); conv2's data gradient measures the same on
-            // both kernels and stays; HULC_BAND_PLANES=1: every geometry it covers, =0: none
-            const char* pe = getenv("HULC_BAND_PLANES");       // (read per launch: the tests switch inside one process)
-            const int want = pe ? atoi(pe) : -1;
-            const bool conv3 = NSET == 2 && TH == 3 && TW == 3;    // (forward: 70 vs 75 us with its loads spread over the tile loop)
-            if ((want == 1 || (want == -1 && conv3)) && !(ge && !atoi(ge))) rc = launch_band_planes(p, NSET, TH, TW, s);
-        }
+        if (NSET == 2 && TH == 3 && TW == 3) rc = launch_band_planes(p, NSET, TH, TW, s);
         if (rc == -1 && y_dtype == HULC_F16) return 1;       // (the fp16 twin is stored by the direct-to-LDS kernel only)
-        if (rc == -1) {
         const bool contiguous = x_sx == 64 && x_sy == (long)W * 64 && x_sn == (long)H * W * 64 && ((uintptr_t)x % 16) == 0;
-        if (!(ge && !atoi(ge)) && !mask_only(mask, bits_in) && !add && !bits_out && x_dtype == HULC_BF16 && y_dtype == HULC_BF16 && contiguous &&
-            (long)p.OHmax * p.OWmax >= 256 && !p.dbg) {
+        if (rc == -1 && !mask_only(mask, bits_in) && !add && !bits_out && x_dtype == HULC_BF16 && y_dtype == HULC_BF16 && contiguous &&
+            (long)p.OHmax * p.OWmax >= 256) {
             const bool padded = pad_y != 0 || pad_x != 0;
             if (NSET == 2 && !padded && !bits_in) rc = launch_band_glds<2, 3, 3, 0, false>(p, s);
             else if (NSET == 2 && padded && bits_in) rc = launch_band_glds<2, 3, 3, 2, true>(p, s);
             else if (NSET == 4 && padded && bits_in) rc = launch_band_glds<4, 2, 2, 2, true>(p, s);
         }
-        }
-        if (rc == -1) rc = NSET == 2 ? launch_band<64, 2, 3, 3, 1, 10, 2, 9>(p, s) : launch_band<64, 4, 2, 2, 1, 12, 2, 9>(p, s);
+        if (rc == -1) rc = NSET == 2 ? launch_band<64, 2, 3, 3, 1, 10, 2>(p, s) : launch_band<64, 4, 2, 2, 1, 12, 2>(p, s);
     }
     else return 1;
     if (rc == -1) return 1;                      // band does not fit: gather kernel

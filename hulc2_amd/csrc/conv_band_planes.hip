@@ -1,7 +1,7 @@
 // conv_band_planes.hip — the direct-to-LDS band convolution with a CHUNK-MAJOR band (round 6).
 //
 // reference arithmetic: nn.Conv2d(+ReLU) of hulc2/models/perceptual_encoders/vision_network.py:41-46 (conv3 of the static camera) and
-// autograd's conv2d input gradient of conv3 / conv2.
+// autograd's conv2d input gradient of conv3.
 //
 // conv_band_glds_kernel (conv_band.hip) fills its band pixel-major (128-byte pixels, no padding possible: a direct load writes 1 KB of
 // consecutive LDS) and spreads the fragment reads over the banks with an XOR swizzle on the source address — which every fragment read
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(512) void conv_band_planes_kernel(BandP p, unsigned
                                                  (void __attribute__((address_space(3)))*)(band + i * 1024), 16, 0, 0);
         }
     };
-    // one of them (block i) — for the variant that spreads a wave's loads over its tile loop (SPREAD)
+    // one of them (block i) — for the instances that spread a wave's loads over its tile loop (spread)
     auto glds_one = [&](int unit, char* band, int i) {
         const uint16_t* frame = (const uint16_t*)p.X + (long)unit * p.x_sn;
         const int slot = lane >> 3, pj = lane & 7, q = i * 8 + pj;
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(512) void conv_band_planes_kernel(BandP p, unsigned
         unsigned long long c0 = 0, c1 = 0, c2 = 0, c3 = 0;
         if (STAMP) c0 = __builtin_readcyclecounter();
         if (BITS == 2 && next < nunits) mask_fetch(next);         // requested BEFORE the direct loads, parked behind the closing wait, used a unit later
-        const bool spread = (p.dbg & 256) != 0;               // (HULC_BAND_PLANES_SPREAD: a wave's direct loads between its tiles instead of up front)
+        constexpr bool spread = !PAD;                         // a wave's direct loads between its tiles instead of up front (see launch_planes)
         if (next < nunits && !spread) glds_band(next, band_next);        // lands while this unit is multiplied
         if (STAMP) c1 = __builtin_readcyclecounter();
 
@@ -281,9 +281,8 @@ int launch_planes(BandP& p, hipStream_t s) {
     const long npix = (long)p.OHmax * p.OWmax;
     if (BITS == 2 && (npix + 31) / 32 > (long)(NSET == 2 ? 6 : 12) * (8 / NSET)) return -1;      // the per-wave sign-word registers cover a unit's tiles
     const int nunits = p.Nimg, per = (nunits + 255) / 256, grid = (nunits + per - 1) / per;
-    // a wave's direct loads between its tiles instead of up front: conv3's forward 70 vs 75 us (the ~250-cycle issue of each load then falls
-    // behind MFMAs that are in flight), conv3's data gradient the same either way, conv2's 180 vs 173: default for the unpadded geometry only
-    { const char* sp = getenv("HULC_BAND_PLANES_SPREAD"); p.dbg = (sp ? atoi(sp) != 0 : !PAD) ? 256 : 0; }
+    // (the kernel spreads a wave's direct loads between its tiles for the unpadded geometry: conv3's forward 70 vs 75 us — the ~250-cycle issue
+    // of each load then falls behind MFMAs that are in flight —, conv3's data gradient the same either way, conv2's 180 vs 173)
     // HULC_BAND_STAMPS=<device address of 256 x 8 x 5 uint64>: the instrumented instance leaves, per workgroup and wave, the cycle sums of a
     // unit's phases (issue of the next band's loads | tile loop | wait for loads + store acknowledgements | barrier) and the unit count
     const char* se = getenv("HULC_BAND_STAMPS");
@@ -303,15 +302,13 @@ namespace hulc_band {
 int launch_band_planes(BandP& p, int NSET, int TH, int TW, hipStream_t s) {
     // (an fp32 Y goes with its bf16 twin Y16 — hulc_conv_desc.y_bf16 — on the forward instances)
     const bool y_ok = (p.y_dtype == HULC_BF16 && !p.Y16) || ((p.y_dtype == HULC_F32 || p.y_dtype == HULC_F16) && p.Y16 && !p.bits_in);
-    if (p.x_dtype != HULC_BF16 || !y_ok || p.w_dtype != HULC_BF16 || p.add || p.bits_out || (p.mask && !p.bits_in) || p.dbg) return -1;
+    if (p.x_dtype != HULC_BF16 || !y_ok || p.w_dtype != HULC_BF16 || p.add || p.bits_out || (p.mask && !p.bits_in)) return -1;
     if (p.x_sx != 64 || p.x_sy != (long)p.W * 64 || p.x_sn != (long)p.H * p.W * 64 || ((uintptr_t)p.X % 16) != 0) return -1;
     const bool padded = p.pad_y != 0 || p.pad_x != 0;
     if (NSET == 2 && TH == 3 && TW == 3 && !padded && !p.bits_in && p.H == 23 && p.W == 23)                          // conv3 forward
         return launch_planes<2, 3, 3, 23, 23, 0, false>(p, s);
     if (NSET == 2 && TH == 3 && TW == 3 && p.pad_y == 2 && p.pad_x == 2 && p.bits_in && p.H == 21 && p.W == 21)      // conv3 data gradient
         return launch_planes<2, 3, 3, 21, 21, 2, true>(p, s);
-    if (NSET == 4 && TH == 2 && TW == 2 && p.pad_y == 1 && p.pad_x == 1 && p.bits_in && p.H == 23 && p.W == 23)      // conv2 data gradient
-        return launch_planes<4, 2, 2, 23, 23, 2, true>(p, s);
     return -1;
 }
 

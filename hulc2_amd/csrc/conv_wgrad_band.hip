@@ -32,8 +32,6 @@ struct WBandP {
     float* partial_w;                 // [grid][Cout][K]
     float* partial_b;                 // [grid][Cout]
     int u8, pad; const int* shift; const int* fidx;   // conv1 fed by uint8 NHWC frames: shift / scale / normalise applied while staging (see conv1_band.hip)
-    int burst;                        // bf16 NHWC layers: 1 = the next unit's loads as ONE burst in front of the MFMA loop (else staggered by wave)
-    int stag_num;                     // the bursts are spread over the first stag_num / 8 of the loop
 };
 
 // C: input channels, CT: Cout / 32, TH x TW taps, S stride, NCHW: conv1 layout (k = (c, kh, kw), fp32 planes)
@@ -254,14 +252,14 @@ __global__ __launch_bounds__(512, 2 * BPC) void conv_wgrad_band_kernel(WBandP p,
         // first wave half way through it.  A load instruction of a wave is a kilobyte through the CU's one vector-memory path (~35 cycles each,
         // 120 of them per unit: tools/study/wband_stamps.py — 2300 cycles for the first wave of a SIMD, 4300 for the second, and the same
         // total when the loads are spread between the steps), and a wave queueing there issues no MFMAs: with all eight waves in one burst the
-        // matrix pipes idle meanwhile (one workgroup per CU); staggered, the other wave of the SIMD has them.  HULC_WB_BURST=1: one burst.
-        const bool pre = next < nunits, stagger = TR && !p.burst;
+        // matrix pipes idle meanwhile (one workgroup per CU); staggered, the other wave of the SIMD has them.
+        const bool pre = next < nunits, stagger = TR;
         int n, r0, R, rows, npix; unit_geom(unit, n, r0, R, rows, npix);
         const int nsteps = (npix + 15) / 16;
         // the step in front of which this wave issues its loads: every wave its own slot over the loop (the two waves of a SIMD half of it
         // apart) — a wave then pays for its own 15 loads, not for its place in a queue of 120 (conv2, 2048 frames: 139 us as one burst, 129 in
         // two half-workgroup bursts, 122 / 116 / 114 with the slots over 5/8, 7/8, all of the loop; the last wave's data still arrives in time)
-        const int bat = stagger ? ((wave * ((nsteps * p.stag_num) >> 3)) >> 3) & ~1 : 0;
+        const int bat = stagger ? ((wave * nsteps) >> 3) & ~1 : 0;
         if (pre && !stagger) stage_load(next);
         if (STAMP) c1 = __builtin_readcyclecounter();
 
@@ -479,7 +477,6 @@ struct W1P {
     long dy_sn, dy_sy, dy_sx;
     float* partial_w; float* partial_b;
     int u8, pad; const int* shift; const int* fidx;
-    int dbg;
     const void* X2; int nsplit;             // fp32 frames: frames n >= nsplit come from X2 (pre-offset by -nsplit frames); X2 == X when unused
     const void* const* xs; const void* const* xs2;   // optional device slots holding the frame tensors' addresses (see conv1_band.hip)
 };
@@ -735,11 +732,11 @@ __global__ __launch_bounds__(512, 4) void conv1_wgrad_kernel(W1P p, unsigned lon
         const int next = unit + 1;
         if (STAMP) c0 = __builtin_readcyclecounter();
         const Geo gn = geo_next(gc);
-        if (next < nunits && !(p.dbg & 8)) stage_load(next, gn);
+        if (next < nunits) stage_load(next, gn);
         if (STAMP) c1 = __builtin_readcyclecounter();
 
         const int R = gc.R;
-        if ((live || biasw) && !(p.dbg & 1)) {
+        if (live || biasw) {
             const int nblk = R * nbx, nsteps = (nblk + 1) / 2;
             // this lane half's pixel block b = 2 * s + h as (row, column bx) — only its X offset `xo` is kept: + 32 bytes per step, one row of
             // planes further when the column wraps.  An odd block count leaves the last step's second block empty: its dY^T slots are zero
@@ -946,12 +943,8 @@ int launch_wband(WBandP& p, float* dw, float* db, void* ws, long ws_bytes, int d
 int hulc_conv_wgrad_band_dispatch(int nchw, int Cin, int Cout, int KH, int KW, int S, const void* x, int x_dtype, const void* dy, int dy_dtype,
                                   int N, int H, int W, float* dw, float* db, void* ws, long ws_bytes, int dw_oihw, int accumulate, int u8, int pad,
                                   const int* shift, const int* fidx, const void* x2, int n_split, const void* x_slot, const void* x2_slot, hipStream_t s) {
-    if (getenv("HULC_NO_BAND_WGRAD") && !u8) return 1;
     WBandP p;
     p.u8 = u8; p.pad = pad; p.shift = shift; p.fidx = fidx;
-    // (read per launch: the tests switch between the arrangements inside one process)
-    { const char* e = getenv("HULC_WB_BURST"); p.burst = e && atoi(e); }
-    { const char* e = getenv("HULC_WB_STAG"); p.stag_num = e ? atoi(e) : 8; }
     p.X = x; p.dY = dy; p.x_dtype = x_dtype; p.dy_dtype = dy_dtype;
     p.Nimg = N; p.H = H; p.W = W; p.OH = (H - KH) / S + 1; p.OW = (W - KW) / S + 1; p.R = 1; p.F = 1;
     if (nchw) { p.x_sn = (long)Cin * H * W; p.x_sc = (long)H * W; p.x_sy = W; p.x_sx = 1; }
@@ -966,11 +959,11 @@ int hulc_conv_wgrad_band_dispatch(int nchw, int Cin, int Cout, int KH, int KW, i
         rc = pure16 ? launch_wband<32, 2, 4, 4, 2, false, 10, 5, 1, true>(p, dw, db, ws, ws_bytes, dw_oihw, accumulate, s)
                     : launch_wband<32, 2, 4, 4, 2, false, 10, 5, 1>(p, dw, db, ws, ws_bytes, dw_oihw, accumulate, s);
     else if (nchw && Cin == 3 && Cout == 32 && KH == 8 && KW == 8 && S == 4 && (x_dtype == HULC_F32 || (u8 && W % 4 == 0 && (uintptr_t)x % 4 == 0))) {
-        if (x2 && (dy_dtype != HULC_BF16 || n_split < 0 || n_split > N || ((uintptr_t)x2 % (u8 ? 4 : 16)) || (u8 && fidx) || getenv("HULC_CONV1_WGRAD_OLD")))
+        if (x2 && (dy_dtype != HULC_BF16 || n_split < 0 || n_split > N || ((uintptr_t)x2 % (u8 ? 4 : 16)) || (u8 && fidx)))
             return hulc_fail(-6, "conv1 weight gradient: x2 needs a bf16 gradient map, 0 <= n_split <= N, 16-byte (uint8 frames: 4-byte) alignment, no frame_index");
-        if ((x_slot || x2_slot) && (getenv("HULC_CONV1_WGRAD_OLD") || dy_dtype != HULC_BF16))
+        if ((x_slot || x2_slot) && dy_dtype != HULC_BF16)
             return hulc_fail(-6, "conv1 weight gradient: frame slots need the phase-plane kernel (bf16 gradient map)");
-        if (getenv("HULC_CONV1_WGRAD_OLD") || dy_dtype != HULC_BF16) rc = launch_wband<3, 1, 8, 8, 4, true, 6, 4, 2>(p, dw, db, ws, ws_bytes, dw_oihw, accumulate, s);
+        if (dy_dtype != HULC_BF16) rc = launch_wband<3, 1, 8, 8, 4, true, 6, 4, 2>(p, dw, db, ws, ws_bytes, dw_oihw, accumulate, s);
         else {
             W1P q;
             q.X = x; q.dY = dy; q.dy_dtype = dy_dtype; q.Nimg = N; q.H = H; q.W = W; q.OH = p.OH; q.OW = p.OW;
@@ -984,7 +977,6 @@ int hulc_conv_wgrad_band_dispatch(int nchw, int Cin, int Cout, int KH, int KW, i
                 q.X2 = u8 ? (const float*)((const unsigned char*)x2 - (long)n_split * 3 * H * W) : (const float*)x2 - (long)n_split * 3 * H * W;
                 q.nsplit = n_split;
             }
-            q.dbg = getenv("HULC_W1_DBG") ? atoi(getenv("HULC_W1_DBG")) : 0;
             rc = launch_conv1_wgrad(q, dw, db, ws, ws_bytes, accumulate, s);
         }
     }

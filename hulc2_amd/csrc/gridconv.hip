@@ -353,16 +353,14 @@ static int gridconv_launch(const void* x, long ldx, const void* wt, void* y, lon
     const unsigned gx = (unsigned)((R + GC_BM - 1) / GC_BM);
     hipStream_t s = (hipStream_t)stream;
     // thin layers: persistent workgroups with the filter in registers (gridconv_thin_kernel)
-    static const int thin = getenv("HULC_GRIDCONV_THIN") ? atoi(getenv("HULC_GRIDCONV_THIN")) : 1;
-    if (thin && ldy % 8 == 0 && (!y || (uintptr_t)y % 16 == 0) && ((Cin == 32 && (Cout == 32 || Cout == 64)) || (Cin == 64 && (Cout == 32 || (thin > 1 && Cout == 64))))) {
+    if (ldy % 8 == 0 && (!y || (uintptr_t)y % 16 == 0) && ((Cin == 32 && (Cout == 32 || Cout == 64)) || (Cin == 64 && Cout == 32))) {
         static int ncu_cached = 0;                                  // (one device model per process: the count is asked once)
         if (!ncu_cached) {
             int dev = 0, n = 0;
             if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
             ncu_cached = n;
         }
-        static const int occ3 = getenv("HULC_GRIDCONV_THIN_OCC3") ? atoi(getenv("HULC_GRIDCONV_THIN_OCC3")) : 1;
-#define GT_LAUNCH(CINv, NBv, GYv, OCCv)                                                                                \
+#define GT_LAUNCH(CINv, NBv, OCCv)                                                                                     \
         {                                                                                                              \
             auto kern = gridconv_thin_kernel<CINv, NBv, OCCv>;                                                         \
             const int wgs = ((OCCv * ncu_cached + 7) / 8) * 8;     /* OCC per CU, a multiple of the 8 XCDs */          \
@@ -373,18 +371,16 @@ static int gridconv_launch(const void* x, long ldx, const void* wt, void* y, lon
                     return hulc_fail(-8, "hulc_gridconv3x3: could not raise the dynamic LDS limit (thin)");            \
                 attr = true;                                                                                           \
             }                                                                                                          \
-            kern<<<dim3(wgs, GYv), 256, lds, s>>>(p, (int)gx);                                                         \
+            kern<<<wgs, 256, lds, s>>>(p, (int)gx);                                                                    \
         }
-        if (Cin == 32 && Cout == 32) { if (occ3) GT_LAUNCH(32, 1, 1, 3) else GT_LAUNCH(32, 1, 1, 2) }
-        else if (Cin == 32) GT_LAUNCH(32, 2, 1, 2)
-        else if (Cout == 32) GT_LAUNCH(64, 1, 1, 2)
-        else GT_LAUNCH(64, 1, 2, 2)
+        if (Cin == 32 && Cout == 32) GT_LAUNCH(32, 1, 3)
+        else if (Cin == 32) GT_LAUNCH(32, 2, 2)
+        else GT_LAUNCH(64, 1, 2)
 #undef GT_LAUNCH
         return hulc_check_launch("hulc_gridconv3x3 (thin)");
     }
     // k-steps of 64 channels (half the barriers per MFMA) where the channel count allows and the layer is not a thin HBM-bound one
-    static const int k64 = getenv("HULC_GRIDCONV_K64") ? atoi(getenv("HULC_GRIDCONV_K64")) : 1;
-    const bool wide = k64 && Cin % 64 == 0 && Cin >= 128;
+    const bool wide = Cin % 64 == 0 && Cin >= 128;
 #define GC_LAUNCH(WNv, TNv, KCHv, BNv)                                                                                 \
     {                                                                                                                  \
         auto kern = gridconv_kernel<WNv, TNv, KCHv>;                                                                   \
@@ -399,8 +395,7 @@ static int gridconv_launch(const void* x, long ldx, const void* wt, void* y, lon
     }
     // 128-channel k-steps for the layers that put at most one 128 x 128 workgroup on a CU (512-channel maps at 14 x 14): nothing overlaps a
     // workgroup's barriers there, so fewer, longer k-steps
-    static const int k128 = getenv("HULC_GRIDCONV_K128") ? atoi(getenv("HULC_GRIDCONV_K128")) : 1;
-    if (k128 && Cout % 128 == 0 && Cin % 128 == 0 && Cin >= 256 && (long)gx * (Cout / 128) <= 320) GC_LAUNCH(2, 2, 4, 128)
+    if (Cout % 128 == 0 && Cin % 128 == 0 && Cin >= 256 && (long)gx * (Cout / 128) <= 320) GC_LAUNCH(2, 2, 4, 128)
     else if (Cout % 128 == 0) { if (wide) GC_LAUNCH(2, 2, 2, 128) else GC_LAUNCH(2, 2, 1, 128) }
     else if (Cout % 64 == 0) { if (wide) GC_LAUNCH(1, 2, 2, 64) else GC_LAUNCH(1, 2, 1, 64) }
     else { if (wide) GC_LAUNCH(1, 1, 2, 32) else GC_LAUNCH(1, 1, 1, 32) }

@@ -36,7 +36,7 @@ struct TItem {
     int mstore;                              // rows m < mstore are stored (the one-channel head padded to 32 output channels)
     long slab0;                              // first slab (split items)
 };
-struct TapsP { int first[MAXI]; int rfirst[MAXI]; TItem it[MAXI]; int n; float* slabs; int dbg; };
+struct TapsP { int first[MAXI]; int rfirst[MAXI]; TItem it[MAXI]; int n; float* slabs; };
 
 typedef short v4s __attribute__((ext_vector_type(4)));
 typedef v4s __attribute__((address_space(3))) * lds_v4s;
@@ -130,9 +130,9 @@ HULC_DEVICE void taps_unit(const TItem& it, const TapsP& p, int local, char* sme
     __syncthreads();
     for (int st = step0; st + 1 < step1; ++st) {
         const int cur = (st - step0) & 1;
-        if (!(p.dbg & 1)) TP_LOAD(st + 1)
+        TP_LOAD(st + 1)
         __builtin_amdgcn_sched_barrier(0);
-        if (!(p.dbg & 2)) TP_MMA(cur)
+        TP_MMA(cur)
         __builtin_amdgcn_sched_barrier(0);
         TP_STORE(cur ^ 1, st + 1)
         __syncthreads();
@@ -185,8 +185,8 @@ HULC_DEVICE void taps_unit(const TItem& it, const TapsP& p, int local, char* sme
         for (int e = 0; e < 16; ++e) slab[(u * 16 + e) * 64 + lane] = acc[u][e];
 }
 
-template <int OCC>     // workgroups per CU the register budget allows: 2 -> at most 256 registers per lane
-__global__ __launch_bounds__(256, OCC) void wgrad_taps_kernel(TapsP p) {
+// two workgroups per CU: at most 256 registers per lane
+__global__ __launch_bounds__(256, 2) void wgrad_taps_kernel(TapsP p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // runs of 8 consecutive units (slices of one tile: neighbouring rows, overlapping dy windows) share an XCD and its L2
     const int g = blockIdx.x >> 3;
@@ -249,8 +249,7 @@ TPlan plan_taps(const hulc_wgrad_item& d) {
     pl.mode = (d.M == 32 ? 1 : 0) | (d.N == 32 ? 2 : 0);
     pl.kp = pl.mode == 0 ? 1 : (pl.mode == 3 ? 4 : 2);
     const int nsteps = (d.K + T - 1) / T;
-    static const int per = getenv("HULC_WGRAD_TAPS_KPER") ? atoi(getenv("HULC_WGRAD_TAPS_KPER")) : 64;
-    int want = (nsteps + per * pl.kp - 1) / (per * pl.kp);                 // ~64 k-steps of nine-tap MFMAs per wave and unit
+    int want = (nsteps + 64 * pl.kp - 1) / (64 * pl.kp);                   // ~64 k-steps of nine-tap MFMAs per wave and unit
     if (nsteps <= 160 && pl.tiles >= 32) want = 1;                         // many tiles, few rows: no slabs at all
     if (want > 128) want = 128;
     if (want < 1) want = 1;
@@ -264,8 +263,7 @@ TPlan plan_taps(const hulc_wgrad_item& d) {
 
 // ---- internal interface of hulc_wgrad_group (wgrad_group.hip): the conv_taps_wp items this file takes
 int hulc_wgrad_taps_takes(const hulc_wgrad_item* d) {
-    static const bool off = getenv("HULC_NO_WGRAD_TAPS") != nullptr;
-    if (off || d->conv_taps_wp <= 0) return 0;
+    if (d->conv_taps_wp <= 0) return 0;
     if (d->a_dtype != HULC_BF16 || d->b_dtype != HULC_BF16 || d->rowsum || d->col_perm || d->col_mul != 9) return 0;
     if (!((d->M % T == 0) || d->M == 32) || !((d->N % T == 0) || d->N == 32) || d->K % 32 || d->K < T) return 0;
     if (d->lda % 8 || d->ldb % 8 || ((uintptr_t)d->A | (uintptr_t)d->B) % 16) return 0;
@@ -282,11 +280,9 @@ long hulc_wgrad_taps_workspace(const hulc_wgrad_item* const* items, int n) {
 }
 
 int hulc_wgrad_taps_launch(const hulc_wgrad_item* const* items, int n, void* slabs, hipStream_t s) {
-    static const int occ = getenv("HULC_WGRAD_TAPS_OCC") ? atoi(getenv("HULC_WGRAD_TAPS_OCC")) : 2;
     static bool attr = false;
     if (!attr) {
-        if (hipFuncSetAttribute((const void*)wgrad_taps_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE_B + 2 * RS) != hipSuccess ||
-            hipFuncSetAttribute((const void*)wgrad_taps_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE_B + 2 * RS) != hipSuccess)
+        if (hipFuncSetAttribute((const void*)wgrad_taps_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE_B + 2 * RS) != hipSuccess)
             return hulc_fail(-8, "hulc_wgrad_group: could not raise the dynamic LDS limit (taps)");
         attr = true;
     }
@@ -298,7 +294,6 @@ int hulc_wgrad_taps_launch(const hulc_wgrad_item* const* items, int n, void* sla
         TapsP p;
         p.n = n - base < MAXI ? n - base : MAXI;
         p.slabs = (float*)slabs;
-        p.dbg = getenv("HULC_TAPS_DBG") ? atoi(getenv("HULC_TAPS_DBG")) : 0;      // timing probes: 1 no global loads, 2 no MFMAs (results are wrong)
         int first = 0, rfirst = 0;
         for (int j = 0; j < MAXI; ++j) p.first[j] = p.rfirst[j] = 0x7fffffff;
         for (int j = 0; j < p.n; ++j) {
@@ -319,8 +314,7 @@ int hulc_wgrad_taps_launch(const hulc_wgrad_item* const* items, int n, void* sla
             for (int j = p.n - 1; j >= 0; --j) { if (p.rfirst[j] == 0x7fffffff) p.rfirst[j] = run; else run = p.rfirst[j]; }
         }
         const int total = (first + 63) / 64 * 64;
-        if (occ == 1) wgrad_taps_kernel<1><<<total, 256, 2 * STAGE_B + 2 * RS, s>>>(p);
-        else wgrad_taps_kernel<2><<<total, 256, 2 * STAGE_B + 2 * RS, s>>>(p);
+        wgrad_taps_kernel<<<total, 256, 2 * STAGE_B + 2 * RS, s>>>(p);
         if (rfirst > 0) wgrad_taps_reduce_kernel<<<rfirst, 1024, 0, s>>>(p);
     }
     return hulc_check_launch("hulc_wgrad_group (taps)");

@@ -243,21 +243,6 @@ class FlattenLinearFn(torch.autograd.Function):
         O = W.shape[0]
         ctx.a_dtype = a.dtype
         chw = (a.shape[3], a.shape[1], a.shape[2])
-        if kn.exact_site_in_bf16_step() and a.dtype == torch.bfloat16 and os.environ.get("HULC_FLATLIN_X2"):
-            # OPT-IN (HULC_FLATLIN_X2=1; round 5): the exact-forward site "encfc" behind a bf16 conv stack as two bf16 MFMA GEMMs, a w_hi + a w_lo
-            # (the activation IS bf16: nothing to split), on the trainer's layout shadows — instead of a cast copy of the activation, a per-step
-            # fp32 relayout of the weight and an fp32-MFMA GEMM (38 + 9 + 5 us per step).  Off by default: the 2^-17 weight remainder it drops
-            # moved one recorded gradient error of the B = 2 parity case past its 1.5 x ratchet (tests/golden/error_budget.json), and the
-            # recorded errors are not re-recorded for a 0.8 % step-time gain
-            x2 = _c(a).reshape(N, K)
-            out = _f32(N, O, like=x2)
-            with kn.compute_scope("bf16", fwd_only=True):
-                part = _f32(N, O, like=x2)
-                kn.gemm(x2, weight_operand(W, "hwc_lo", chw=chw), part, N, O, K, K, K, O)
-                kn.gemm(x2, weight_operand(W, "hwc", chw=chw), out, N, O, K, K, K, O, bias=b, add=part, ld_add=O, relu=True)
-            ctx.save_for_backward(x2, out, W, b)
-            ctx.ashape = a.shape
-            return out
         if kn.get_compute() != "bf16" and a.dtype == torch.bfloat16:
             # an exact-fp32 site behind a bf16 conv stack (HULC_FP32_SITES "encfc"): the fp32 GEMM takes fp32 operands — the stack's own
             # exact map when it kept one (site "a3"), else a cast copy of the bf16 map
@@ -419,8 +404,8 @@ def _conv1_pair_ok(xs, u8, bits, cout, shifts=None, indices=None) -> bool:
 
 def _pair_not_covered(e: Exception) -> bool:
     """the library's answer to a two-tensor conv1 launch (hulc_conv_desc.x2) on a geometry its band kernels do not take — small frames
-    (W <= 40: fewer than two 8-pixel blocks per output row), LDS / workspace limits, HULC_NO_BAND_WGRAD: nothing was launched, the caller
-    runs the per-input loop instead"""
+    (W <= 40: fewer than two 8-pixel blocks per output row), LDS / workspace limits: nothing was launched, the caller runs the per-input
+    loop instead"""
     return "(x2) is taken by the conv1 band kernel only" in str(e)
 
 
@@ -474,7 +459,7 @@ class ConvStackFn(torch.autograd.Function):
             # bytes: an fp32 twin's 16-byte pieces at 256-byte pixel pitch cost conv3's launch 48 us per 2048 frames and the softmax twice the
             # bytes —, the gripper camera's small map (the exact-fp32 flatten-linear's operand) an fp32 one
             twin = a3_exact and li == 2
-            f16_twin = twin and (h, w_, cin, cout, k, s) == (23, 23, 64, 64, 3, 1) and not os.environ.get("HULC_A3_F32_TWIN")
+            f16_twin = twin and (h, w_, cin, cout, k, s) == (23, 23, 64, 64, 3, 1)
             y = torch.empty(N, oh, ow, cout, dtype=(torch.float16 if f16_twin else torch.float32) if twin else _act_dtype(), device=xs[0].device)
             y16 = torch.empty(N, oh, ow, cout, dtype=torch.bfloat16, device=xs[0].device) if twin else None
             if want_bits and li < 2 and cout % 32 == 0 and (li > 0 or cout == 32):     # (conv1 writes per input tensor: one plane, pixel-major slices)
@@ -510,7 +495,8 @@ class ConvStackFn(torch.autograd.Function):
                 except kn._L.HulcKernelError:
                     if not (twin and y.dtype == torch.float16):
                         raise
-                    # (the fp16 twin is stored by the direct-to-LDS kernel only — e.g. HULC_BAND_PLANES=0 —: the fp32 twin is served everywhere)
+                    # (the fp16 twin is stored by the direct-to-LDS kernel only, which declines e.g. a frame that is not 23 x 23 or
+                    #  not contiguous: the fp32 twin is served everywhere)
                     y = torch.empty(N, oh, ow, cout, dtype=torch.float32, device=xs[0].device)
                     kn.conv2d_fwd(inp, w2d, bs[li], y, N, h, w_, cin, cout, k, k, s, nchw, relu=True, relu_bits=bits[li], y_bf16=y16)
             dims.append((h, w_, cin, cout, k, s, nchw))

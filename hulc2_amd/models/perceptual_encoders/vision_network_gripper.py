@@ -4,7 +4,6 @@ Mirrors hulc2.models.perceptual_encoders.vision_network_gripper.VisionNetwork (r
 vision_network_gripper.py:11-26,57-89): keys conv_model.{0,2,4,7}, fc1.0, fc2, ln.  The reference's Flatten
 runs over NCHW, so the NHWC conv output is re-ordered (a 3136-float copy per frame) before the first Linear.
 """
-import os
 from typing import Tuple
 
 import torch
@@ -47,7 +46,7 @@ class VisionNetwork(nn.Module):
     def forward(self, x: torch.Tensor, aug_shift=None, aug_pad: int = 0, frame_index=None, pre_ln: bool = False) -> torch.Tensor:
         # (site "encfc": the exact-fp32 flatten-linear below gets the EXACT map — conv3 stores it next to the bf16 one, hulc_conv_desc.y_bf16)
         a3 = HF.conv_stack(x, self.conv_params(), grad_premasked=True, aug_pad=aug_pad, aug_shifts=aug_shift, frame_index=frame_index,
-                           exact_out="encfc" in kn.fp32_sites() and not os.environ.get("HULC_A3_NOTWIN"))                                                                               # (N, 7, 7, 64) NHWC
+                           exact_out="encfc" in kn.fp32_sites())                                                                               # (N, 7, 7, 64) NHWC
         # nn.Flatten + Linear(3136, 128) + ReLU on the NHWC activation in place: the weight's columns are reordered, not the activations
         c = self.conv_model
         with kn.site_scope("encfc"):         # (selective precision)

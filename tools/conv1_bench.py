@@ -1,4 +1,4 @@
-import sys, torch, os
+import sys, torch
 sys.path.insert(0, '.')
 from hulc2_amd import kernels as kn
 dev = torch.device('cuda')
@@ -18,7 +18,7 @@ for name,N,H in (("static1",1024,200),("static1x2",2048,200),("grip1",1024,84),(
     y = torch.empty(N,OH,OH,32,device=dev,dtype=torch.bfloat16)
     t = timeit(lambda: kn.conv2d_fwd(x,w2d,b,y,N,H,H,3,32,8,8,4,True,relu=True))
     byts = x.numel()*4 + y.numel()*2
-    print(f"{name:10s} conv1 fwd {t:.3f} ms  {byts/t/1e9:.2f} TB/s (algorithmic bytes)  band={'off' if os.environ.get('HULC_NO_BAND_CONV1') else 'on'}")
+    print(f"{name:10s} conv1 fwd {t:.3f} ms  {byts/t/1e9:.2f} TB/s (algorithmic bytes)")
 # uint8 NHWC frames through the same entry point
 for name,N,H in (("static1 u8",1024,200),("grip1 u8",1024,84)):
     OH = (H-8)//4+1

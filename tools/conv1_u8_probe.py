@@ -1,6 +1,5 @@
 """conv1 on uint8 NHWC frames vs fp32 NCHW frames: forward and weight gradient, 1024 static frames, graph-timed.
-HULC_W1_DBG bits (1: no MFMA loop, 8: no prefetch loads) split the weight gradient's time, HULC_C1_DBG bits (1: no tile loop, 2: no
-staging after the first band) the forward's.  HULC_LIB=<another build of the library> gives an A/B inside one gpurun call."""
+HULC_LIB=<another build of the library> gives an A/B inside one process."""
 import os, sys
 import torch
 sys.path.insert(0, '.')
@@ -36,7 +35,7 @@ b = torch.zeros(32, device=dev)
 y = torch.empty(N, OH, OW, 32, device=dev, dtype=torch.bfloat16)
 dy = torch.randn(N, OH, OW, 32, device=dev).to(torch.bfloat16)
 dw, db = torch.empty(32, 192, device=dev), torch.empty(32, device=dev)
-tag = f"N={N} dbg={os.environ.get('HULC_W1_DBG', '0')}"
+tag = f"N={N}"
 print(f"[{tag}] fwd   fp32 {gtime(lambda: kn.conv2d_fwd(xf, w, b, y, N, H, H, 3, 32, 8, 8, 4, True)):7.1f} us   "
       f"uint8 {gtime(lambda: kn.conv2d_fwd(xu, w, b, y, N, H, H, 3, 32, 8, 8, 4, True, aug_shift=sh, aug_pad=10)):7.1f} us")
 print(f"[{tag}] wgrad fp32 {gtime(lambda: kn.conv2d_bwd_weight(xf, dy, dw, db, N, H, H, 3, 32, 8, 8, 4, True)):7.1f} us   "

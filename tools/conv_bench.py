@@ -1,4 +1,4 @@
-import sys, torch, os
+import sys, torch
 sys.path.insert(0, '.')
 from hulc2_amd import kernels as kn
 dev = torch.device('cuda')
@@ -24,4 +24,4 @@ for name,N,H,W,Cin,Cout,K,s in L:
     flops = 2.0*N*OH*OW*Cout*Cin*K*K
     tf = timeit(lambda: kn.conv2d_fwd(x,w2d,b,y,N,H,W,Cin,Cout,K,K,s,False))
     td = timeit(lambda: kn.conv2d_bwd_data(dy,wt,dx,x,N,H,W,Cin,Cout,K,K,s))
-    print(f"{name:8s} band={'off' if os.environ.get('HULC_NO_BAND') else 'on '} fwd {tf:.3f} ms ({flops/tf/1e9:.0f} TF/s)  dgrad {td:.3f} ms ({flops/td/1e9:.0f} TF/s)")
+    print(f"{name:8s} fwd {tf:.3f} ms ({flops/tf/1e9:.0f} TF/s)  dgrad {td:.3f} ms ({flops/td/1e9:.0f} TF/s)")

@@ -1,6 +1,5 @@
 """Times the six NHWC conv kernels of a camera encoder (conv2 / conv3: forward with sign planes, data gradient from sign planes, weight
-gradient) at several frame counts, each launch between a cold-cache fill when COLD=1.  HULC_BAND_DBG / HULC_NO_BAND etc. are read by the
-library once per process: run one process per variant.  usage: python tools/conv_probe.py [N ...]"""
+gradient) at several frame counts, each launch between a cold-cache fill when COLD=1.  usage: python tools/conv_probe.py [N ...]"""
 import os
 import sys
 

@@ -1,6 +1,7 @@
 // How fast does ONE wave per SIMD issue v_mfma_f32_32x32x16_bf16 when its B operands come out of the LDS through a ring of prefetched
 // ds_read_b128 (consumed RD steps after they were issued, as the band kernels do) — per number of independent accumulator chains and reads per MFMA?
-// (round 6: the question behind conv_band4.hip; overlap_probe2's LDS variant consumed every read where it was issued.)
+// (round 6: the question behind a four-wave band kernel, measured slower and removed; overlap_probe2's LDS variant consumed every read where
+// it was issued.)
 #include <hip/hip_runtime.h>
 #include <cstdio>
 typedef __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16 bf16x8;

@@ -1,6 +1,6 @@
 """forked step graph vs one chain (HULC_FORK=1 / 0), three eager optimizer steps from SEED: how many parameters' gradients differ by more than 1e-5
-(relative L2) per step.  HULC_A3_NOTWIN=1: the gripper camera's flatten-linear on the bf16 map instead of the exact one.  Round 6, seeds 3 5 7 11 13:
-exact map 0/52/104, 0/0/0, 52/106/106, 0/0/0, 52/106/106 — bf16 map 0/0/0, 0/0/56, 0/0/0, 0/0/0, 0/0/0."""
+(relative L2) per step.  Round 6, seeds 3 5 7 11 13: 0/52/104, 0/0/0, 52/106/106, 0/0/0, 52/106/106 (the gripper camera's flatten-linear on
+the exact map)."""
 import os, sys
 from pathlib import Path
 ROOT = Path(__file__).resolve().parents[2]
