@@ -416,7 +416,6 @@ struct WgradP {
     float* partial_w;          // [P][Cout][K]
     float* partial_b;          // [P][Cout] or null
     long pix_per_block;        // pixels per workgroup (multiple of the reduction tile)
-    int pair_fastest;          // staging item order: consecutive lanes walk pixel pairs (1) or k-chunks (0)
 };
 
 // write two pixels' worth of one 8-wide chunk transposed into the LDS tile: element j of the chunk
@@ -477,15 +476,15 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradP p) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) bacc[j] = 0.f;
 
-    // item -> (pixel pair, chunk): consecutive threads take consecutive chunks of one pixel pair so a
-    // wave's loads cover whole contiguous channel runs.  Pixel coordinates are carried incrementally.
-    const int dy_pr = p.pair_fastest ? tid % PAIRS : tid / (CO / 8), dy_ch = p.pair_fastest ? tid / PAIRS : tid % (CO / 8);
+    // item -> (pixel pair, chunk): consecutive threads walk the pixel pairs of one chunk (conflict-light transposed LDS writes;
+    // measured faster than chunk-fastest on all six layers).  Pixel coordinates are carried incrementally.
+    const int dy_pr = tid % PAIRS, dy_ch = tid / PAIRS;
     PixIter dyit; dyit.init(mb + 2 * dy_pr < Mtot ? mb + 2 * dy_pr : Mtot - 1, g.OH, g.OW);
     PixIter xit[X_PER]; int x_pr[X_PER], x_ch[X_PER];
 #pragma unroll
     for (int q = 0; q < X_PER; ++q) {
         const int id = tid + q * 256;
-        x_pr[q] = p.pair_fastest ? id % PAIRS : id / (KS / 8); x_ch[q] = p.pair_fastest ? id / PAIRS : id % (KS / 8);
+        x_pr[q] = id % PAIRS; x_ch[q] = id / PAIRS;
         const long m = mb + 2 * x_pr[q];
         xit[q].init(m < Mtot ? m : Mtot - 1, g.OH, g.OW);
     }
@@ -570,7 +569,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradP p) {
         __syncthreads();
         if (tid < CO) {
             float sacc = 0.f;
-            for (int pr = 0; pr < PAIRS; ++pr) sacc += bpart[p.pair_fastest ? (tid / 8) * PAIRS + pr : pr * (CO / 8) + tid / 8][tid % 8];
+            for (int pr = 0; pr < PAIRS; ++pr) sacc += bpart[(tid / 8) * PAIRS + pr][tid % 8];
             p.partial_b[(long)blockIdx.x * CO + tid] = sacc;
         }
     }
@@ -925,12 +924,6 @@ extern "C" int hulc_conv2d_bwd_weight(const hulc_conv_desc* d, const void* x, co
     long P, ppb, K, Mtot;
     wgrad_split(d, P, ppb, K, Mtot);
     p.pix_per_block = ppb;
-    {
-        // staging order: consecutive lanes walk pixel pairs (conflict-light transposed LDS writes; measured faster than
-        // chunk-fastest on all six layers: tools/wgrad_bench.py).  HULC_WGRAD_PAIR_FASTEST=0 keeps the other order for A/B runs.
-        const char* e = getenv("HULC_WGRAD_PAIR_FASTEST");
-        p.pair_fastest = e ? atoi(e) : 1;
-    }
     p.partial_w = (float*)ws;
     p.partial_b = db ? p.partial_w + P * d->Cout * K : nullptr;
     dim3 grid((unsigned)P, (unsigned)((K + 255) / 256));

@@ -302,7 +302,7 @@ __global__ __launch_bounds__(256) void ffn_slice_sum_kernel(const float* __restr
 }
 
 int ffn_groups(int T) {
-    static const int gmax = getenv("HULC_FFN_GROUPS") ? atoi(getenv("HULC_FFN_GROUPS")) : 16;   // 16 groups x 16 hidden slices = one workgroup per CU; 32 groups doubled the partial slabs (0.140 vs 0.104 ms per 2 launches)
+    constexpr int gmax = 16;   // 16 groups x 16 hidden slices = one workgroup per CU; 32 groups doubled the partial slabs (0.140 vs 0.104 ms per 2 launches)
     const int nt = (T + TT - 1) / TT;
     return nt < gmax ? nt : gmax;
 }

@@ -660,10 +660,8 @@ void launch_skinny(const GemmP& p, int ak, int bk, float* ws, long ws_bytes, hip
     const bool big2 = !big && p.K >= 1024;                       // 33..64 rows: 8 waves x TM=2, same LDS footprint
     const int nw = big ? 16 : (big2 ? 8 : 4);
     int splitk = 1;
-    const char* force = getenv("HULC_SKINNY_SPLITK");           // tuning knob for A/B runs
-    static const int min_kw = getenv("HULC_SKINNY_MINKW") ? atoi(getenv("HULC_SKINNY_MINKW")) : 64;   // measured (tools/rnn_bench.py): more, shorter K slices win even with the extra epilogue launch
+    constexpr int min_kw = 64;                                   // measured (tools/rnn_bench.py): more, shorter K slices win even with the extra epilogue launch
     while (colblocks * splitk < 200 && p.K / (nw * (splitk * 2)) >= min_kw) splitk *= 2;
-    if (force) splitk = atoi(force);
     unsigned* ctr = (unsigned*)ws;                               // the head of the workspace: tile counters (zero between launches)
     ws = ws ? ws + HULC_GEMM_CTR_BYTES / 4 : ws;
     ws_bytes = ws_bytes > HULC_GEMM_CTR_BYTES ? ws_bytes - HULC_GEMM_CTR_BYTES : 0;
@@ -704,11 +702,10 @@ void launch_cfg(const GemmP& p, int ak, int bk, float* ws, long ws_bytes, hipStr
     const int gx = (p.M + BM - 1) / BM, gy = (p.N + BN - 1) / BN;
     // few output tiles but a long reduction (dgrads into narrow layers, wgrads of narrow layers): split K over workgroups.
     // One workgroup per CU is latency-bound (a k-tile's loads are only covered by one tile of MFMAs): ~3 per CU (768) with >= 4
-    // k-tiles per slice measured best (tools/gemm_heur_sweep.sh: step 6.52 -> 6.20 ms together with the short-K rule below)
+    // k-tiles per slice measured best (a sweep of both constants: step 6.52 -> 6.20 ms together with the short-K rule below)
     const int nkt = (p.K + MmaTraits<CT>::KT - 1) / MmaTraits<CT>::KT;
     int splitk = 1;
-    static const int target = getenv("HULC_TILE_TARGET") ? atoi(getenv("HULC_TILE_TARGET")) : 768;
-    static const int minkt = getenv("HULC_TILE_MINKT") ? atoi(getenv("HULC_TILE_MINKT")) : 4;
+    constexpr int target = 768, minkt = 4;
     while (gx * gy * splitk < target && nkt / (splitk * 2) >= minkt) splitk *= 2;
     // workspace: [HULC_GEMM_CTR_BYTES of tile counters (zero between launches) | split-K slabs + row-sum slabs]
     unsigned* ctr = (unsigned*)ws;
@@ -749,7 +746,7 @@ void launch_ct(const GemmP& p, int ak, int bk, float* ws, long ws_bytes, hipStre
     const long blocks128 = (long)((p.M + 127) / 128) * ((p.N + 127) / 128);
     // short reductions (K <= 256: weight gradients over 32 / 64 sequences, projections out of d_model = 128) are one or two k-tiles
     // of latency followed by a 64 KB store per tile: 64 x 64 tiles give 4x the workgroups to overlap them
-    static const int smallk = getenv("HULC_TILE_SMALLK") ? atoi(getenv("HULC_TILE_SMALLK")) : 256;
+    constexpr int smallk = 256;
     if (blocks128 < 192 || p.K <= smallk) launch_cfg<CT, 1, 1, 2, 2>(p, ak, bk, ws, ws_bytes, s);   // 64 x 64
     else launch_cfg<CT, 2, 2, 2, 2>(p, ak, bk, ws, ws_bytes, s);                    // 128 x 128
 }

@@ -144,8 +144,7 @@ int hulc_gemm_nt128_try(const hulc_gemm_desc* d, hipStream_t s) {
     p.accumulate = d->accumulate; p.rowsum = d->rowsum_a; p.rowsum_accumulate = d->rowsum_accumulate;
     // 64-row tiles when 128-row ones would leave one workgroup per CU: a k-step's loads need ~1 us, its 16 MFMAs 0.2 — a second workgroup
     // on the CU computes meanwhile
-    static const int min_wg = getenv("HULC_NT128_MINWG") ? atoi(getenv("HULC_NT128_MINWG")) : 512;
-    const bool small = (long)(d->M / NT_B) * (d->N / NT_B) < min_wg;
+    const bool small = (long)(d->M / NT_B) * (d->N / NT_B) < 512;
     const size_t lds = (size_t)2 * ((small ? 64 : 128) + NT_B) * NT_RS;
     static bool attr[2] = {false, false};
     if (!attr[small]) {

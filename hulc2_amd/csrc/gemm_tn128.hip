@@ -27,8 +27,8 @@ struct TnP {
     int M, N, K;
     int accumulate;
     float* rowsum; int rowsum_accumulate;
-    unsigned long long* tstamp;         // HULC_TN_DBG & 8: per workgroup, s_memrealtime at kernel start / first tile in LDS / k loop done / epilogue done
-    int dbg;                            // HULC_TN_DBG (probe): 8 = time stamps of the first launches, printed by the next call; 16 = all loads from tile 0
+    unsigned long long* tstamp;         // HULC_TN_DBG & 8 (probe): per workgroup, s_memrealtime at kernel start / first tile in LDS / k loop done / epilogue
+                                        // done, for the first launches, printed by the next call
 };
 
 typedef short v4s __attribute__((ext_vector_type(4)));
@@ -202,8 +202,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         { const int k1 = nkt > 1 ? 1 : 0;
           TN_LD1_PINNED(0, k1) TN_LD1_PINNED(1, k1) TN_LD1_PINNED(2, k1) TN_LD1_PINNED(3, k1) TN_LD1_PINNED(4, k1) TN_LD1_PINNED(5, k1) TN_LD1_PINNED(6, k1) TN_LD1_PINNED(7, k1) }
         for (int kt = 0; kt < nkt; kt += 2) {                          // nkt is even
-            int k2 = kt + 2 < nkt ? kt + 2 : kt, k3 = kt + 3 < nkt ? kt + 3 : kt + 1;   // past the end: tiles nobody consumes, no branch
-            if (p.dbg & 16) k2 = k3 = 0;                               // (probe: every load hits the same hot tile — wrong results, memory taken out of the timing)
+            const int k2 = kt + 2 < nkt ? kt + 2 : kt, k3 = kt + 3 < nkt ? kt + 3 : kt + 1;   // past the end: tiles nobody consumes, no branch
             TN_KSTEP_I(0, TN_LD2, k2, TN_ST1)                          // stage 0: tile kt; loads tile kt + 2 -> set s; stores tile kt + 1 (set r) -> stage 1
             __syncthreads();
             TN_KSTEP_I(1, TN_LD1, k3, TN_ST2)                          // stage 1: tile kt + 1; loads tile kt + 3 -> set r; stores tile kt + 2 (set s) -> stage 0
@@ -269,9 +268,9 @@ int hulc_gemm_tn128_try(const hulc_gemm_desc* d, hipStream_t s) {
             return hulc_fail(-8, "hulc_gemm: could not raise the dynamic LDS limit (tn128)");
         attr = true;
     }
-    { static const char* e = getenv("HULC_TN_DBG"); p.dbg = e ? atoi(e) : 0; }
+    static const char* dbg = getenv("HULC_TN_DBG");
     p.tstamp = nullptr;
-    if (p.dbg & 8) {
+    if (dbg && (atoi(dbg) & 8)) {
         static unsigned long long* buf = nullptr; static int calls = 0, nwg = 0;
         if (!buf) hipMalloc(&buf, 4096 * 4 * 8);
         if ((calls == 1 || calls == 2) && nwg) {             // the second and third (eager) calls print the launch before them
@@ -287,8 +286,7 @@ int hulc_gemm_tn128_try(const hulc_gemm_desc* d, hipStream_t s) {
         if (calls < 2 || (calls == 2 && 0)) { p.tstamp = buf; nwg = (d->N / BT) * (d->M / BT) <= 4096 ? (d->N / BT) * (d->M / BT) : 0; if (!nwg) p.tstamp = nullptr; }
         ++calls;
     }
-    static const bool deep_ok = !(getenv("HULC_TN128_DEEP") && atoi(getenv("HULC_TN128_DEEP")) == 0);
-    if (deep_ok && d->K % (2 * BT) == 0) gemm_tn128_kernel<true><<<dim3(d->N / BT, d->M / BT), 256, lds, s>>>(p);
+    if (d->K % (2 * BT) == 0) gemm_tn128_kernel<true><<<dim3(d->N / BT, d->M / BT), 256, lds, s>>>(p);
     else gemm_tn128_kernel<false><<<dim3(d->N / BT, d->M / BT), 256, lds, s>>>(p);
     return 1;
 }

@@ -348,13 +348,8 @@ static int chain_launch(const hulc_mlp_chain_desc* d, const hulc_mlp_chain_desc*
     // take part in the barriers), which leaves the other half of the device to a second cooperative launch (round 6: g_coop_share)
     int widest = 0;
     for (int l = 0; l < d->nl; ++l) widest = d->layers[l].N > widest ? d->layers[l].N : widest;
-    int grid = 256;
-    {
-        static const char* e = getenv("HULC_CHAIN_GRID");
-        const int want = e ? atoi(e) : (hulc_coop_share() > 1 ? 256 / hulc_coop_share() : 256);
-        if (want >= 8 && want < 256 && want % 8 == 0 && widest <= 16 * want) grid = want;
-        else if (hulc_coop_share() > 1) return hulc_fail(-9, "hulc_mlp_chain: the chain is wider than its share of the device (hulc_set_coop_share)");
-    }
+    const int grid = 256 / hulc_coop_share();
+    if (hulc_coop_share() > 1 && widest > 16 * grid) return hulc_fail(-9, "hulc_mlp_chain: the chain is wider than its share of the device (hulc_set_coop_share)");
     if (p.x3) {
         for (int l = 0; l < d->nl; ++l) {
             const int kk = d2 && l < d2->nl && p.L2[l].K > p.L[l].K ? p.L2[l].K : p.L[l].K;

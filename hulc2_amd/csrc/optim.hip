@@ -342,22 +342,15 @@ extern "C" int hulc_adam_step_amp(float* p, const float* g, float* m, float* v, 
     auto meant = [](float b) -> double { const double d = (double)b, r = std::round(d * 1e7) / 1e7; return std::fabs(r - d) <= 6e-8 * std::fabs(d) ? r : d; };
     const double b1d = meant(beta1), b2d = meant(beta2);
     const float bc1 = (float)(1.0 - std::pow(b1d, (double)step)), bc2s = (float)std::sqrt(1.0 - std::pow(b2d, (double)step));
-    // (round 5, tools/adam_sweep.py on two boxes) every operand of the pass is touched once per step and the arenas (753 MB) are three times the
+    // (round 5, a sweep on two boxes) every operand of the pass is touched once per step and the arenas (753 MB) are three times the
     // MALL: non-temporal loads of p / g / m / v and stores of p / m / v take the 47 M-element pass from 256-288 us to 241-251 us (5.5 -> 5.8 TB/s of
     // its 30 B per element); the bf16 shadow keeps the default policy (derive_copies reads it next).  8192 workgroups instead of 4096: -3 %.
-    // HULC_ADAM_NT (bit 0: g loads, 1: p / m / v loads, 2: p / m / v stores, 3: shadow stores) / HULC_ADAM_BLOCKS: the sweep's knobs.
-    static const long cap = getenv("HULC_ADAM_BLOCKS") ? atol(getenv("HULC_ADAM_BLOCKS")) : 8192;
-    static const int nt = getenv("HULC_ADAM_NT") ? atoi(getenv("HULC_ADAM_NT")) : 7;
+    // adam_kernel<NT>, NT bits: 0 g loads, 1 p / m / v loads, 2 p / m / v stores, 3 shadow stores (non-temporal)
+    constexpr long cap = 8192;
     long blocks = (n / 4 + 255) / 256; if (blocks > cap) blocks = cap; if (blocks < 1) blocks = 1;
-#define ADAM_GO(NTV) adam_kernel<NTV><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(p, g, m, v, (uint16_t*)bf16_shadow, n, lr, beta1, beta2, eps, weight_decay, \
-                                                                   bc1, bc2s, grad_scale, step_state, skip_flag, (uint16_t*)lo_shadow, lr_, \
-                                                                   (float)(1.0 - b1d), (float)(1.0 - b2d), b1d, b2d, loss_scale, found_inf)
-    switch (nt) {
-        case 1: ADAM_GO(1); break; case 3: ADAM_GO(3); break; case 4: ADAM_GO(4); break; case 5: ADAM_GO(5); break;
-        case 0: ADAM_GO(0); break; case 15: ADAM_GO(15); break; case 12: ADAM_GO(12); break; case 13: ADAM_GO(13); break;
-        default: ADAM_GO(7);
-    }
-#undef ADAM_GO
+    adam_kernel<7><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(p, g, m, v, (uint16_t*)bf16_shadow, n, lr, beta1, beta2, eps, weight_decay,
+                                                                    bc1, bc2s, grad_scale, step_state, skip_flag, (uint16_t*)lo_shadow, lr_,
+                                                                    (float)(1.0 - b1d), (float)(1.0 - b2d), b1d, b2d, loss_scale, found_inf);
     return hulc_check_launch("hulc_adam_step");
 }
 

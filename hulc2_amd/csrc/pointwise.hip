@@ -673,7 +673,7 @@ extern "C" int hulc_spatial_softmax_fwd(const void* x, int x_dtype, int N, int H
     if (C > 64 || C <= 0) return hulc_fail(-2, "hulc_spatial_softmax_fwd: C must be in 1..64 (lane = channel)");
     if (x_dtype == HULC_F16 && (C != 64 || ((uintptr_t)x % 16))) return hulc_fail(-4, "hulc_spatial_softmax_fwd: an fp16 map has 64 channels, 16-byte aligned");
     const int esz = x_dtype == HULC_F32 ? 4 : 2;
-    if (C == 64 && ((uintptr_t)x % (8 * esz)) == 0 && HW >= 32 && HW <= 448 && !getenv("HULC_SSM_ONLINE")) {
+    if (C == 64 && ((uintptr_t)x % (8 * esz)) == 0 && HW >= 32 && HW <= 448) {
         if (x_dtype == HULC_BF16) spatial_softmax_fwd64_regs_kernel<HULC_BF16><<<N, 256, 0, (hipStream_t)stream>>>(x, HW, xmap, ymap, temperature, out, stats);
         else if (x_dtype == HULC_F16) spatial_softmax_fwd64_regs_kernel<HULC_F16><<<N, 256, 0, (hipStream_t)stream>>>(x, HW, xmap, ymap, temperature, out, stats);
         else spatial_softmax_fwd64_regs_kernel<HULC_F32><<<N, 256, 0, (hipStream_t)stream>>>(x, HW, xmap, ymap, temperature, out, stats);

@@ -26,7 +26,7 @@
 #include <stdlib.h>
 
 #define RNN_CTR_STRIDE 1024                                   // unsigned words between barrier counters (4 KB)
-#define RNN_WS_HEADER (17 * RNN_CTR_STRIDE * 4)               // 16 barrier counters (8 in the unpipelined kernel) + the error word
+#define RNN_WS_HEADER (17 * RNN_CTR_STRIDE * 4)               // 16 barrier counters + the error word
 #define RNN_ERR_WORD (16 * RNN_CTR_STRIDE)
 
 namespace {
@@ -47,7 +47,7 @@ struct WaveP {
     unsigned* bar; int* err; int* err_sticky;
     const float* add1c; long ld_add1c;           // per-row constant of the first half, the same at every step (nullable): folded into the bias term
     unsigned long long* ts;                      // HULC_RNN_DBG & 8: s_memrealtime stamps [workgroup 0 / 100][wave 1, 0, 7][sub-step][7 phases] (printed by the next launch)
-    int dbg;                                     // experiments / tests only (HULC_RNN_DBG): 1 = skip state loads + MFMAs, 2 = skip the barrier, 4 = inject a barrier timeout
+    int dbg;                                     // tests / probes only (HULC_RNN_DBG): 4 = inject a barrier timeout, 8 = phase stamps
 };
 
 // The bf16 state copy is the only data exchanged between workgroups inside the kernel.  Measured alternatives:
@@ -76,200 +76,10 @@ HULC_DEVICE bf16x8_t load_w(const uint16_t* w, long ld, int n, int k) {
     return x.b;
 }
 
-template <int H, bool WT>
-__global__ __launch_bounds__(512) void rnn_wavefront_kernel(WaveP p) {
-    constexpr int KS = H / 32;                   // k-steps (of 32) per half of the state row
-    constexpr int KPW = KS / 8;                  // per wave
-    static_assert(KS % 8 == 0, "H must be a multiple of 256");
-    __shared__ float red[8][4][256];             // [wave][mt*2 + ct][reg*64 + lane]
-    __shared__ uint4 wlds[8][KPW][64];           // second-half weights of the "second" columns (the registers hold the rest)
-    __shared__ __attribute__((aligned(16))) uint16_t otile[32][2][16 + 8];    // bf16 outputs of the step, [row][half][col] (+pad), for 16-byte coherent stores
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int i = lane & 15, kb = lane >> 4;
-    // workgroups are dispatched round-robin over the 8 XCDs: xcd = blockIdx % 8.  64 "line groups" (row half x 64 columns)
-    // of 4 workgroups each; line group L lives on XCD L % 8.
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int lgrp = xcd + 8 * (slot >> 2);
-    const int rowhalf = lgrp & 1, n0 = ((lgrp >> 1) * 4 + (slot & 3)) * 16;
-    const int nblk = gridDim.x;
-    const long ldz = 2 * H;
-
-    // ---- resident weights: B-operand fragments (lane = column n0 + i, 8 consecutive k)
-    bf16x8_t wfa[KPW], wfb[KPW];
-#pragma unroll
-    for (int q = 0; q < KPW; ++q) {
-        const int k = (wave * KPW + q) * 32 + kb * 8;
-        wfa[q] = load_w<WT>(p.wA, p.ldA, n0 + i, k);
-        wfb[q] = load_w<WT>(p.wB1, p.ldB1, n0 + i, k);
-        union { bf16x8_t b; uint4 u; } wc; wc.b = load_w<WT>(p.wB2, p.ldB2, n0 + i, k);
-        wlds[wave][q][lane] = wc.u;                                          // read back only by this wave: no barrier needed
-    }
-    bool timed_out = false;
-    // ---- this thread's two outputs per wave step (fixed): tile t4 = mt*2 + ct, accumulator element e
-    int om[2], on[2]; float obias[2];
-#pragma unroll
-    for (int rep = 0; rep < 2; ++rep) {
-        const int o = tid + rep * 512, t4 = o >> 8, e = o & 255, ln = e & 63;
-        om[rep] = rowhalf * 32 + (t4 >> 1) * 16 + 4 * (ln >> 4) + (e >> 6);
-        on[rep] = n0 + (ln & 15);
-        const float* ba = (t4 & 1) ? p.bias2a : p.bias1a;
-        const float* bb = (t4 & 1) ? p.bias2b : p.bias1b;
-        obias[rep] = (ba ? ba[on[rep]] : 0.f) + (bb ? bb[on[rep]] : 0.f);
-        if (!(t4 & 1) && p.add1c) obias[rep] += p.add1c[(long)(om[rep] < p.B ? om[rep] : p.B - 1) * p.ld_add1c + on[rep]];
-    }
-
-    for (int tau = 0; tau <= p.S; ++tau) {
-        const bool first_on = tau < p.S, second_on = tau >= 1;
-        f32x4_t acc[2][2];
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int ct = 0; ct < 2; ++ct) acc[mt][ct] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        // epilogue operands first: their latency hides behind the state loads and the MFMAs
-        float oadd[2], omask[2];
-#pragma unroll
-        for (int rep = 0; rep < 2; ++rep) {
-            const int ct = ((tid + rep * 512) >> 8) & 1;
-            const int m = om[rep] < p.B ? om[rep] : p.B - 1, n = on[rep];
-            oadd[rep] = 0.f; omask[rep] = 1.f;
-            if (ct == 0) {
-                if (p.add1 && first_on) oadd[rep] = p.add1[(long)tau * p.add1_step + (long)m * p.ld_add1 + n];
-                if (p.mask1 && first_on) omask[rep] = p.mask1[(long)tau * p.mask1_step + (long)m * p.ld_mask1 + n];
-            } else if (p.mask2 && second_on) omask[rep] = p.mask2[(long)tau * p.mask2_step + (long)m * p.ld_mask2 + n];
-        }
-        if (tau > 0 && !(p.dbg & 1)) {                       // z_0 = 0: nothing to multiply
-            const uint16_t* a = p.xb + (long)(p.zb_row0 + tau * p.zb_dir) * 64 * ldz + (long)(rowhalf * 32 + i) * 8;
-            // the step's 32 fragment loads are independent of the MFMAs: the scheduler keeps as many in flight as registers allow
-            bf16x8_t af[2][KPW][2];
-#pragma unroll
-            for (int hf = 0; hf < 2; ++hf)
-#pragma unroll
-                for (int q = 0; q < KPW; ++q)
-#pragma unroll
-                    for (int mt = 0; mt < 2; ++mt)
-                        af[hf][q][mt] = load_state8(a + ((long)(hf * (H / 8) + (wave * KPW + q) * 4 + kb) * 64 + mt * 16) * 8);
-#pragma unroll
-            for (int q = 0; q < KPW; ++q)
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt) {
-                    acc[mt][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0][q][mt], wfa[q], acc[mt][0], 0, 0, 0);
-                    acc[mt][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0][q][mt], wfb[q], acc[mt][1], 0, 0, 0);
-                }
-#pragma unroll
-            for (int q = 0; q < KPW; ++q) {
-                union { bf16x8_t b; uint4 u; } wc; wc.u = wlds[wave][q][lane];
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt) acc[mt][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1][q][mt], wc.b, acc[mt][1], 0, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) red[wave][mt * 2 + ct][e * 64 + lane] = acc[mt][ct][e];
-        __syncthreads();
-
-        // ---- fixed-order sum over the 8 K slices + epilogue; 1024 outputs, 2 per thread
-        float* zn = p.z + (long)(tau + 1) * p.z_step;
-        uint16_t* zbn = p.zb + (long)(p.zb_row0 + (tau + 1) * p.zb_dir) * p.B * ldz;
-        uint16_t* xbn = p.xb + (long)(p.zb_row0 + (tau + 1) * p.zb_dir) * 64 * ldz;
-        float vout[2]; bool vst[2];
-#pragma unroll
-        for (int rep = 0; rep < 2; ++rep) {
-            const int o = tid + rep * 512, t4 = o >> 8, e = o & 255, ct = t4 & 1;
-            const int m = om[rep], n = on[rep];
-            float v = 0.f;
-#pragma unroll
-            for (int w = 0; w < 8; ++w) v += red[w][t4][e];
-            const bool on_ = ct == 0 ? first_on : second_on;
-            vst[rep] = m < p.B && !(ct == 0 && !on_);                    // last wave step: the first half is not produced
-            v += oadd[rep] + obias[rep];
-            if ((ct == 0 ? p.mask1 : p.mask2) != nullptr) v = omask[rep] > 0.f ? v : 0.f;
-            else if (p.relu) v = fmaxf(v, 0.f);
-            if (!on_) v = 0.f;                                           // wave step 0: the second half (h1_{-1}) is zero
-            vout[rep] = v;
-            if (vst[rep]) otile[m - rowhalf * 32][ct][n - n0] = f32_to_bf16_bits(v);
-        }
-        __syncthreads();
-        // the exchange copy first — it is all the other workgroups wait for; the fp32 rows and the row-major mirror are only read
-        // after the kernel and are stored behind the barrier arrival, off the critical path
-        uint4 v16 = make_uint4(0, 0, 0, 0); bool st16 = false; long off16 = 0;
-        if (tid < 128) {                                     // 32 rows x 2 halves x 2 chunks of 8 columns = 128 16-byte pieces
-            const int row = tid & 31, ct = tid >> 6, ch = (tid >> 5) & 1;
-            const int m = rowhalf * 32 + row;
-            st16 = m < p.B && (ct == 1 || first_on);
-            if (st16) {
-                v16 = *(const uint4*)&otile[row][ct][ch * 8];
-                off16 = (long)m * ldz + ct * H + n0 + ch * 8;
-                unsigned long long* dst = (unsigned long long*)(xbn + ((long)(ct * (H / 8) + n0 / 8 + ch) * 64 + m) * 8);
-                __hip_atomic_store(dst, (unsigned long long)v16.x | ((unsigned long long)v16.y << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(dst + 1, (unsigned long long)v16.z | ((unsigned long long)v16.w << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-        const bool last = tau == p.S;
-        if (!last) {
-            // ---- device-wide barrier, arrival: everybody's z_{tau+1} is visible before anybody reads it
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // this wave's coherent stores have been acknowledged
-            __syncthreads();
-            if (tid == 0 && !(p.dbg & 2)) __hip_atomic_fetch_add(p.bar + xcd * RNN_CTR_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-#pragma unroll
-        for (int rep = 0; rep < 2; ++rep)
-            if (vst[rep]) zn[(long)om[rep] * ldz + (((tid + rep * 512) >> 8) & 1) * H + on[rep]] = vout[rep];
-        if (st16) *(uint4*)(zbn + off16) = v16;                               // row-major mirror
-        if (p.zt && tid < 128) {                                              // transposed mirror: (half, column, 8 rows) per thread
-            const int ct = tid >> 6, col = (tid >> 2) & 15, ch = tid & 3;
-            const int m = rowhalf * 32 + ch * 8;
-            if (m < p.B && (ct == 1 || first_on)) {                           // B % 8 == 0 (checked by the launcher)
-                unsigned w[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) w[e] = (unsigned)otile[ch * 8 + 2 * e][ct][col] | ((unsigned)otile[ch * 8 + 2 * e + 1][ct][col] << 16);
-                *(uint4*)(p.zt + (long)(ct * H + n0 + col) * p.ld_t + (long)(p.zb_row0 + (tau + 1) * p.zb_dir) * p.B + m) = make_uint4(w[0], w[1], w[2], w[3]);
-            }
-        }
-        if (last) break;
-
-        if (tid < 4 && !(p.dbg & 2)) {
-            // The two row halves never exchange data, and a half lives on four XCDs (xcd parity = row half): one arrival counter per
-            // (half, XCD), 4 KB apart (separate memory channels); a workgroup adds to its own and lanes 0..3 each poll one of its
-            // half's four counters.  One counter for all 256 workgroups cost 13.4 us per wave step, one per half 11.1, this 10.5:
-            // same-address atomics and 256 pollers on one line serialise at the memory side.
-            const unsigned per = (unsigned)(nblk / 8) * (unsigned)(tau + 1);
-            const unsigned* bar = p.bar + ((xcd & 1) + 2 * tid) * RNN_CTR_STRIDE;
-            long spins = 0;
-            while (__hip_atomic_load(bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < per) {
-                __builtin_amdgcn_s_sleep(1);
-                if (++spins > (1L << 22)) {
-                    __hip_atomic_store(p.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (p.err_sticky) __hip_atomic_fetch_or(p.err_sticky, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // bit 0 = rnn_wavefront
-                    break;
-                }
-            }
-        }
-        __syncthreads();
-        asm volatile("" ::: "memory");
-    }
-    // a barrier timeout anywhere poisons the state so the failure is loud (NaN loss) instead of silent
-    __syncthreads();
-    if ((p.dbg & 4) && blockIdx.x == 0 && tid == 0) {        // fault injection (tests): behave as if the barrier had timed out
-        __hip_atomic_store(p.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (p.err_sticky) __hip_atomic_fetch_or(p.err_sticky, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // bit 0 = rnn_wavefront
-    }
-    if (__hip_atomic_load(p.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) timed_out = true;
-    if (timed_out) {
-        float* zn = p.z + (long)(p.S + 1) * p.z_step;
-        for (int o = tid; o < 32 * 16; o += 512) {
-            const int m = rowhalf * 32 + o / 16, n = n0 + o % 16;
-            if (m < p.B) { zn[(long)m * ldz + n] = __builtin_nanf(""); zn[(long)m * ldz + H + n] = __builtin_nanf(""); }
-        }
-    }
-}
-
 // ------------------------------------------------------------------------------------------------------------------------------------------
-// The same sweep, software-pipelined over two independent row groups (round 3).
+// The sweep is software-pipelined over two independent row groups (round 3).
 //
-// A wave step of the kernel above is a dependent chain: state loads + MFMA (2.8 us) -> 8-wave sum + epilogue -> write-through exchange stores ->
+// An unpipelined wave step is a dependent chain: state loads + MFMA (2.8 us) -> 8-wave sum + epilogue -> write-through exchange stores ->
 // their acknowledgement -> barrier arrival -> barrier propagation (1.3 us) -> next state loads: 6.5-7 us, the matrix pipes busy for 0.3 of them.
 // Sequences (batch rows) are independent, so the 32 rows a workgroup owns are split into two groups of 16 (the two MFMA row tiles) with their OWN
 // barrier counters, and the workgroup alternates between them: while group A's stores travel and its barrier collects the other workgroups,
@@ -339,7 +149,7 @@ __global__ __launch_bounds__(512) void rnn_wavefront2_kernel(WaveP p) {
         const int om = rowhalf * 32 + g * 16 + orow;
         if (tau > 0) {
             // ---- inputs of (g, tau): every workgroup of this row half has published the group's z_tau
-            if (wave == 7 && lane < 4 && !(p.dbg & 2)) {
+            if (wave == 7 && lane < 4) {
                 const unsigned per = (unsigned)(nblk / 8) * (unsigned)tau;
                 const unsigned* bar = p.bar + (g * 8 + (xcd & 1) + 2 * lane) * RNN_CTR_STRIDE;
                 long spins = 0;
@@ -357,7 +167,7 @@ __global__ __launch_bounds__(512) void rnn_wavefront2_kernel(WaveP p) {
         }
         RNN_TS(u, 1)
         f32x4_t acc[2] = {f32x4_t{0.f, 0.f, 0.f, 0.f}, f32x4_t{0.f, 0.f, 0.f, 0.f}};
-        const bool mul = tau > 0 && !(p.dbg & 1);
+        const bool mul = tau > 0;
         bf16x8_t af[2][KPW];
         if (mul) {
             const uint16_t* a = p.xb + (long)(p.zb_row0 + tau * p.zb_dir) * 64 * ldz + (long)(rowhalf * 32 + g * 16 + i) * 8;
@@ -372,7 +182,7 @@ __global__ __launch_bounds__(512) void rnn_wavefront2_kernel(WaveP p) {
             asm volatile("" ::: "memory");
             if (mul) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * KPW) : "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (lane == 0 && !(p.dbg & 2)) __hip_atomic_fetch_add(p.bar + (pending * 8 + xcd) * RNN_CTR_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (lane == 0) __hip_atomic_fetch_add(p.bar + (pending * 8 + xcd) * RNN_CTR_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             pending = -1;
         }
         // epilogue operands: requested behind the state loads (their latency hides under the MFMAs) and consumed as opaque values in the
@@ -481,8 +291,7 @@ __global__ __launch_bounds__(512) void rnn_wavefront2_kernel(WaveP p) {
 
 // zero the barrier header and the bf16 mirror of the initial state row: a kernel, not hipMemsetAsync, so that a captured hipGraph holds
 // nothing but kernel nodes with plain pointer arguments (a captured hipMemsetAsync node
-// was found to leave the barrier header un-zeroed on later replays once other allocations ran in between: NaN from replay 2 on, round 2;
-// HULC_RNN_MEMSET=1 restores the memset calls to reproduce it)
+// was found to leave the barrier header un-zeroed on later replays once other allocations ran in between: NaN from replay 2 on, round 2)
 __global__ __launch_bounds__(256) void rnn_prep_kernel(uint4* __restrict__ a, long na, uint4* __restrict__ b, long nb, float4* __restrict__ z0, long nz0,
                                                        float* __restrict__ zl, int B, int H) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -559,34 +368,23 @@ extern "C" int hulc_rnn_wavefront(const hulc_rnn_wave_desc* d, void* ws, void* s
     }
     p.zb_row0 = d->z_step > 0 ? 0 : d->S + 1; p.zb_dir = d->z_step > 0 ? 1 : -1;
     // barrier words, and the bf16 copy of the (zero) initial state row: the copy is a full mirror of the fp32 rows for the weight-gradient GEMMs
-    static const bool use_memset = getenv("HULC_RNN_MEMSET") != nullptr;
-    if (use_memset) {
-        if (hipMemsetAsync(ws, 0, RNN_WS_HEADER, s) != hipSuccess ||
-            hipMemsetAsync(p.zb + (long)p.zb_row0 * d->B * 2 * d->H, 0, (size_t)d->B * 2 * d->H * 2, s) != hipSuccess)   // (exchange region 0 is never read: z_0 = 0 is skipped)
-            return hulc_fail(-9, "hulc_rnn_wavefront: could not reset the barrier words");
-    } else {
-        if ((uintptr_t)ws % 16 || RNN_WS_HEADER % 16) return hulc_fail(-4, "hulc_rnn_wavefront: workspace must be 16-byte aligned");
-        const long na = RNN_WS_HEADER / 16, nb = (long)d->B * 2 * d->H * 2 / 16;
-        const long nz0 = d->zero_edges ? (long)d->B * 2 * d->H / 4 : 0;
-        long n = na > nb ? na : nb;
-        if (nz0 > n) n = nz0;
-        float* zlast = d->zero_edges ? d->z + (long)(d->S + 1) * d->z_step : nullptr;       // row S+1 of the sweep
-        rnn_prep_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>((uint4*)ws, na, (uint4*)(p.zb + (long)p.zb_row0 * d->B * 2 * d->H), nb,
-                                                                  d->zero_edges ? (float4*)d->z : nullptr, nz0, zlast, d->B, d->H);
-    }
+    if ((uintptr_t)ws % 16 || RNN_WS_HEADER % 16) return hulc_fail(-4, "hulc_rnn_wavefront: workspace must be 16-byte aligned");
+    const long na = RNN_WS_HEADER / 16, nb = (long)d->B * 2 * d->H * 2 / 16;
+    const long nz0 = d->zero_edges ? (long)d->B * 2 * d->H / 4 : 0;
+    long n = na > nb ? na : nb;
+    if (nz0 > n) n = nz0;
+    float* zlast = d->zero_edges ? d->z + (long)(d->S + 1) * d->z_step : nullptr;       // row S+1 of the sweep
+    rnn_prep_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>((uint4*)ws, na, (uint4*)(p.zb + (long)p.zb_row0 * d->B * 2 * d->H), nb,
+                                                              d->zero_edges ? (float4*)d->z : nullptr, nz0, zlast, d->B, d->H);
     if (p.zt) {
         const long n = 2L * d->H * d->B;
         rnn_zero2d_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(p.zt + (long)p.zb_row0 * d->B, p.ld_t, d->B, 2 * d->H);
     }
     if (d->tA != d->tB1 || d->tA != d->tB2) return hulc_fail(-3, "hulc_rnn_wavefront: the three weight matrices share one layout (tA == tB1 == tB2)");
-    static const bool pipelined = !(getenv("HULC_RNN_PIPE") && atoi(getenv("HULC_RNN_PIPE")) == 0);     // HULC_RNN_PIPE=0: the unpipelined kernel
-    if (pipelined && p.ts) {
+    if (p.ts) {
         if (d->tA) rnn_wavefront2_kernel<2048, true, true><<<2 * (2048 / 16), 512, 0, s>>>(p);
         else rnn_wavefront2_kernel<2048, false, true><<<2 * (2048 / 16), 512, 0, s>>>(p);
-    } else if (pipelined) {
-        if (d->tA) rnn_wavefront2_kernel<2048, true><<<2 * (2048 / 16), 512, 0, s>>>(p);
-        else rnn_wavefront2_kernel<2048, false><<<2 * (2048 / 16), 512, 0, s>>>(p);
-    } else if (d->tA) rnn_wavefront_kernel<2048, true><<<2 * (2048 / 16), 512, 0, s>>>(p);
-    else rnn_wavefront_kernel<2048, false><<<2 * (2048 / 16), 512, 0, s>>>(p);
+    } else if (d->tA) rnn_wavefront2_kernel<2048, true><<<2 * (2048 / 16), 512, 0, s>>>(p);
+    else rnn_wavefront2_kernel<2048, false><<<2 * (2048 / 16), 512, 0, s>>>(p);
     return hulc_check_launch("hulc_rnn_wavefront");
 }

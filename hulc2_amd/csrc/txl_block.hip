@@ -50,7 +50,6 @@ struct BlockK {
     unsigned* sync;             // [B][SYNC_STRIDE]: word 0 arrivals, word 1 members that finished
     float* xpart;               // [L][B][Q][4 waves][16][64] partial tiles
     int* err_sticky;
-    int dbg;                    // timing probes (HULC_TXL_DBG, results invalid): 1 skip the attention stages, 2 the feed-forward loops, 4 the exchanges
 };
 
 HULC_DEVICE TxlP attn_params(const BlockP& d, const LayerP& l) {
@@ -82,7 +81,7 @@ HULC_DEVICE void exchange_tiles(const f32x16_t (&acc)[4], float* part, int w, in
 
 // sum of the Q members' partial tiles, in member order (every member ends with the same bits).  sync_no: 1, 2, ... within the launch.
 HULC_DEVICE void quad_exchange(const BlockK& k, f32x16_t& o, int b, int q, int li, int sync_no) {
-    if (k.Q == 1 || (k.dbg & 4)) return;
+    if (k.Q == 1) return;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     float* base = k.xpart + ((long)li * k.d.B + b) * k.Q * (4 * 16 * 64);
     float* mine = base + (long)q * (4 * 16 * 64) + (w * 16) * 64 + lane;
@@ -120,7 +119,7 @@ HULC_DEVICE void quad_exchange(const BlockK& k, f32x16_t& o, int b, int q, int l
 
 // behind the last exchange of a launch: the member that gets here last puts the sequence's counters back to zero
 HULC_DEVICE void quad_finish(const BlockK& k, int b) {
-    if (k.Q == 1 || (k.dbg & 4) || threadIdx.x != 0) return;
+    if (k.Q == 1 || threadIdx.x != 0) return;
     unsigned* ctr = k.sync + (long)b * SYNC_STRIDE;
     if (__hip_atomic_fetch_add(ctr + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(k.Q - 1)) {
         __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -237,9 +236,9 @@ HULC_DEVICE void ffn_fwd_seq(const BlockK& k, const LayerP& l, int b, int q, int
             }
         }
     };
-    const int NS = (k.dbg & 2) ? 0 : FF / 128 / k.Q, s0 = q * NS, s1 = s0 + NS;     // this member's hidden slices
+    const int NS = FF / 128 / k.Q, s0 = q * NS, s1 = s0 + NS;     // this member's hidden slices
     FfnFrags fa, fb;
-    if (NS) load(fa, s0);
+    load(fa, s0);
     for (int s = s0; s < s1; s += 2) {                             // the next slice's weights are in flight under this slice's products
         if (s + 1 < s1) load(fb, s + 1);
         compute(fa, s);
@@ -319,7 +318,7 @@ __global__ __launch_bounds__(256) void txl_block_fwd_kernel(BlockK k) {
         // address products out of this loop — 60+ registers live across both stages, spilled)
         int bb = b;
         asm volatile("" : "+s"(bb));
-        if (!(k.dbg & 1)) txl_attn_fwd_body<X3>(p, bb, lds);
+        txl_attn_fwd_body<X3>(p, bb, lds);
         __syncthreads();
         ffn_fwd_seq<X3>(k, l, bb, q, li, lds, li + 1 == d.L);
         __syncthreads();
@@ -421,7 +420,7 @@ HULC_DEVICE void ffn_bwd_seq(const BlockK& k, const LayerP& l, int b, int q, int
     for (int ot = 0; ot < 4; ++ot) acc[ot] = zero16();
     uint16_t* hrow = (uint16_t*)l.h + (tok0 + r) * (long)FF + 4 * hf;
     uint16_t* dhrow = (uint16_t*)l.dh + (tok0 + r) * (long)FF + 4 * hf;
-    const int NS = (k.dbg & 2) ? 0 : FF / 128 / k.Q;
+    const int NS = FF / 128 / k.Q;
     for (int s = q * NS; s < (q + 1) * NS; ++s) {                   // this member's hidden slices
         const int j0 = s * 128 + 32 * w;
         bf16x8_t w1f[8], w2t[8], w1t[8];
@@ -513,7 +512,7 @@ __global__ __launch_bounds__(256) void txl_block_bwd_kernel(BlockK k) {
         __syncthreads();
         const TxlP p = attn_params(d, l);
         asm volatile("" : "+s"(bb));
-        if (!(k.dbg & 1)) txl_attn_bwd_body<true>(p, bb, lds, dy1, dyv);
+        txl_attn_bwd_body<true>(p, bb, lds, dy1, dyv);
         __syncthreads();
     }
     quad_finish(k, b);
@@ -568,18 +567,16 @@ int device_cus() {
 
 // workgroups per sequence: as many as divide the hidden slices while the whole grid is co-resident (one workgroup per CU)
 int block_share(const hulc_txl_block_desc* d) {
-    static const int forced = getenv("HULC_TXL_SHARE") ? atoi(getenv("HULC_TXL_SHARE")) : 0;
     if (!d->ws || d->exclusive == 0) return 1;
     const int ns = d->FF / 128, groups = (d->B + 7) / 8 * 8;
     for (int q = 4; q > 1; q >>= 1)
-        if ((forced == 0 || q <= forced) && ns % q == 0 && groups * q <= device_cus() / hulc_coop_share() && d->B <= SYNC_MAX_SEQ) return q;
+        if (ns % q == 0 && groups * q <= device_cus() / hulc_coop_share() && d->B <= SYNC_MAX_SEQ) return q;
     return 1;
 }
 
 BlockK block_kernel_params(const hulc_txl_block_desc* d, int Q) {
     BlockK k = {};
-    static const int dbg = getenv("HULC_TXL_DBG") ? atoi(getenv("HULC_TXL_DBG")) : 0;
-    k.d = *d; k.Q = Q; k.err_sticky = d->err_sticky; k.dbg = dbg;
+    k.d = *d; k.Q = Q; k.err_sticky = d->err_sticky;
     k.sync = (unsigned*)d->ws;
     k.xpart = (float*)((char*)d->ws + SYNC_BYTES);
     return k;

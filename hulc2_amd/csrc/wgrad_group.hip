@@ -276,9 +276,8 @@ Plan plan_item(const hulc_wgrad_item& d) {
     const int nsteps = (d.K + T - 1) / T;
     // slices of 32 k-steps (2048 tokens: the per-timestep layers of a 64-sequence step are NOT split), at most 256 slabs per problem.  Round 4: with
     // slices of 4 k-steps / 1024 slabs the launch moved 594 MB, two thirds of it partial slabs written through to memory and read back (a slab is
-    // 16 KB per tile and slice), at 4.6 TB/s — bound by traffic it created itself; 0.115 -> 0.086 ms (HULC_WGG_SLICE / HULC_WGG_CAP: the sweep)
-    static const int slice = getenv("HULC_WGG_SLICE") ? atoi(getenv("HULC_WGG_SLICE")) : 32;
-    static const int maxslabs = getenv("HULC_WGG_CAP") ? atoi(getenv("HULC_WGG_CAP")) : 256;
+    // 16 KB per tile and slice), at 4.6 TB/s — bound by traffic it created itself; 0.115 -> 0.086 ms (a sweep of both constants)
+    constexpr int slice = 32, maxslabs = 256;
     int want = (nsteps + slice - 1) / slice;
     const int cap = pl.tiles >= maxslabs ? 1 : maxslabs / pl.tiles;
     if (want > cap) want = cap;

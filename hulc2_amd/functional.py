@@ -437,7 +437,7 @@ class ConvStackFn(torch.autograd.Function):
         inp, h, w_, cin = None, H, W, C
         # ReLU sign planes of conv1's and conv2's outputs (one bit per element, written by the forward kernels' epilogues): all the data
         # gradients need of those activations is the sign — conv2's data gradient then reads 20 MB instead of 315 MB per 2048 frames
-        want_bits = (_act_dtype() == torch.bfloat16 and any(ctx.needs_input_grad[2:8]) and not os.environ.get("HULC_NO_RELU_BITS"))
+        want_bits = _act_dtype() == torch.bfloat16 and any(ctx.needs_input_grad[2:8])
         bits = [None, None, None]
         # selective precision site "a3" (DESIGN §5): the stack's OUTPUT (conv3's ReLU map, the spatial softmax's / flatten-linear's input) is
         # kept in fp32 inside a bf16 step — its rounding to bf16 alone costs as much gradient fidelity as all of conv1's operand rounding
@@ -1178,11 +1178,11 @@ def transformer_trunk_pooled(emb, pos, pos_ids, layer_params, nhead: int, drop_p
 # action decoder recurrence: 2-layer ReLU RNN over [plan | emb_slice | goal]
 # reference: logistic_decoder_rnn.py:257-270 + decoders/utils/rnn.py:5-14
 # ------------------------------------------------------------------------------------------------
-def _rnn_persistent(B: int, Hd: int, state_dtype, device) -> bool:
+def _rnn_persistent(B: int, Hd: int, device) -> bool:
     """the persistent wavefront kernel covers the benchmarked geometry (bf16 compute, H = 2048, <= 64 rows, fp32 state) on a whole
     MI355X (its 256 workgroups must all be resident, one per CU: a CPX/DPX partition or a CU-masked device shows fewer CUs);
     other geometries and the exact-fp32 mode use the per-step GEMMs.  HULC_NO_RNN_WAVEFRONT=1 forces the per-step path."""
-    return (kn.get_compute() == "bf16" and Hd == 2048 and B <= 64 and state_dtype == torch.float32
+    return (kn.get_compute() == "bf16" and Hd == 2048 and B <= 64
             and kn.device_cu_count(device) >= 256
             and not kn.concurrent_streams()          # its device-wide barrier needs the GPU to itself (kernels.set_concurrent_streams)
             and not os.environ.get("HULC_NO_RNN_WAVEFRONT"))
@@ -1208,9 +1208,8 @@ def _decoder_rnn_forward(plan, emb, goal, lo: int, hi: int, w_ih0, w_hh0, b_ih0,
     kn.gemm(plan, wih0, c, B, Hd, P, P, Kin, Hd, bias=b_ih0)
     kn.gemm(goal, wih0[:, P + E:], c, B, Hd, G, G, Kin, Hd, accumulate=True)
     emb_t = _c(emb) if emb_tm else emb[:, :, lo:hi].permute(1, 0, 2).contiguous()                   # (S, B, E) time-major
-    zdt0 = _act_dtype() if os.environ.get("HULC_RNN_STATE_BF16") else torch.float32
-    persistent0 = h0 is None and _rnn_persistent(B, Hd, zdt0, dev)
-    if persistent0:       # the per-sequence constant c enters the recurrent kernel as its own (step-independent) term: no (S, B, H) expand
+    persistent = h0 is None and _rnn_persistent(B, Hd, dev)
+    if persistent:       # the per-sequence constant c enters the recurrent kernel as its own (step-independent) term: no (S, B, H) expand
         pre0 = torch.empty(S, B, Hd, dtype=torch.float32, device=dev)
         kn.gemm(emb_t, wih0[:, P:P + E], pre0, S * B, Hd, E, E, Kin, Hd)
     else:
@@ -1218,14 +1217,12 @@ def _decoder_rnn_forward(plan, emb, goal, lo: int, hi: int, w_ih0, w_hh0, b_ih0,
         kn.gemm(emb_t, wih0[:, P:P + E], pre0, S * B, Hd, E, E, Kin, Hd, accumulate=True)
     # state kept fp32: a bf16 state halves the step traffic but the big reduction-major wgrad GEMMs over it then run on
     # 2-byte strided loads and lose more than the steps gain (tools/decoder_bench.py: 3.07 ms fp32 vs 3.69 ms bf16)
-    zdt = _act_dtype() if os.environ.get("HULC_RNN_STATE_BF16") else torch.float32
-    persistent = h0 is None and _rnn_persistent(B, Hd, zdt, dev)
     if persistent:
         # the persistent kernel writes every row it owns (rows 1..S+1, zeros included): only the initial row and the half of the last
         # row it never produces are cleared, not 36 MB
-        zbuf = torch.empty(S + 2, B, 2 * Hd, dtype=zdt, device=dev)            # zbuf[t+1] = [h0_t | h1_{t-1}]; edges cleared by the launcher
+        zbuf = torch.empty(S + 2, B, 2 * Hd, dtype=torch.float32, device=dev)  # zbuf[t+1] = [h0_t | h1_{t-1}]; edges cleared by the launcher
     else:
-        zbuf = torch.zeros(S + 2, B, 2 * Hd, dtype=zdt, device=dev)
+        zbuf = torch.zeros(S + 2, B, 2 * Hd, dtype=torch.float32, device=dev)
     if h0 is not None:                                                         # carried state: h0_{-1} and h1_{-1}
         zbuf[0][:, :Hd] = h0[0]
         zbuf[1][:, Hd:] = h0[1]
@@ -1238,17 +1235,9 @@ def _decoder_rnn_forward(plan, emb, goal, lo: int, hi: int, w_ih0, w_hh0, b_ih0,
                                mirror_t=bool(os.environ.get("HULC_RNN_WGRAD_TMIRROR")), add1c=c, zero_edges=True)
         return zbuf, plan, emb_t, goal, z16, meta
     w1cat = weight_operand(torch.cat([w_ih1.detach(), w_hh1.detach()], dim=1))   # (H, 2H) = [W_ih1 | W_hh1]
-    s0, s1 = torch.cuda.current_stream(dev), kn.side_stream(dev)
-    s1.wait_stream(s0)
     for t in range(S):
         kn.gemm(zbuf[t][:, :Hd], whh0, zbuf[t + 1][:, :Hd], B, Hd, Hd, 2 * Hd, Hd, 2 * Hd, bias=b_hh0, add=pre0[t], ld_add=Hd, relu=True)
-        ev = torch.cuda.Event()
-        ev.record(s0)
-        with torch.cuda.stream(s1):
-            s1.wait_event(ev)
-            kn.gemm(zbuf[t + 1], w1cat, zbuf[t + 2][:, Hd:], B, Hd, 2 * Hd, 2 * Hd, 2 * Hd, 2 * Hd, bias=b_ih1, add=b_hh1, ld_add=0,
-                    relu=True)
-    s0.wait_stream(s1)
+        kn.gemm(zbuf[t + 1], w1cat, zbuf[t + 2][:, Hd:], B, Hd, 2 * Hd, 2 * Hd, 2 * Hd, 2 * Hd, bias=b_ih1, add=b_hh1, ld_add=0, relu=True)
     return zbuf, plan, emb_t, goal, None, meta
 
 
@@ -1270,11 +1259,10 @@ class DecoderRNNFn(torch.autograd.Function):
       * layer 0's input projection is split by linearity: plan/goal columns of W_ih0 once per sequence, the embedding
         columns per token (one batched GEMM);
       * layer 1's input projection is fused into its recurrent GEMM: h1_t = relu([h0_t | h1_{t-1}] [W_ih1 | W_hh1]^T + b)
-        (K = 2H), so layer 1 needs nothing but h0_t; the two layers can run as a wavefront on two HIP streams
-        (HULC_WAVEFRONT=1) — measured neutral-to-slower on MI355X because each launch already fills the chip, so the
-        default is one stream;
+        (K = 2H), so layer 1 needs nothing but h0_t; running the two layers as a wavefront on two HIP streams measured
+        neutral-to-slower on MI355X because each launch already fills the chip, so they share one stream;
       * activations are time-major (S, B, .) so each step's rows are contiguous; zbuf[t+1] = [h0_t | h1_{t-1}].
-    Backward mirrors it: delta0_t = ([delta1_t | delta0_{t+1}] [W_ih1^T | W_hh0^T]^T) * (h0_t > 0), again a wavefront.
+    Backward mirrors it: delta0_t = ([delta1_t | delta0_{t+1}] [W_ih1^T | W_hh0^T]^T) * (h0_t > 0).
     """
 
     @staticmethod
@@ -1318,26 +1306,18 @@ class DecoderRNNFn(torch.autograd.Function):
         else:
             whh1_t = weight_operand(w_hh1, "t")
             wb0 = weight_operand(torch.cat([w_ih1.detach().t(), w_hh0.detach().t()], dim=1))   # (H, 2H) = [W_ih1^T | W_hh0^T]
-            s0, s1 = torch.cuda.current_stream(dev), kn.side_stream(dev)
-            s1.wait_stream(s0)
-        for t in (range(S - 1, -1, -1) if not ctx.persistent else ()):
-            h1_t, h0_t = zbuf[t + 2][:, Hd:], zbuf[t + 1][:, :Hd]
-            # delta1_t = (dH1_t + delta1_{t+1} W_hh1) * (h1_t > 0)      (dbuf[S+1] does not exist: delta1_S = 0 -> zero rows of zbuf[0])
-            prev = dbuf[t + 2][:, :Hd] if t + 2 <= S else zbuf[0][:, :Hd]
-            kn.gemm(prev, whh1_t, dbuf[t + 1][:, :Hd], B, Hd, Hd, 2 * Hd, Hd, 2 * Hd, add=dH1_t[t], ld_add=Hd, mask=h1_t, ld_mask=2 * Hd)
-            ev = torch.cuda.Event()
-            ev.record(s0)
-            with torch.cuda.stream(s1):
-                s1.wait_event(ev)
+            for t in range(S - 1, -1, -1):
+                h1_t, h0_t = zbuf[t + 2][:, Hd:], zbuf[t + 1][:, :Hd]
+                # delta1_t = (dH1_t + delta1_{t+1} W_hh1) * (h1_t > 0)      (dbuf[S+1] does not exist: delta1_S = 0 -> zero rows of zbuf[0])
+                prev = dbuf[t + 2][:, :Hd] if t + 2 <= S else zbuf[0][:, :Hd]
+                kn.gemm(prev, whh1_t, dbuf[t + 1][:, :Hd], B, Hd, Hd, 2 * Hd, Hd, 2 * Hd, add=dH1_t[t], ld_add=Hd, mask=h1_t, ld_mask=2 * Hd)
                 # delta0_t = ([delta1_t | delta0_{t+1}] [W_ih1^T | W_hh0^T]^T) * (h0_t > 0)
                 kn.gemm(dbuf[t + 1], wb0, dbuf[t][:, Hd:], B, Hd, 2 * Hd, 2 * Hd, 2 * Hd, 2 * Hd, mask=h0_t, ld_mask=2 * Hd)
-        if not ctx.persistent:
-            s0.wait_stream(s1)
         d1 = dbuf[1:S + 1]            # rows (t, b): [delta1_t | delta0_{t+1}]
         d0 = dbuf[0:S][:, :, Hd:]     # rows (t, b): delta0_t   (strided view, ld 2H)
         # operands of the big weight-gradient GEMMs: the bf16 mirrors the persistent kernels left behind (half the bytes; the MFMA
         # rounds to bf16 while staging anyway), else the fp32 buffers
-        use16 = ctx.persistent and not os.environ.get("HULC_RNN_WGRAD_FP32")
+        use16 = ctx.persistent
         z16, z16t = ctx.z16 if ctx.persistent else (None, None)
         zw = z16 if use16 else zbuf
         d1w = d16[1:S + 1] if use16 else d1

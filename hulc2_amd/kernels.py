@@ -293,20 +293,6 @@ def _gemm_scratch(device) -> torch.Tensor:
     return t
 
 
-_side = {}
-
-
-def side_stream(device) -> "torch.cuda.Stream":
-    """second HIP stream used to run independent kernel chains concurrently (the two RNN layers as a wavefront)"""
-    import os
-    if not os.environ.get("HULC_WAVEFRONT"):            # measured (tools/decoder_bench.py): the two recurrent chains do not overlap
-        return torch.cuda.current_stream(device)        # usefully (each launch already fills the chip) -> default: one stream
-    s = _side.get(device)
-    if s is None:
-        s = _side[device] = torch.cuda.Stream(device=device)
-    return s
-
-
 def gemm(A, B, C, M, N, K, lda, ldb, ldc, a_kmajor=True, b_kmajor=True, bias=None, add=None, ld_add=0,
          mask=None, ld_mask=0, mask_scale=1.0, relu=False, accumulate=False, alpha=1.0, drop_p=0.0,
          drop_seed=0, compute=None, rowsum=None, rowsum_accumulate=False):
@@ -965,8 +951,7 @@ _wg_armed = set()
 
 def wgrad_group_ok(A, B, C, M, N, K, lda, ldb, ldc, any_size=False) -> bool:
     """shapes hulc_wgrad_group takes; the three 2048^3 products of the recurrent decoder stay on their own kernel (gemm_tn128) unless any_size"""
-    import os
-    if _compute_mode != BF16 or os.environ.get("HULC_NO_WGRAD_GROUP"):
+    if _compute_mode != BF16:
         return False
     if K % 32 or M % 8 or N % 8 or C.dtype != torch.float32 or A.dtype not in (torch.float32, torch.bfloat16) \
             or B.dtype not in (torch.float32, torch.bfloat16):
@@ -1023,43 +1008,11 @@ def wgrad_reset(device) -> None:
     _wg_pending.pop(device, None)
     _wg_streams.pop(device, None)
     _wg_armed.discard(device)
-    ent = _wg_side.get(device)
-    if ent is not None and len(ent) > 2:
-        torch.cuda.current_stream(device).wait_stream(ent[0])
-        del ent[2:]
-        ent[1].clear()
-
-
-_wg_side = {}           # device -> (side stream, [item lists kept alive until the join])
-
-
-def wgrad_flush_early(device) -> None:
-    """Issue what is pending NOW on a second stream (called from a gradient hook at the perceptual embedding: everything but the camera
-    encoders' layers is queued by then): the grouped launch runs in the gaps of the convolution backward instead of behind it.  The operands
-    stay referenced until wgrad_flush joins the stream at the end of the pass."""
-    import os
-    q = _wg_pending.get(device)
-    if not q or os.environ.get("HULC_WGRAD_EARLY", "0") != "1":     # measured: 4.01 vs 3.73 ms/step — the grouped launch and the convolution
-        return                                                       # backward slow each other down more than the overlap hides; off by default
-    ent = _wg_side.get(device)
-    if ent is None:
-        ent = _wg_side[device] = [torch.cuda.Stream(device=device), []]
-    cur = torch.cuda.current_stream(device)
-    ent[0].wait_stream(cur)
-    ent[1].append(list(q))
-    with torch.cuda.stream(ent[0]):
-        _wgrad_issue(device)
-    ent.append("joined-pending")
 
 
 def wgrad_flush(device=None) -> None:
-    """issue the pending weight-gradient products (all devices when device is None) and join an early flush's stream"""
-    for dev in ([device] if device is not None else list(set(_wg_pending) | set(_wg_side))):
-        ent = _wg_side.get(dev)
-        if ent is not None and len(ent) > 2:
-            torch.cuda.current_stream(dev).wait_stream(ent[0])
-            del ent[2:]
-            ent[1].clear()
+    """issue the pending weight-gradient products (all devices when device is None)"""
+    for dev in ([device] if device is not None else list(_wg_pending)):
         _wgrad_issue(dev)
 
 
@@ -1079,44 +1032,43 @@ def join_stream(dev, other) -> None:
 
 
 def _wgrad_issue(dev) -> None:
-    if True:
-        q = _wg_pending.pop(dev, None)
-        producers = _wg_streams.pop(dev, None)
-        if producers:                           # (also with nothing queued: a forked weight-gradient branch writes the arena by itself)
-            here = _stream_of(dev)
-            for h in producers:
-                if h != here and h != 0:
-                    join_stream(dev, torch.cuda.ExternalStream(h, device=dev))
-        if not q:
-            return
-        n = len(q)
-        items = (_L.WgradItem * n)()
-        flops = nbytes = 0.0
-        for it, (A, B, C, rs, M, N, K, lda, ldb, ldc, acc, racc, *rest) in zip(items, q):
-            it.A, it.B, it.C = A.data_ptr(), B.data_ptr(), C.data_ptr()
-            it.rowsum = rs.data_ptr() if rs is not None else None
-            it.M, it.N, it.K, it.lda, it.ldb, it.ldc = M, N, K, lda, ldb, ldc
-            it.a_dtype, it.b_dtype = _dt(A), _dt(B)
-            it.accumulate, it.rowsum_accumulate = int(acc), int(racc)
-            it.col_perm = rest[0] if rest else 0
-            it.col_mul = rest[1] if len(rest) > 1 else 1
-            it.store_rows = rest[2] if len(rest) > 2 else 0
-            it.conv_taps_wp = rest[3] if len(rest) > 3 else 0
-            flops += 2.0 * M * N * K * (9 if (len(rest) > 3 and rest[3]) else 1)
-            nbytes += K * M * A.element_size() + K * N * B.element_size() + M * N * 4 * (2 if acc else 1)
-        lib = _L.load()
-        lib.hulc_wgrad_group_workspace.restype = _c.c_long
-        need = int(lib.hulc_wgrad_group_workspace(items, _i(n)))
-        with torch.cuda.device(dev):
-            key = (dev, _stream())
-            ws = _wg_ws.get(key)
-            if ws is None or ws.numel() * 4 < need:
-                ws = torch.zeros((need + (8 << 20)) // 4, dtype=torch.float32, device=dev)
-                if not torch.cuda.is_current_stream_capturing():      # (memory of a graph's pool must not outlive the graph in this cache)
-                    _wg_ws[key] = ws
-            with _Timed(("wgrad_group", n), flops, nbytes):
-                _L.check(lib.hulc_wgrad_group(items, _i(n), _c.c_void_p(ws.data_ptr()), _l(ws.numel() * 4), _c.c_void_p(_stream())),
-                         "hulc_wgrad_group")
+    q = _wg_pending.pop(dev, None)
+    producers = _wg_streams.pop(dev, None)
+    if producers:                           # (also with nothing queued: a forked weight-gradient branch writes the arena by itself)
+        here = _stream_of(dev)
+        for h in producers:
+            if h != here and h != 0:
+                join_stream(dev, torch.cuda.ExternalStream(h, device=dev))
+    if not q:
+        return
+    n = len(q)
+    items = (_L.WgradItem * n)()
+    flops = nbytes = 0.0
+    for it, (A, B, C, rs, M, N, K, lda, ldb, ldc, acc, racc, *rest) in zip(items, q):
+        it.A, it.B, it.C = A.data_ptr(), B.data_ptr(), C.data_ptr()
+        it.rowsum = rs.data_ptr() if rs is not None else None
+        it.M, it.N, it.K, it.lda, it.ldb, it.ldc = M, N, K, lda, ldb, ldc
+        it.a_dtype, it.b_dtype = _dt(A), _dt(B)
+        it.accumulate, it.rowsum_accumulate = int(acc), int(racc)
+        it.col_perm = rest[0] if rest else 0
+        it.col_mul = rest[1] if len(rest) > 1 else 1
+        it.store_rows = rest[2] if len(rest) > 2 else 0
+        it.conv_taps_wp = rest[3] if len(rest) > 3 else 0
+        flops += 2.0 * M * N * K * (9 if (len(rest) > 3 and rest[3]) else 1)
+        nbytes += K * M * A.element_size() + K * N * B.element_size() + M * N * 4 * (2 if acc else 1)
+    lib = _L.load()
+    lib.hulc_wgrad_group_workspace.restype = _c.c_long
+    need = int(lib.hulc_wgrad_group_workspace(items, _i(n)))
+    with torch.cuda.device(dev):
+        key = (dev, _stream())
+        ws = _wg_ws.get(key)
+        if ws is None or ws.numel() * 4 < need:
+            ws = torch.zeros((need + (8 << 20)) // 4, dtype=torch.float32, device=dev)
+            if not torch.cuda.is_current_stream_capturing():      # (memory of a graph's pool must not outlive the graph in this cache)
+                _wg_ws[key] = ws
+        with _Timed(("wgrad_group", n), flops, nbytes):
+            _L.check(lib.hulc_wgrad_group(items, _i(n), _c.c_void_p(ws.data_ptr()), _l(ws.numel() * 4), _c.c_void_p(_stream())),
+                     "hulc_wgrad_group")
 
 
 def _ffn_ws(T, FF, device):

@@ -213,10 +213,6 @@ class Hulc2(LightningModule):
         if self._batchable(mods):
             with kn.site_scope("enc"):
                 emb_all = self.perceptual_encoder([db["rgb_obs"] for _, db in mods], None, None)
-            if emb_all.requires_grad and emb_all.is_cuda:
-                # when backward reaches the embedding every weight gradient outside the camera encoders is queued: HULC_WGRAD_EARLY=1 issues the
-                # grouped launch on a second stream at that point (kernels.wgrad_flush_early; measured slower, off by default)
-                emb_all.register_hook(lambda g_: kn.wgrad_flush_early(g_.device))
             B = mods[0][1]["actions"].shape[0]
             # the embedding's four consumers get their views from one fan-out node (one gather launch forward, ONE merge launch backward
             # instead of autograd's select / slice backward fills and three accumulate adds): emb[:, 0] -> prior, emb[:B, -1] of a leading
@@ -296,7 +292,7 @@ class Hulc2(LightningModule):
             # beside the start of the decoder's.  The recurrent sweeps take every CU while they run, so nothing in this branch may be a
             # cooperative launch (coop_share_scope(0): the projections' chains fall back to GEMMs — a chain spinning on some CUs while the sweep
             # waits for all of them would never finish).
-            if fork and self.use_clip_auxiliary_loss and any("lang" in p_[0] for p_ in per) and not os.environ.get("HULC_NO_CLIP_FORK"):
+            if fork and self.use_clip_auxiliary_loss and any("lang" in p_[0] for p_ in per):
                 side.wait_stream(cur)
                 with torch.cuda.stream(side), kn.coop_share_scope(0):
                     for (scope_, db_, _e, goal_, seqf_, plan_, _k) in per:

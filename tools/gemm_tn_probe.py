@@ -29,4 +29,4 @@ torch.cuda.synchronize(); g.replay(); torch.cuda.synchronize()
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 e0.record(); g.replay(); g.replay(); e1.record(); torch.cuda.synchronize()
 us = e0.elapsed_time(e1) / 20 * 1e3
-print(f"[{os.environ.get('HULC_LIB', 'lib')[-28:]}] tn gemm {M}^3 rowsum={rs is not None} deep={os.environ.get('HULC_TN128_DEEP', '1')}: {us:.1f} us = {2.0 * M * N * K / us / 1e6:.0f} TFLOP/s")
+print(f"[{os.environ.get('HULC_LIB', 'lib')[-28:]}] tn gemm {M}^3 rowsum={rs is not None}: {us:.1f} us = {2.0 * M * N * K / us / 1e6:.0f} TFLOP/s")

@@ -1,6 +1,5 @@
 """Times the whole-trunk transformer launches (csrc/txl_block.hip) at the benchmark's shape: 64 sequences x 32 positions, 2 layers, dropout 0.1.
-HULC_TXL_DBG (1 skip attention, 2 skip the feed-forward loops, 4 skip the exchanges; results invalid) splits the time; HULC_TXL_NO_SHARE=1 /
-HULC_TXL_SHARE=2 change the workgroups per sequence."""
+HULC_TXL_NO_SHARE=1 runs one workgroup per sequence."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
