@@ -24,6 +24,7 @@ import torch.nn as nn
 from hulc2_amd import functional as HF
 from hulc2_amd import kernels as kn
 from hulc2_amd.compat import LightningModule, instantiate
+from hulc2_amd.models.plan_encoders.plan_recognition_net import trunk_site
 from hulc2_amd.utils.distributions import State
 
 logger = logging.getLogger(__name__)
@@ -121,7 +122,7 @@ class Hulc2(LightningModule):
                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, State, State, torch.Tensor]:
         """hulc2.py:200-245; returns the prior/posterior *states* in place of torch.distributions objects."""
         pp_state = self.plan_proposal(perceptual_emb[:, 0], latent_goal)
-        pr_state, seq_feat = self.plan_recognition(perceptual_emb)
+        pr_state, seq_feat = self.plan_recognition(perceptual_emb, seed=trunk_site(self.modality_scope))
         site = 0xA11CE if "lang" in self.modality_scope else 0xB0B       # distinct RNG sites for the two modalities
         sampled_plan, _ = self.dist.rsample_plan(pr_state, seed=site, idx=plan_idx)
         action_loss = self.action_decoder.loss(sampled_plan, perceptual_emb, latent_goal, train_acts, robot_obs)
@@ -317,7 +318,7 @@ class Hulc2(LightningModule):
                     latent_goal = self.language_goal(db["lang"]) if "lang" in self.modality_scope else self.visual_goal(emb[:, -1])
                 with kn.site_scope("prior"):
                     pp_state = self.plan_proposal(emb[:, 0], latent_goal)
-                pr_state, seq_feat = self.plan_recognition(emb)
+                pr_state, seq_feat = self.plan_recognition(emb, seed=trunk_site(self.modality_scope))
                 site = 0xA11CE if "lang" in self.modality_scope else 0xB0B
                 plan, _ = self.dist.rsample_plan(pr_state, seed=site, idx=db.get("plan_idx"))
                 per.append((self.modality_scope, db, emb, latent_goal, seq_feat, plan, self.compute_kl_loss(pp_state, pr_state)))

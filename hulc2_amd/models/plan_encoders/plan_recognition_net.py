@@ -18,6 +18,16 @@ from hulc2_amd import functional as HF
 from hulc2_amd import kernels as kn
 from hulc2_amd.utils.distributions import Distribution, State
 
+# Dropout sites of the trunk (the per-step stream comes from the device step state, kernels.step_state).  A call derives its sub-sites
+# s (position add) and s + 100 (l + 1) + {11, 12, 13, 15} (layer l), so sites 0x1000 apart never share a stream.
+TRUNK_SITE = 0x5EED0001                          # one call over all modalities stacked on the batch axis: each row has its own indices
+MODALITY_SITES = {"vis": 0x5EED1001, "lang": 0x5EED2001}     # one call per modality: rows restart at 0, so each modality gets its own site
+
+
+def trunk_site(modality_scope: str) -> int:
+    """the site of a per-modality trunk call (Hulc2.lmp_train, the per-modality step): distinct masks for the two modalities"""
+    return MODALITY_SITES["lang" if "lang" in modality_scope else "vis"]
+
 
 class PlanRecognitionTransformersNetwork(nn.Module):
     def __init__(self, num_heads: int, num_layers: int, encoder_hidden_size: int, fc_hidden_size: int, plan_features: int,
@@ -77,10 +87,9 @@ class PlanRecognitionTransformersNetwork(nn.Module):
             ids._hulc_arange = True          # (rows 0..S-1 in order: the table's gradient rows are the batch sum itself)
         return ids
 
-    def forward(self, perceptual_emb: torch.Tensor) -> Tuple[State, torch.Tensor]:
+    def forward(self, perceptual_emb: torch.Tensor, seed: int = TRUNK_SITE) -> Tuple[State, torch.Tensor]:
         B, S, E = perceptual_emb.shape
         p = self.dropout_p if self.training else 0.0
-        seed = 0x5EED0001           # site id; the per-step stream comes from the device step state (kernels.step_state)
         position_ids = self._position_ids(S, perceptual_emb.device)
         layers = [self._layer_params(l) for l in range(self.num_layers)]
         if HF.txl_block_ok(perceptual_emb, layers, S, self.num_heads):

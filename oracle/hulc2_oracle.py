@@ -122,9 +122,16 @@ def plan_proposal(sd: SD, p: str, emb0: torch.Tensor, goal: torch.Tensor) -> tor
 # ------------------------------------------------------------------------------------------------
 # plan recognition transformer (post-norm nn.TransformerEncoderLayer written out)
 # ------------------------------------------------------------------------------------------------
-def _encoder_layer(sd: SD, p: str, x: torch.Tensor, nhead: int) -> torch.Tensor:
+def _keep(m, like: torch.Tensor) -> torch.Tensor:
+    """a replayed dropout mask (keep-scales 0 or 1 / (1 - p), oracle/counter_rng.py) in the dtype of the tensor it scales"""
+    return torch.as_tensor(m).to(like.dtype)
+
+
+def _encoder_layer(sd: SD, p: str, x: torch.Tensor, nhead: int, masks: Optional[dict] = None) -> torch.Tensor:
     """x: (S, B, E).  torch.nn.TransformerEncoderLayer defaults as the reference instantiates it
-    (plan_recognition_net.py:115-117): post-norm, ReLU, eps 1e-5, packed in_proj; dropout off."""
+    (plan_recognition_net.py:115-117): post-norm, ReLU, eps 1e-5, packed in_proj; dropout off, or — `masks`, one layer of
+    counter_rng.trunk_masks, batch-major — the replayed masks where torch's layer calls dropout: the attention probabilities
+    (multi_head_attention_forward), dropout1 (out_proj branch), dropout (FFN hidden), dropout2 (linear2 branch)."""
     S, B, E = x.shape
     dh = E // nhead
     qkv = F.linear(x, sd[p + "self_attn.in_proj_weight"], sd[p + "self_attn.in_proj_bias"])
@@ -133,26 +140,48 @@ def _encoder_layer(sd: SD, p: str, x: torch.Tensor, nhead: int) -> torch.Tensor:
     def heads(t):  # (S, B, E) -> (B*h, S, dh), feature e = head*dh + d
         return t.contiguous().view(S, B * nhead, dh).transpose(0, 1)
 
+    def tm(m, like):  # batch-major (B, S, n) mask -> the (S, B, n) layout of x
+        return _keep(m, like).permute(1, 0, 2)
+
     q, k, v = heads(q), heads(k), heads(v)
     att = torch.softmax(torch.bmm(q, k.transpose(1, 2)) / math.sqrt(dh), dim=-1)
+    if masks is not None:
+        att = att * _keep(masks["attn"], att).reshape(B * nhead, S, S)
     o = torch.bmm(att, v).transpose(0, 1).contiguous().view(S, B, E)
     o = F.linear(o, sd[p + "self_attn.out_proj.weight"], sd[p + "self_attn.out_proj.bias"])
+    if masks is not None:
+        o = o * tm(masks["out"], o)
     x = F.layer_norm(x + o, (E,), sd[p + "norm1.weight"], sd[p + "norm1.bias"], 1e-5)
-    ff = F.linear(F.relu(F.linear(x, sd[p + "linear1.weight"], sd[p + "linear1.bias"])),
-                  sd[p + "linear2.weight"], sd[p + "linear2.bias"])
+    h = F.relu(F.linear(x, sd[p + "linear1.weight"], sd[p + "linear1.bias"]))
+    if masks is not None:
+        h = h * tm(masks["ffn"], h)
+    ff = F.linear(h, sd[p + "linear2.weight"], sd[p + "linear2.bias"])
+    if masks is not None:
+        ff = ff * tm(masks["lin2"], ff)
     return F.layer_norm(x + ff, (E,), sd[p + "norm2.weight"], sd[p + "norm2.bias"], 1e-5)
 
 
-def plan_recognition(sd: SD, p: str, emb: torch.Tensor, nhead: int = 8, num_layers: int = 2) -> Tuple[torch.Tensor, torch.Tensor]:
-    """PlanRecognitionTransformersNetwork.forward (position_embedding=True, no normalisation flags,
-    dropout disabled), plan_recognition_net.py:125-148.  Returns (posterior logits, seq_feat)."""
+def plan_recognition_trunk(sd: SD, p: str, emb: torch.Tensor, nhead: int = 8, num_layers: int = 2,
+                           masks: Optional[dict] = None) -> torch.Tensor:
+    """position embedding -> dropout -> the encoder layers, plan_recognition_net.py:132-143: (B, S, E) tokens in front of `fc`.
+    masks: None (dropout off) or counter_rng.trunk_masks of this call (the position add's mask and one entry per layer)."""
     B, S, E = emb.shape
     pos_ids = torch.arange(S, dtype=torch.long)          # integer indexing: bit-exact by construction
     x = emb + sd[p + "position_embeddings.weight"][pos_ids].unsqueeze(0)
+    if masks is not None:
+        x = x * _keep(masks["pos"], x)
     x = x.permute(1, 0, 2)
     for l in range(num_layers):
-        x = _encoder_layer(sd, f"{p}transformer_encoder.layers.{l}.", x, nhead)
-    x = F.linear(x.permute(1, 0, 2), sd[p + "fc.weight"], sd[p + "fc.bias"])
+        x = _encoder_layer(sd, f"{p}transformer_encoder.layers.{l}.", x, nhead, None if masks is None else masks["layers"][l])
+    return x.permute(1, 0, 2)
+
+
+def plan_recognition(sd: SD, p: str, emb: torch.Tensor, nhead: int = 8, num_layers: int = 2,
+                     masks: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """PlanRecognitionTransformersNetwork.forward (position_embedding=True, no normalisation flags,
+    dropout disabled unless `masks` replays them), plan_recognition_net.py:125-148.  Returns (posterior logits, seq_feat)."""
+    x = plan_recognition_trunk(sd, p, emb, nhead, num_layers, masks)
+    x = F.linear(x, sd[p + "fc.weight"], sd[p + "fc.bias"])
     seq_feat = torch.mean(x, dim=1)
     logits = F.linear(seq_feat, sd[p + "fc_state.0.weight"], sd[p + "fc_state.0.bias"])
     return logits, seq_feat
@@ -524,10 +553,11 @@ def clip_auxiliary_loss(sd: SD, seq_feat: torch.Tensor, goal: torch.Tensor, use:
 # ------------------------------------------------------------------------------------------------
 # whole step
 # ------------------------------------------------------------------------------------------------
-def lmp_train(sd: SD, emb, goal, actions, robot_obs, plan_idx, cfg) -> Dict[str, torch.Tensor]:
-    """Hulc2.lmp_train, hulc2.py:200-245, with the categorical sample injected as `plan_idx` (B,32)."""
+def lmp_train(sd: SD, emb, goal, actions, robot_obs, plan_idx, cfg, masks: Optional[dict] = None) -> Dict[str, torch.Tensor]:
+    """Hulc2.lmp_train, hulc2.py:200-245, with the categorical sample injected as `plan_idx` (B,32); masks: the posterior trunk's
+    replayed dropout masks (plan_recognition_trunk), None = dropout off."""
     pp = plan_proposal(sd, "plan_proposal.", emb[:, 0], goal)
-    pr, seq_feat = plan_recognition(sd, "plan_recognition.", emb)
+    pr, seq_feat = plan_recognition(sd, "plan_recognition.", emb, masks=masks)
     plan = straight_through_sample(pr, plan_idx)
     lp, ls, mu, grip = decoder_forward(sd, "action_decoder.", plan, emb, goal, emb_slice=cfg.get("emb_slice", (64, 128)))
     acts = world_to_tcp_frame(actions, robot_obs) if cfg.get("gripper_control", False) else actions
@@ -541,9 +571,10 @@ def real_world_cfg() -> dict:
     return dict(gripper_control=False, emb_slice=(0, 128), use_clip_auxiliary_loss=False)
 
 
-def training_step(sd: SD, batch: Dict[str, Dict], cfg: Optional[dict] = None) -> Dict[str, torch.Tensor]:
+def training_step(sd: SD, batch: Dict[str, Dict], cfg: Optional[dict] = None, masks: Optional[Dict[str, dict]] = None) -> Dict[str, torch.Tensor]:
     """Hulc2.training_step, hulc2.py:379-442.  `batch[m]` carries rgb_static, rgb_gripper, actions,
-    robot_obs (state_info), plan_idx (injected sample) and, for 'lang', lang (B,384) + use_for_aux_lang_loss."""
+    robot_obs (state_info), plan_idx (injected sample) and, for 'lang', lang (B,384) + use_for_aux_lang_loss.
+    masks: None (dropout off) or, per modality m, the posterior trunk's replayed dropout masks of that modality's rows."""
     cfg = cfg or {}
     out: Dict[str, torch.Tensor] = {}
     kl = act = total = clip = torch.tensor(0.0)
@@ -553,7 +584,7 @@ def training_step(sd: SD, batch: Dict[str, Dict], cfg: Optional[dict] = None) ->
             goal = language_goal_encoder(sd, "language_goal.", db["lang"])
         else:
             goal = visual_goal_encoder(sd, "visual_goal.", emb[:, -1])
-        r = lmp_train(sd, emb, goal, db["actions"], db["robot_obs"], db["plan_idx"], cfg)
+        r = lmp_train(sd, emb, goal, db["actions"], db["robot_obs"], db["plan_idx"], cfg, None if masks is None else masks[m])
         if "lang" in m and cfg.get("use_clip_auxiliary_loss", True) and torch.any(db["use_for_aux_lang_loss"]):
             clip = clip + clip_auxiliary_loss(sd, r["seq_feat"], goal, db["use_for_aux_lang_loss"])
         kl, act, total = kl + r["kl"], act + r["act"], total + r["total"]
