@@ -165,7 +165,8 @@ class Hulc2(LightningModule):
 
     def _step_node(self, keeper):
         """the whole training step as one autograd node (hulc2_amd/stepnode.py) when this model's keeper owns a gradient arena and the call can
-        take it: gradients enabled, no gradient being accumulated over several calls, the keeper's parameter set still the trainable one"""
+        take it: gradients enabled, the keeper's parameter set still the trainable one.  Gradients still attached from earlier calls (accumulation,
+        `zero_grad(set_to_none=False)`) do not keep a call off the node: it adds them back, the capturing call included (stepnode._capture)"""
         if keeper is None or not getattr(keeper, "step_node", False) or not torch.is_grad_enabled():
             return None
         node = self.__dict__.get("_hulc_step_node")

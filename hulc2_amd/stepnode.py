@@ -19,9 +19,11 @@ From the third step of an unchanged configuration on (same batch layout, same ar
 side stream — forward (RNG word advance, forward, losses) and backward (root = a static device scalar) — and the node's forward / backward
 are one `replay()` each: ~12 000 Python-level calls per step become ~10.  The batch of the capturing call is the graphs' input buffer;
 a later batch at other addresses is copied into it (one multi-tensor copy), one at the same addresses (a resident batch, an HBM episode
-store's fixed windows) costs nothing.  Anything the graphs cannot express falls back to the eager node or to the plain call: gradients
-being accumulated over several calls (a live `.grad`), a batch with host data (sentences for the on-device tokenizer), an active capture
-or per-launch timing, a capture that fails (kept as `disabled`).  HULC_NO_STEP_NODE=1 keeps round 4's loop, HULC_NO_STEP_GRAPH=1 the eager node.
+store's fixed windows) costs nothing.  Anything the graphs cannot express falls back to the eager node or to the plain call: a batch with
+host data (sentences for the on-device tokenizer), an active capture or per-launch timing, a capture that fails (kept as `disabled`).
+Gradients still attached when backward runs (accumulation over several calls, `zero_grad(set_to_none=False)`) stay on the node and its
+graphs and come out as old + new (_take_live_grads); the capturing call puts back the gradient arena its warm-up overwrote (_capture).
+HULC_NO_STEP_NODE=1 keeps round 4's loop, HULC_NO_STEP_GRAPH=1 the eager node.
 """
 import os
 import warnings
@@ -407,6 +409,30 @@ class StepNode:
         return slots
 
     def _capture(self, batch, batch_idx, leaves) -> None:
+        """_record, with the gradient arena put back as it was: its warm-up backward and the self-check's replays overwrite the arena, and
+        from the second call on the parameters' `.grad` are views of it.  Gradients still attached when the capturing call runs (accumulation
+        over several calls, `zero_grad(set_to_none=False)` before training_step) would otherwise be replaced by the warm-up's gradient, and
+        this call's backward would hand out new + warm-up instead of old + new.  An arena that hulc2_amd.optim.Adam.zero_grad marked as all
+        zeros is zeroed and marked again (the backward then neither copies nor adds); any other is copied back whole, scratch slices
+        included, on the caller's stream — also when the capture fails.  Nothing is kept when no `.grad` is an arena view (set_to_none=True)."""
+        tr = self.keeper
+        lo = tr.flat_g.data_ptr()
+        hi = lo + tr.flat_g.numel() * 4
+        attached = any(p.grad is not None and lo <= p.grad.data_ptr() < hi for p in tr.params)
+        zeroed = attached and getattr(tr, "grads_zeroed_at", None) is not None and tr.grads_zeroed_at == tr.flat_g._version
+        kept = tr.flat_g.clone() if attached and not zeroed else None
+        try:
+            self._record(batch, batch_idx, leaves)
+        finally:
+            if attached:
+                torch.cuda.synchronize(self.dev)              # (a capture that failed may have left its warm-up running on the side stream)
+                if zeroed:
+                    tr.flat_g.zero_()
+                    tr.grads_zeroed_at = tr.flat_g._version
+                else:
+                    tr.flat_g.copy_(kept)
+
+    def _record(self, batch, batch_idx, leaves) -> None:
         """forward and backward of this batch layout as two hipGraphs on a side stream (shared memory pool).  A warm-up pass on that stream
         comes first: per-stream workspaces and lazily made buffers exist before the capture; the RNG word it drew from is put back, so the
         loop's sequence of draws is the eager loop's.

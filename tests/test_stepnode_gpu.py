@@ -501,3 +501,167 @@ def test_adam_kernel_takes_the_scalers_device_scalars(dev):
     kn.step_count_advance_if(st, torch.zeros(1, device=dev))
     kn.step_count_advance_if(st, None)
     assert st.tolist() == [0, 9]
+
+
+# ---- gradients attached while the node captures -----------------------------------------------------------------------------------------
+# The third call of a batch layout captures (StepNode._capture): a warm-up forward + backward and the frame-slot self-check write the gradient
+# arena, of which the parameters' `.grad` are views from the second call on.  Every leg below runs one loop twice — on the eager node
+# (HULC_NO_STEP_GRAPH=1, the reference) and on the graphs — and compares every parameter's `.grad` bit for bit after EVERY backward.
+
+def _grad_loop(dev, plan, opt_kind, amp, seed=43, running_sum=False):
+    """`plan` = [(layout, zero_before, step_after)] per call: opt.zero_grad(set_to_none=False) -> training_step -> backward -> (step).
+    -> (node, losses, [{name: .grad} after each backward], parameters at the end).
+    running_sum: the reference without attached gradients — every call starts from none (set_to_none=True); the fp32 sums, in call order,
+    of the calls' gradients since the plan last zeroed are formed here and are what the optimizer steps on"""
+    kn.reset_step_state(dev)
+    m = _model(dev, seed)
+    batches = {"big": _batch(dev, seed), "small": _batch(dev, seed + 1, S=4)}
+    params = [p for p in m.parameters() if p.requires_grad]
+    opt = {"sgd": lambda: torch.optim.SGD(params, lr=1e-3), "adam": lambda: torch.optim.Adam(params, lr=2e-4),
+           "arena_adam": lambda: m.configure_optimizers()["optimizer"]}[opt_kind]()
+    scaler = torch.amp.GradScaler("cuda", init_scale=65536.0) if amp else None
+    named = list(m.named_parameters())
+    losses, grads, acc = [], [], None
+    for i, (layout, zero, step) in enumerate(plan):
+        if running_sum:
+            opt.zero_grad(set_to_none=True)
+            if zero and acc is not None:
+                acc = {n: (None if s is None else torch.zeros_like(s)) for n, s in acc.items()}
+        elif zero:
+            opt.zero_grad(set_to_none=False)
+        with torch.autocast("cuda", dtype=torch.float16, enabled=amp):
+            loss = m.training_step(batches[layout], i)
+        (scaler.scale(loss) if amp else loss).backward()
+        g = {n: (None if p.grad is None else p.grad.detach().clone()) for n, p in named}
+        if running_sum:
+            acc = g if acc is None else {n: (s if g[n] is None else g[n] if s is None else s + g[n]) for n, s in acc.items()}
+            g = acc
+            for n, p in named:
+                p.grad = None if acc[n] is None else acc[n].clone()
+        grads.append(g)
+        if step:
+            if amp:
+                scaler.step(opt)
+                scaler.update()
+            else:
+                opt.step()
+        if running_sum:                                   # (what the step left in .grad — unscale_ divides it in place — is the running sum now)
+            acc = {n: (None if p.grad is None else p.grad.detach().clone()) for n, p in named}
+        losses.append(float(loss))
+    torch.cuda.synchronize()
+    kn.check_faults(dev)
+    return m.__dict__["_hulc_step_node"], losses, grads, {n: p.detach().clone() for n, p in named}
+
+
+def _eager_and_graphed(dev, plan, opt_kind, amp, **env):
+    with _env(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH="1", HULC_TORCH_ADAM=None, **env):
+        eager = _grad_loop(dev, plan, opt_kind, amp)
+    assert eager[0].captures == 0 and eager[0].eager_steps == len(plan)
+    # every comparison includes logit_scale: the 0-dim parameter at arena offset 0 whose `.grad` AccumulateGrad clones out of the arena —
+    # its slice is never zeroed, where a slightly wrong restore or add-back of the whole arena shows first
+    assert all(g["logit_scale"] is not None for g in eager[2])
+    with _env(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH=None, HULC_TORCH_ADAM=None, **env):
+        graphed = _grad_loop(dev, plan, opt_kind, amp)
+    return eager, graphed
+
+
+def _same_grads_every_call(got, want, what):
+    """`.grad` after each backward, bit for bit; a mismatch names the first call that differs and the size of the difference"""
+    assert len(got) == len(want)
+    for i, (a, b) in enumerate(zip(got, want)):
+        assert a.keys() == b.keys()
+        bad = [n for n in a if (a[n] is None) != (b[n] is None) or (a[n] is not None and not torch.equal(a[n], b[n]))]
+        if bad:
+            both = [n for n in a if a[n] is not None and b[n] is not None]
+            na = sum(float(a[n].double().pow(2).sum()) for n in both) ** 0.5
+            nb = sum(float(b[n].double().pow(2).sum()) for n in both) ** 0.5
+            nd = sum(float((a[n].double() - b[n].double()).pow(2).sum()) for n in both) ** 0.5
+            pytest.fail(f"{what}: .grad after the backward of call {i}: {len(bad)} of {len(a)} tensors differ (e.g. {bad[:3]}); "
+                        f"|got| / |want| = {na / nb:.6f}, |got - want| / |want| = {nd / nb:.3e}")
+
+
+_STANDARD = [("sgd", False, True), ("sgd", False, False), ("adam", True, True), ("arena_adam", True, True)]
+
+
+@pytest.mark.parametrize("opt_kind,amp,slots", _STANDARD, ids=["sgd", "sgd-no-frame-slots", "torch-adam-scaler", "arena-adam-scaler"])
+def test_in_place_zero_grad_before_training_step_across_the_capture(dev, opt_kind, amp, slots):
+    """The usual non-Lightning order with torch 1.12's default: zero_grad(set_to_none=False) -> training_step -> backward -> step.  From
+    the second call on the zeroed `.grad` are attached arena views when the third call captures; its gradient must be this batch's alone
+    (before the arena was put back: new + the warm-up's gradient — twice the gradient without a scaler).  With hulc2_amd.optim.Adam the
+    capturing call also keeps the optimizer's all-zero mark: no step takes the copy-and-add-back."""
+    plan = [("big", True, True)] * 6
+    env = {} if slots else {"HULC_NO_FRAME_SLOTS": "1"}
+    (ne, le, ge, pe), (ng, lg, gg, pg) = _eager_and_graphed(dev, plan, opt_kind, amp, **env)
+    assert ng.disabled is None, ng.disabled
+    assert (ng.captures, ng.eager_steps, ng.replays) == (1, 2, 4), (ng.captures, ng.eager_steps, ng.replays)
+    assert ng.slots_ok == slots                              # (slots on: the capture's self-check replayed the backward graph twice)
+    _same_grads_every_call(gg, ge, "graphs vs eager node")
+    assert lg == le, (lg, le)
+    _same(pg, pe, "parameters after six steps")
+    if opt_kind == "arena_adam":
+        assert (ne.zeroed_steps, ne.accum_steps) == (5, 0), (ne.zeroed_steps, ne.accum_steps)
+        assert (ng.zeroed_steps, ng.accum_steps) == (ne.zeroed_steps, ne.accum_steps), (ng.zeroed_steps, ng.accum_steps)
+    else:
+        assert ng.accum_steps == ne.accum_steps == 5, (ng.accum_steps, ne.accum_steps)
+
+
+@pytest.mark.parametrize("amp", [False, True], ids=["sgd", "torch-adam-scaler"])
+@pytest.mark.parametrize("k", [3, 4])
+def test_accumulation_from_the_first_call_across_the_capture(dev, k, amp):
+    """Gradient accumulation over k calls from call 0 (Lightning's accumulate_grad_batches >= 3): calls 0 and 1 run eagerly and leave
+    g0 + g1 attached, call 2 captures; two windows, so the second one replays.  Against the eager node bit for bit, and both against the
+    running fp32 sum of the same calls' gradients taken one call at a time (no gradient attached: nothing of _take_live_grads involved)."""
+    plan = [("big", j == 0, j == k - 1) for _ in range(2) for j in range(k)]
+    opt_kind = "adam" if amp else "sgd"
+    (ne, le, ge, pe), (ng, lg, gg, pg) = _eager_and_graphed(dev, plan, opt_kind, amp)
+    with _env(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH="1"):
+        nr, lr_, gr, pr = _grad_loop(dev, plan, opt_kind, amp, running_sum=True)
+    assert ng.disabled is None, ng.disabled
+    assert (ng.captures, ng.eager_steps, ng.replays) == (1, 2, 2 * k - 2), (ng.captures, ng.eager_steps, ng.replays)
+    assert ng.slots_ok
+    # (every call but the first sees gradients attached; the reference never does)
+    assert nr.accum_steps == nr.zeroed_steps == 0 and ng.accum_steps == ne.accum_steps == 2 * k - 1, (nr.accum_steps, ng.accum_steps, ne.accum_steps)
+    _same_grads_every_call(ge, gr, "eager node vs the running sum of single-call gradients")
+    _same_grads_every_call(gg, ge, "graphs vs eager node")
+    assert lg == le == lr_, (lg, le, lr_)
+    _same(pe, pr, "parameters after two windows: eager node vs the running sum")
+    _same(pg, pe, "parameters after two windows: graphs vs eager node")
+
+
+def test_layout_changes_and_a_recapture_inside_an_accumulation_window(dev, monkeypatch):
+    """One window of ten calls, never zeroed: big, big, small x 3 (the third small call captures with four gradients attached), big (captures:
+    its two eager calls were counted before; small's graphs are evicted — StepNode.STASHED = 0 keeps none beside the current layout), small x 4
+    (big evicted, small re-captured at its third call with eight gradients attached, then replayed)."""
+    from hulc2_amd.stepnode import StepNode
+    monkeypatch.setattr(StepNode, "STASHED", 0)
+    layouts = ["big", "big", "small", "small", "small", "big", "small", "small", "small", "small"]
+    plan = [(lay, False, i == len(layouts) - 1) for i, lay in enumerate(layouts)]
+    (ne, le, ge, pe), (ng, lg, gg, pg) = _eager_and_graphed(dev, plan, "sgd", False)
+    assert ng.disabled is None, ng.disabled
+    assert (ng.captures, ng.evictions, ng.eager_steps, ng.replays) == (3, 2, 6, 4), (ng.captures, ng.evictions, ng.eager_steps, ng.replays)
+    _same_grads_every_call(gg, ge, "graphs vs eager node")
+    assert lg == le, (lg, le)
+    _same(pg, pe, "parameters after the window's step")
+    assert ng.accum_steps == ne.accum_steps == 9, (ng.accum_steps, ne.accum_steps)
+
+
+def test_a_failed_capture_keeps_the_accumulated_gradients(dev, monkeypatch):
+    """A capture that raises after its warm-up wrote the arena (here: the graph objects cannot be made — a Python stub, no stream capture is
+    begun) leaves the node disabled and the call eager; the gradients accumulated before it must come through it unchanged."""
+    from hulc2_amd import stepnode
+
+    class _NoGraph:
+        def __init__(self, *a, **kw):
+            raise RuntimeError("graph objects unavailable")
+    plan = [("big", False, i == 4) for i in range(5)]
+    with _env(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH="1"):
+        ne, le, ge, pe = _grad_loop(dev, plan, "sgd", False)
+    assert ne.eager_steps == 5 and all(g["logit_scale"] is not None for g in ge)
+    monkeypatch.setattr(stepnode.torch.cuda, "CUDAGraph", _NoGraph)
+    with _env(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH=None), pytest.warns(UserWarning, match="capture failed"):
+        ng, lg, gg, pg = _grad_loop(dev, plan, "sgd", False)
+    assert ng.disabled is not None and "graph objects unavailable" in ng.disabled, ng.disabled
+    assert (ng.captures, ng.replays, ng.eager_steps) == (0, 0, 5), (ng.captures, ng.replays, ng.eager_steps)
+    _same_grads_every_call(gg, ge, "failed capture vs eager node")
+    assert lg == le, (lg, le)
+    _same(pg, pe, "parameters after the window's step")
