@@ -212,8 +212,11 @@ __global__ __launch_bounds__(512) void conv_band_planes_kernel(BandP p, unsigned
             if (BITS == 0 && p.Y16 && p.y_dtype == HULC_F16) {
                 // the fp16 twin (11 bits of mantissa at the bf16 map's two bytes: measured, the fp32 twin's 16-byte pieces at 256-byte pixel
                 // pitch cost this launch 48 us per 2048 frames): packed and exchanged between the lane halves exactly like the bf16 map below
+                // half precision ends at 65504: a larger accumulator is stored as that, not as the +inf of a plain cast (the spatial softmax
+                // behind the map would take exp(inf - inf)); the fp32 and bf16 maps have no such limit
                 auto pkh = [&](float a, float b) -> uint32_t {
-                    if (p.relu) { a = fmaxf(a, 0.f); b = fmaxf(b, 0.f); }
+                    const float floor = p.relu ? 0.f : -65504.f;
+                    a = fminf(fmaxf(a, floor), 65504.f); b = fminf(fmaxf(b, floor), 65504.f);
                     union { _Float16 hh[2]; uint32_t u; } r; r.hh[0] = (_Float16)a; r.hh[1] = (_Float16)b;
                     return r.u;
                 };

@@ -689,6 +689,9 @@ extern "C" int hulc_spatial_softmax_bwd(const void* x, int x_dtype, int N, int H
                                         void* dx, int dx_dtype, int relu_mask, void* stream) {
     if (!x || !out || !stats || !dout || !dx) return hulc_fail(-1, "hulc_spatial_softmax_bwd: null pointer");
     if (C > 64 || C <= 0) return hulc_fail(-2, "hulc_spatial_softmax_bwd: C must be in 1..64");
+    // (the generic kernel reads 16-bit elements as bf16: an fp16 map is served by the 64-channel kernel only, as in the forward)
+    if (x_dtype == HULC_F16 && (C != 64 || ((uintptr_t)x % 16) || ((uintptr_t)dx % (dx_dtype == HULC_F32 ? 32 : 16))))
+        return hulc_fail(-4, "hulc_spatial_softmax_bwd: an fp16 map has 64 channels, 16-byte aligned");
     const int esz = x_dtype == HULC_F32 ? 4 : 2, dsz = dx_dtype == HULC_F32 ? 4 : 2;
     if (C == 64 && ((uintptr_t)x % (8 * esz)) == 0 && ((uintptr_t)dx % (8 * dsz)) == 0)
         spatial_softmax_bwd64_kernel<<<N, 256, 0, (hipStream_t)stream>>>(x, x_dtype, HW, xmap, ymap, temperature, out, stats, dout, dx, dx_dtype,

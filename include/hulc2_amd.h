@@ -144,7 +144,8 @@ int hulc_conv2d_bwd_weight(const hulc_conv_desc* d, const void* x, const void* d
 /* Spatial softmax over NHWC activations x[N][HW][C] (C <= 64): out[N][2C] = interleaved (E[xmap], E[ymap])
  * per channel, stats[N][C][2] = (max, sum) kept for the backward.  Replaces SpatialSoftmax.forward,
  * vision_network.py:100-108 (xmap/ymap/temperature are that module's registered buffers).
- * bwd writes dx (same layout as x) and, with relu_mask, multiplies by (x > 0) — the ReLU after conv3. */
+ * bwd writes dx (same layout as x) and, with relu_mask, multiplies by (x > 0) — the ReLU after conv3.
+ * An fp16 map (HULC_F16, the twin of conv3's bf16 map) has 64 channels and is 16-byte aligned, in both directions (bwd: dx aligned too). */
 int hulc_spatial_softmax_fwd(const void* x, int x_dtype, int N, int HW, int C, const float* xmap, const float* ymap,
                              const float* temperature, float* out, float* stats, void* stream);
 int hulc_spatial_softmax_bwd(const void* x, int x_dtype, int N, int HW, int C, const float* xmap, const float* ymap,

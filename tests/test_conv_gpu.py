@@ -295,6 +295,48 @@ def test_conv3_stores_the_exact_map_and_the_bf16_map_from_one_launch(dev, name, 
             kn.conv2d_fwd(x, w2d, b, yh, N, H, W, Cin, Cout, K, K, s, False, y_bf16=y16b)
 
 
+def test_conv3_fp16_twin_saturates_instead_of_overflowing(dev):
+    """the fp16 twin of the static camera's conv3 map with accumulators above 65504 (weights scaled up): half precision has no such value,
+    a plain cast stores +inf and the spatial softmax behind the map returns NaN (exp(inf - inf)).  The twin holds 65504 there: it equals the
+    fp32 map clamped and rounded, and the spatial softmax over it equals the float64 softmax of that clamped map."""
+    from hulc2_amd import kernels as kn
+    from tests.kcheck import compare
+
+    kn.set_compute("bf16")
+    N, H, W, Cin, Cout, K, s = 3, 23, 23, 64, 64, 3, 1
+    g = torch.Generator().manual_seed(23)
+    x = torch.relu(torch.randn(N, H, W, Cin, generator=g)).to(torch.bfloat16).to(dev)
+    w = torch.randn(Cout, Cin, K, K, generator=g) / (Cin * K * K) ** 0.5 * 6e4
+    w2d = w.permute(0, 2, 3, 1).reshape(Cout, -1).contiguous().to(torch.bfloat16).to(dev)
+    b = (torch.rand(Cout, generator=g) * 0.2 - 0.1).to(dev)
+    OH, OW = kn.conv_out_hw(H, W, K, K, s)
+    y32 = torch.empty(N, OH, OW, Cout, device=dev)
+    kn.conv2d_fwd(x, w2d, b, y32, N, H, W, Cin, Cout, K, K, s, False)
+    yh = torch.full((N, OH, OW, Cout), float("nan"), device=dev, dtype=torch.float16)
+    y16 = torch.full((N, OH, OW, Cout), float("nan"), device=dev, dtype=torch.bfloat16)
+    kn.conv2d_fwd(x, w2d, b, yh, N, H, W, Cin, Cout, K, K, s, False, y_bf16=y16)
+    torch.cuda.synchronize()
+    over = y32 > 65504.0
+    assert int(over.sum()) > 100 and int((~over & (y32 > 0)).sum()) > 100, "the case needs accumulators on both sides of the half-precision range"
+    assert torch.isfinite(yh).all(), "the fp16 twin holds a non-finite value"
+    assert torch.equal(yh, y32.clamp(max=65504.0).to(torch.float16)) and torch.equal(y16, y32.to(torch.bfloat16))
+    HW = OH * OW
+    xmap = torch.linspace(-1, 1, OW, device=dev).repeat(OH).contiguous()
+    ymap = torch.linspace(-1, 1, OH, device=dev).repeat_interleave(OW).contiguous()
+    out, stats = torch.full((N, 2 * Cout), float("nan"), device=dev), torch.full((N, Cout, 2), float("nan"), device=dev)
+    kn.spatial_softmax_fwd(yh, N, HW, Cout, xmap, ymap, torch.ones(1, device=dev), out, stats)
+    torch.cuda.synchronize()
+    assert torch.isfinite(out).all() and torch.isfinite(stats).all(), "the spatial softmax behind the twin is not finite"
+
+    def ref(dt):
+        z = yh.cpu().to(dt).reshape(N, HW, Cout)
+        e = torch.exp(z - z.max(1, keepdim=True).values)
+        xm, ym = xmap.cpu().to(dt)[None, :, None], ymap.cpu().to(dt)[None, :, None]
+        return torch.stack([(e * xm).sum(1) / e.sum(1), (e * ym).sum(1) / e.sum(1)], -1).reshape(N, 2 * Cout)
+
+    compare("spatial_softmax_fwd/regs", "out(sat.)", out, ref(torch.float64), ref(torch.float32), 16.0)     # (margin: tests/test_reductions_gpu.py)
+
+
 def test_site_a3_keeps_the_stack_output_bf16_and_hands_out_its_exact_twin(dev, monkeypatch):
     """site "a3": the conv stack's differentiable output is the bf16 map (its gradient is never cast), the consumers of the VALUES get the exact
     map; without the site there is no twin"""
