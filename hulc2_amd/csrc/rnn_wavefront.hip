@@ -325,6 +325,7 @@ extern "C" int hulc_rnn_wavefront(const hulc_rnn_wave_desc* d, void* ws, void* s
     if ((!d->tA && (d->ldA % 8 || (uintptr_t)d->wA % 16)) || (!d->tB1 && (d->ldB1 % 8 || (uintptr_t)d->wB1 % 16)) ||
         (!d->tB2 && (d->ldB2 % 8 || (uintptr_t)d->wB2 % 16)))
         return hulc_fail(-4, "hulc_rnn_wavefront: k-major weights must be 16-byte aligned");
+    if (d->tA != d->tB1 || d->tA != d->tB2) return hulc_fail(-3, "hulc_rnn_wavefront: the three weight matrices share one layout (tA == tB1 == tB2)");     // before the first launch: a refused call writes nothing
     hipStream_t s = (hipStream_t)stream;
     WaveP p;
     p.z = d->z; p.z_step = d->z_step;
@@ -380,7 +381,6 @@ extern "C" int hulc_rnn_wavefront(const hulc_rnn_wave_desc* d, void* ws, void* s
         const long n = 2L * d->H * d->B;
         rnn_zero2d_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(p.zt + (long)p.zb_row0 * d->B, p.ld_t, d->B, 2 * d->H);
     }
-    if (d->tA != d->tB1 || d->tA != d->tB2) return hulc_fail(-3, "hulc_rnn_wavefront: the three weight matrices share one layout (tA == tB1 == tB2)");
     if (p.ts) {
         if (d->tA) rnn_wavefront2_kernel<2048, true, true><<<2 * (2048 / 16), 512, 0, s>>>(p);
         else rnn_wavefront2_kernel<2048, false, true><<<2 * (2048 / 16), 512, 0, s>>>(p);

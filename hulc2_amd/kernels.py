@@ -1278,7 +1278,8 @@ def transpose_bf16_tiles(src, dst, tiles):
 def rnn_wavefront(z0, z_step, S, B, H, wA, wB1, wB2, transposed, add1=None, add1_step=0, ld_add1=0, bias1=(None, None), bias2=(None, None),
                   mask1=None, mask1_step=0, ld_mask1=0, mask2=None, mask2_step=0, ld_mask2=0, relu=False, mirror_t=False, add1c=None, zero_edges=False):
     """Both RNN layers of one direction as one persistent kernel (csrc/rnn_wavefront.hip).  z0: view of the (zero) state row
-    wave step 0 reads; rows advance by z_step elements.  Weights are bf16 (H, H) matrices, `transposed` applies to all three."""
+    wave step 0 reads; rows advance by z_step elements.  Weights are bf16 (H, H) matrices, `transposed` applies to all three
+    (or is a 3-tuple, one flag for each of wA, wB1, wB2)."""
     for w in (wA, wB1, wB2):
         if w.dtype != torch.bfloat16:
             raise _L.HulcKernelError("rnn_wavefront: weights must be bf16 shadows (bf16 compute mode)")
@@ -1286,7 +1287,11 @@ def rnn_wavefront(z0, z_step, S, B, H, wA, wB1, wB2, transposed, add1=None, add1
     d.z, d.z_step = z0.data_ptr(), int(z_step)
     d.wA, d.wB1, d.wB2 = wA.data_ptr(), wB1.data_ptr(), wB2.data_ptr()
     d.ldA, d.ldB1, d.ldB2 = wA.stride(0), wB1.stride(0), wB2.stride(0)
-    d.tA = d.tB1 = d.tB2 = int(bool(transposed))
+    if isinstance(transposed, (tuple, list)):                       # one flag per matrix (wA, wB1, wB2): the launcher refuses mixed layouts
+        d.tA, d.tB1, d.tB2 = (int(bool(t)) for t in transposed)
+        transposed = d.tA
+    else:
+        d.tA = d.tB1 = d.tB2 = int(bool(transposed))
     d.add1, d.add1_step, d.ld_add1 = (add1.data_ptr() if add1 is not None else None), int(add1_step), int(ld_add1)
     d.bias1a, d.bias1b = [b.data_ptr() if b is not None else None for b in bias1]
     d.bias2a, d.bias2b = [b.data_ptr() if b is not None else None for b in bias2]

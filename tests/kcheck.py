@@ -1,4 +1,5 @@
-"""Shared pieces of the kernel-level tests (tests/test_reductions_gpu.py, tests/test_losses_gpu.py).
+"""Shared pieces of the kernel-level tests (tests/test_reductions_gpu.py, tests/test_losses_gpu.py, tests/test_ffn_kernel_gpu.py,
+tests/test_rnn_kernel_gpu.py).
 
 Every case of those files follows one pattern:
   1. inputs are drawn on the CPU in float64 from a seeded generator and rounded to the kernel's storage type; the float64 reference is given
@@ -108,6 +109,37 @@ def compare(kernel: str, what: str, got, ref64, ref32, margin: float, grad: bool
     print(f"[kcheck] {kernel:28s} {what:12s} gpu {err:.3e}  cpu-f32 {e_ref:.3e}  ratio {ratio:.2f}  (margin {margin:g})")
     assert err <= margin * base, (f"{kernel} {what}: error {err:.3e} > {margin:g} * max(e_ref {e_ref:.3e}, 2^-23) "
                                   f"(ratio {ratio:.2f}; norm: {'relative L2' if grad else 'max-abs / max-abs'})")
+    return ratio
+
+
+def row_errors(got, ref64) -> torch.Tensor:
+    """per row of a (rows, cols) pair: L2 norm of the difference over L2 norm of the reference row (float64)"""
+    return (got - ref64).norm(dim=1) / ref64.norm(dim=1)
+
+
+def compare_rows(kernel: str, what: str, got, ref64, emu32, margin: float) -> float:
+    """compare() with a LOCALISED norm and an emulation as the yardstick: `got`, the float64 reference and the CPU rounding-point emulation
+    with float32 accumulation are (rows, cols); the error is the maximum over rows of (row L2 error / row L2 norm of the reference) and the
+    bound is margin * max(e_ref, 2^-23) with e_ref the emulation's error in the same norm.  A row is the unit a fault would hit (a token, a
+    sequence, an output feature, a (wave step, batch row, half) of the recurrence): one wrong row fails however many right ones surround it.
+    No row is excluded: a reference row that is exactly zero must come back exactly zero."""
+    got = got.detach().double().cpu()
+    ref64, emu32 = ref64.detach().double().cpu(), emu32.detach().double().cpu()
+    assert got.dim() == 2 and got.shape == ref64.shape == emu32.shape, f"{what}: shapes {tuple(got.shape)} / {tuple(ref64.shape)} / {tuple(emu32.shape)}"
+    assert torch.isfinite(ref64).all() and torch.isfinite(emu32).all(), f"{what}: the reference is not finite (a broken test case)"
+    assert torch.isfinite(got).all(), f"{what}: non-finite values from the kernel"
+    live = ref64.norm(dim=1) > 0
+    assert not got[~live].any(), f"{what}: {int((~live).sum())} reference rows are exactly zero, the kernel left values there"
+    assert live.any(), f"{what}: the reference is zero everywhere (a broken test case)"
+    errs = row_errors(got[live], ref64[live])
+    err, e_ref = errs.max().item(), row_errors(emu32[live], ref64[live]).max().item()
+    base = max(e_ref, EPS32)
+    ratio = err / base
+    RATIOS[kernel] = max(RATIOS.get(kernel, 0.0), ratio)
+    worst = int(live.nonzero()[errs.argmax()])
+    print(f"[kcheck] {kernel:28s} {what:12s} gpu {err:.3e}  cpu-emu32 {e_ref:.3e}  ratio {ratio:.2f}  (margin {margin:g}, worst row {worst} of {got.shape[0]})")
+    assert err <= margin * base, (f"{kernel} {what}: error {err:.3e} > {margin:g} * max(e_ref {e_ref:.3e}, 2^-23) "
+                                  f"(ratio {ratio:.2f}; norm: max over rows of relative L2, worst row {worst})")
     return ratio
 
 
