@@ -4,7 +4,6 @@ Everything here takes device tensors, extracts `data_ptr()` / strides and calls 
 the current torch stream.  No arithmetic happens in Python.
 """
 import ctypes
-from typing import Optional
 
 import torch
 
@@ -203,10 +202,6 @@ def _require_cuda(*ts) -> None:
             )
 
 
-def _p(t: Optional[torch.Tensor]):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
 _scratch = {}
 _step_state = {}
 
@@ -264,7 +259,7 @@ def device_cu_count(device) -> int:
 def advance_step_state(device, rng: bool = True, step: bool = True) -> None:
     """Walk the RNG word and / or bump the optimizer step count (one 1-thread kernel).  The native trainer advances both at the top of a
     step and marks the RNG word fresh, so the `ensure_fresh_rng` inside Hulc2.training_step is then free."""
-    _call("hulc_step_state_advance_words", step_state(device), _i(rng), _i(step))
+    _call("hulc_step_state_advance_words", step_state(device), rng, step)
     if rng:
         _rng_fresh[device] = True
 
@@ -275,7 +270,7 @@ def ensure_fresh_rng(device) -> None:
     once; the optimizer step count (word 1) is never touched here."""
     if _rng_fresh.pop(device, False):
         return
-    _call("hulc_step_state_advance_words", step_state(device), _i(1), _i(0))
+    _call("hulc_step_state_advance_words", step_state(device), 1, 0)
 
 
 def reset_step_state(device, seed: int = 0x243F6A8885A308D3 >> 1, step: int = 0) -> None:
@@ -321,8 +316,7 @@ def gemm(A, B, C, M, N, K, lda, ldb, ldc, a_kmajor=True, b_kmajor=True, bias=Non
     esz = lambda t: t.element_size()
     gbytes = M * K * esz(A) + N * K * esz(B) + M * N * esz(C) * (2 if accumulate else 1) \
         + (M * N * esz(add) if add is not None and ld_add else 0) + (M * N * esz(mask) if mask is not None else 0)
-    with _Timed(("gemm", M, N, K, int(a_kmajor), int(b_kmajor)), 2.0 * M * N * K, float(gbytes)):
-        _L.check(_L.load().hulc_gemm(ctypes.byref(d), ctypes.c_void_p(_stream())), "hulc_gemm")
+    _call("hulc_gemm", ctypes.byref(d), key=("gemm", M, N, K, int(a_kmajor), int(b_kmajor)), flops=2.0 * M * N * K, nbytes=float(gbytes))
     return C
 
 
@@ -428,9 +422,8 @@ def conv2d_fwd(x, w2d, bias, y, N, H, W, Cin, Cout, KH, KW, stride, x_nchw, relu
             raise TypeError("y_bf16: a contiguous bf16 tensor shaped like the fp32 / fp16 output y")
         d.y_bf16 = y_bf16.data_ptr()
     macs = float(N) * oh * ow * Cout * Cin * KH * KW * (3 if w_lo is not None else 1)
-    with _Timed(("conv2d_fwd", N, H, W, Cin, Cout, KH, stride), 2 * macs, _nbytes(x, w2d, y, y_bf16) + (_nbytes(x2) if x2 is not None else 0)):
-        _L.check(_L.load().hulc_conv2d_fwd(ctypes.byref(d), _p(x), _p(w2d), _p(bias), _p(y), ctypes.c_void_p(_stream())),
-                 "hulc_conv2d_fwd")
+    _call("hulc_conv2d_fwd", ctypes.byref(d), x, w2d, bias, y, key=("conv2d_fwd", N, H, W, Cin, Cout, KH, stride), flops=2 * macs,
+          nbytes=_nbytes(x, w2d, y, y_bf16) + (_nbytes(x2) if x2 is not None else 0))
     return y
 
 
@@ -444,9 +437,8 @@ def conv2d_padded_fwd(x, w2d, bias, y, N, H, W, Cin, Cout, KH, KW, stride, pad, 
     d = _conv_desc(N, H, W, Cin, Cout, KH, KW, stride, False, _dt(x), _dt(y), _dt(w2d), relu, compute)
     oh, ow = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
     macs = float(N) * oh * ow * Cout * Cin * KH * KW
-    with _Timed(("conv2d_padded_fwd", N, H, W, Cin, Cout, KH, stride), 2 * macs, _nbytes(x, w2d, y, add)):
-        _L.check(_L.load().hulc_conv2d_padded_fwd(ctypes.byref(d), _i(pad), _p(x), _p(w2d), _p(bias), _p(add), _p(y),
-                                                  ctypes.c_void_p(_stream())), "hulc_conv2d_padded_fwd")
+    _call("hulc_conv2d_padded_fwd", ctypes.byref(d), pad, x, w2d, bias, add, y, key=("conv2d_padded_fwd", N, H, W, Cin, Cout, KH, stride),
+          flops=2 * macs, nbytes=_nbytes(x, w2d, y, add))
     return y
 
 
@@ -459,7 +451,7 @@ def r3m_normalize(x, y, mean3, std3):
     n, _, h, w = x.shape
     m = (ctypes.c_float * 3)(*[float(v) for v in mean3])
     sd = (ctypes.c_float * 3)(*[float(v) for v in std3])
-    _call("hulc_r3m_normalize", x, _i(n), _i(h), _i(w), m, sd, y, _i(_dt(y)))
+    _call("hulc_r3m_normalize", x, n, h, w, m, sd, y, _dt(y))
     return y
 
 
@@ -476,7 +468,7 @@ def r3m_normalize_packed(x, xp, mean3, std3):
         raise TypeError("r3m_normalize_packed: x fp32 (N,3,H,W), xp bf16 (N, H+6, packed width, 4)")
     m = (ctypes.c_float * 3)(*[float(v) for v in mean3])
     sd = (ctypes.c_float * 3)(*[float(v) for v in std3])
-    _call("hulc_r3m_normalize_packed", x, _i(n), _i(h), _i(w), m, sd, xp)
+    _call("hulc_r3m_normalize_packed", x, n, h, w, m, sd, xp)
     return xp
 
 
@@ -485,7 +477,7 @@ def r3m_stem_fwd(xp, w, bias, y, N, H, W, Cout, relu=True):
     _require_contiguous(xp=xp, w=w, y=y)
     oh, ow = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     macs = float(N) * oh * ow * Cout * 147
-    _call("hulc_r3m_stem_fwd", xp, w, bias, y, _i(_dt(y)), _i(N), _i(H), _i(W), _i(Cout), _i(int(relu)),
+    _call("hulc_r3m_stem_fwd", xp, w, bias, y, _dt(y), N, H, W, Cout, int(relu),
           key=("r3m_stem_fwd", N, H, W, Cout), flops=2 * macs, nbytes=_nbytes(xp, w, y))
     return y
 
@@ -493,11 +485,9 @@ def r3m_stem_fwd(xp, w, bias, y, N, H, W, Cout, relu=True):
 def nhwc_bn_train_fwd(z, M, C, gamma, beta, eps, momentum, run_mean, run_var, y, add=None, relu=False, saved=None):
     """nn.BatchNorm2d in training mode over NHWC rows z (M, C) -> y (+ add, ReLU); running statistics updated in place (may be None);
     saved (2, C) fp32 (optional): the batch mean and rstd, what nhwc_bn_train_bwd needs"""
-    lib = _L.load()
-    lib.hulc_nhwc_bn_train_workspace.restype = ctypes.c_long
-    ws = _ws(lib.hulc_nhwc_bn_train_workspace(_l(M), _i(C)), z.device)
-    _call("hulc_nhwc_bn_train_fwd_saved", z, _i(_dt(z)), _l(M), _i(C), gamma, beta, _f(eps), _f(momentum), run_mean, run_var, add,
-          _i(_dt(add) if add is not None else F32), _i(int(relu)), y, _i(_dt(y)), saved, ws)
+    ws = _ws(_L.load().hulc_nhwc_bn_train_workspace(M, C), z.device)
+    _call("hulc_nhwc_bn_train_fwd_saved", z, _dt(z), M, C, gamma, beta, eps, momentum, run_mean, run_var, add,
+          _dt(add) if add is not None else F32, int(relu), y, _dt(y), saved, ws)
     return y
 
 
@@ -509,11 +499,9 @@ def nhwc_bn_train_bwd(dy, y, z, M, C, gamma, saved, dz, g_out=None, dgamma=None,
     if g_out is not None and g_out.dtype != dz.dtype:
         raise TypeError("nhwc_bn_train_bwd: g_out shares dz's dtype")
     _require_contiguous(dy=dy, y=y, z=z, dz=dz, g_out=g_out)
-    lib = _L.load()
-    lib.hulc_nhwc_bn_train_workspace.restype = ctypes.c_long
-    ws = _ws(lib.hulc_nhwc_bn_train_workspace(_l(M), _i(C)), z.device)
-    _call("hulc_nhwc_bn_train_bwd", dy, _i(_dt(dy)), y, _i(_dt(y) if y is not None else F32), z, _l(M), _i(C), gamma, saved, dz, g_out, _i(_dt(dz)),
-          dgamma, dbeta, _i(int(accumulate_params)), ws)
+    ws = _ws(_L.load().hulc_nhwc_bn_train_workspace(M, C), z.device)
+    _call("hulc_nhwc_bn_train_bwd", dy, _dt(dy), y, _dt(y) if y is not None else F32, z, M, C, gamma, saved, dz, g_out, _dt(dz),
+          dgamma, dbeta, int(accumulate_params), ws)
     return dz
 
 
@@ -522,7 +510,7 @@ def maxpool_nhwc_bwd(x, dy, dx, N, H, W, C, k, stride, pad):
     if not (x.dtype == dy.dtype == dx.dtype):
         raise TypeError("maxpool_nhwc_bwd: x, dy, dx share a dtype")
     _require_contiguous(x=x, dy=dy, dx=dx)
-    _call("hulc_maxpool_nhwc_bwd", x, dy, _i(_dt(x)), _i(N), _i(H), _i(W), _i(C), _i(k), _i(stride), _i(pad), dx)
+    _call("hulc_maxpool_nhwc_bwd", x, dy, _dt(x), N, H, W, C, k, stride, pad, dx)
     return dx
 
 
@@ -532,12 +520,12 @@ def nhwc_scatter(x, y, step: int, off: int):
         raise TypeError("nhwc_scatter: x (N, H, W, C) and y (N, Hy, Wy, C) of one dtype")
     _require_contiguous(x=x, y=y)
     n, h, w, c = x.shape
-    _call("hulc_nhwc_scatter", x, _i(_dt(x)), _i(n), _i(h), _i(w), _i(c), _i(y.shape[1]), _i(y.shape[2]), _i(step), _i(off), y)
+    _call("hulc_nhwc_scatter", x, _dt(x), n, h, w, c, y.shape[1], y.shape[2], step, off, y)
     return y
 
 
 def maxpool_nhwc(x, y, N, H, W, C, k, stride, pad):
-    _call("hulc_maxpool_nhwc", x, _i(_dt(x)), _i(N), _i(H), _i(W), _i(C), _i(k), _i(stride), _i(pad), y)
+    _call("hulc_maxpool_nhwc", x, _dt(x), N, H, W, C, k, stride, pad, y)
     return y
 
 
@@ -552,10 +540,8 @@ def conv2d_bwd_data(dy, wt, dx, relu_src, N, H, W, Cin, Cout, KH, KW, stride, co
             raise TypeError("relu_bits: contiguous int32 tensor of N * H * W * Cin / 32 words")
         d.relu_bits = relu_bits.data_ptr()
     macs = float(N) * oh * ow * Cout * Cin * KH * KW
-    with _Timed(("conv2d_bwd_data", N, H, W, Cin, Cout, KH, stride), 2 * macs,
-                _nbytes(dy, wt, dx, relu_bits if relu_bits is not None else relu_src)):
-        _L.check(_L.load().hulc_conv2d_bwd_data(ctypes.byref(d), _p(dy), _p(wt), _p(dx), _p(relu_src),
-                                                ctypes.c_void_p(_stream())), "hulc_conv2d_bwd_data")
+    _call("hulc_conv2d_bwd_data", ctypes.byref(d), dy, wt, dx, relu_src, key=("conv2d_bwd_data", N, H, W, Cin, Cout, KH, stride), flops=2 * macs,
+          nbytes=_nbytes(dy, wt, dx, relu_bits if relu_bits is not None else relu_src))
     return dx
 
 
@@ -565,26 +551,23 @@ def conv2d_bwd_weight(x, dy, dw, db, N, H, W, Cin, Cout, KH, KW, stride, x_nchw,
     accumulate: add into dw / db (gradient arena sinks)."""
     _require_cuda(x, dy, dw, db)
     _require_contiguous(x=x, dy=dy, dw=dw)
-    lib = _L.load()
-    lib.hulc_conv2d_bwd_weight_workspace.restype = ctypes.c_long
     d = _conv_desc(N, H, W, Cin, Cout, KH, KW, stride, x_nchw, F32 if x.dtype == torch.uint8 else _dt(x), _dt(dy), F32, False, compute)
     d.dw_oihw, d.dw_accumulate = int(dw_oihw), int(accumulate)
     _u8_frames(d, x, aug_shift, aug_pad, frame_index)
     _second_frames(d, x, x2, N, Cin, H, W)
     if compute is None and frame_index is None and dy.dtype == torch.bfloat16:
         _slot_fields(d, x, x2, H, W, Cin, Cout, KH, stride, x_nchw)
-    nbytes = lib.hulc_conv2d_bwd_weight_workspace(ctypes.byref(d))
+    nbytes = _L.load().hulc_conv2d_bwd_weight_workspace(ctypes.byref(d))
     ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
     oh, ow = conv_out_hw(H, W, KH, KW, stride)
     macs = float(N) * oh * ow * Cout * Cin * KH * KW
-    with _Timed(("conv2d_bwd_weight", N, H, W, Cin, Cout, KH, stride), 2 * macs, _nbytes(x, dy, dw, db) + (_nbytes(x2) if x2 is not None else 0)):
-        _L.check(lib.hulc_conv2d_bwd_weight(ctypes.byref(d), _p(x), _p(dy), _p(dw), _p(db), _p(ws),
-                                            ctypes.c_void_p(_stream())), "hulc_conv2d_bwd_weight")
+    _call("hulc_conv2d_bwd_weight", ctypes.byref(d), x, dy, dw, db, ws, key=("conv2d_bwd_weight", N, H, W, Cin, Cout, KH, stride), flops=2 * macs,
+          nbytes=_nbytes(x, dy, dw, db) + (_nbytes(x2) if x2 is not None else 0))
     return dw, db
 
 
 # ------------------------------------------------------------------------------------------------
-# generic call helper: tensors -> pointers, python numbers -> ctypes by annotation
+# generic call helper: tensors -> addresses; python numbers are converted by the prototypes lib.load() took from the header
 # ------------------------------------------------------------------------------------------------
 _c = ctypes
 
@@ -595,43 +578,34 @@ def _call(name, *args, key=None, flops=0.0, nbytes=0.0):
     for a in args:
         if isinstance(a, torch.Tensor):
             _require_cuda(a)
-            conv.append(_c.c_void_p(a.data_ptr()))
-        elif a is None:
-            conv.append(_c.c_void_p(0))
-        else:
-            conv.append(a)
-    conv.append(_c.c_void_p(_stream()))
+            a = a.data_ptr()
+        conv.append(a)
     with _Timed(key or (name,), flops, nbytes):
-        _L.check(getattr(lib, name)(*conv), name)
+        _L.check(getattr(lib, name)(*conv, _stream()), name)
 
 
 def _ws(nbytes: int, device) -> torch.Tensor:
     return torch.empty(max(int(nbytes) // 4, 1), dtype=torch.float32, device=device)
 
 
-def _i(v):
-    return _c.c_int(int(v))
-
-
-def _l(v):
-    return _c.c_long(int(v))
-
-
-def _f(v):
-    return _c.c_float(float(v))
-
-
-def _u64(v):
-    return _c.c_ulonglong(int(v) & 0xFFFFFFFFFFFFFFFF)
+def _cached_ws(cache, key, need: int, numel: int, alloc=torch.zeros) -> torch.Tensor:
+    """the workspace `cache` holds for key = (device, stream[, tag]): allocated (`numel` floats) when missing or smaller than `need` bytes, and
+    not cached while the stream is capturing (memory of a graph's pool must not outlive the graph in the cache)"""
+    ws = cache.get(key)
+    if ws is None or ws.numel() * 4 < need:
+        ws = alloc(numel, dtype=torch.float32, device=key[0])
+        if not torch.cuda.is_current_stream_capturing():
+            cache[key] = ws
+    return ws
 
 
 def spatial_softmax_fwd(x, N, HW, C, xmap, ymap, temperature, out, stats):
-    _call("hulc_spatial_softmax_fwd", x, _i(_dt(x)), _i(N), _i(HW), _i(C), xmap, ymap, temperature, out, stats)
+    _call("hulc_spatial_softmax_fwd", x, _dt(x), N, HW, C, xmap, ymap, temperature, out, stats)
 
 
 def spatial_softmax_bwd(x, N, HW, C, xmap, ymap, temperature, out, stats, dout, dx, relu_mask=True):
-    _call("hulc_spatial_softmax_bwd", x, _i(_dt(x)), _i(N), _i(HW), _i(C), xmap, ymap, temperature, out, stats, dout, dx,
-          _i(_dt(dx)), _i(relu_mask))
+    _call("hulc_spatial_softmax_bwd", x, _dt(x), N, HW, C, xmap, ymap, temperature, out, stats, dout, dx,
+          _dt(dx), relu_mask)
 
 
 def _sd(t, drop_p):
@@ -639,54 +613,50 @@ def _sd(t, drop_p):
 
 
 def layernorm_fwd(x, o, drop_p, seed, gamma, beta, eps, R, D, pre_out, y, mean, rstd):
-    _call("hulc_layernorm_fwd", x, o, _f(drop_p), _u64(seed), _sd(x, drop_p), gamma, beta, _f(eps), _i(R), _i(D), pre_out, y, mean, rstd)
+    _call("hulc_layernorm_fwd", x, o, drop_p, seed, _sd(x, drop_p), gamma, beta, eps, R, D, pre_out, y, mean, rstd)
 
 
 def layernorm_bwd(dy, pre, mean, rstd, gamma, R, D, dpre, do_out, drop_p, seed, dgamma, dbeta, accumulate_params=False):
-    lib = _L.load()
-    lib.hulc_layernorm_bwd_workspace.restype = _c.c_long
-    ws = _ws(lib.hulc_layernorm_bwd_workspace(_i(R), _i(D)), dy.device)
-    _call("hulc_layernorm_bwd", dy, pre, mean, rstd, gamma, _i(R), _i(D), dpre, do_out, _f(drop_p), _u64(seed), _sd(dy, drop_p), dgamma,
-          dbeta, _i(accumulate_params), ws)
+    ws = _ws(_L.load().hulc_layernorm_bwd_workspace(R, D), dy.device)
+    _call("hulc_layernorm_bwd", dy, pre, mean, rstd, gamma, R, D, dpre, do_out, drop_p, seed, _sd(dy, drop_p), dgamma,
+          dbeta, accumulate_params, ws)
 
 
 def colsum(x, M, N, ld, out, accumulate=False):
-    lib = _L.load()
-    lib.hulc_colsum_workspace.restype = _c.c_long
-    ws = _ws(lib.hulc_colsum_workspace(_l(M), _i(N)), x.device)
-    _call("hulc_colsum", x, _i(_dt(x)), _l(M), _i(N), _l(ld), out, _i(accumulate), ws, nbytes=float(M) * N * x.element_size())
+    ws = _ws(_L.load().hulc_colsum_workspace(M, N), x.device)
+    _call("hulc_colsum", x, _dt(x), M, N, ld, out, accumulate, ws, nbytes=float(M) * N * x.element_size())
 
 
 def seq_mean_fwd(x, y, B, S, D, scale=1.0):
-    _call("hulc_seq_mean_fwd", x, y, _i(B), _i(S), _i(D), _f(scale))
+    _call("hulc_seq_mean_fwd", x, y, B, S, D, scale)
 
 
 def strided_seq_sum(x, y, B, S, D, stride_b, stride_s, ldy, scale=1.0):
-    _call("hulc_strided_seq_sum", x, _i(_dt(x)), y, _i(B), _i(S), _i(D), _l(stride_b), _l(stride_s), _l(ldy), _f(scale))
+    _call("hulc_strided_seq_sum", x, _dt(x), y, B, S, D, stride_b, stride_s, ldy, scale)
 
 
 def seq_mean_bwd(dy, dx, B, S, D):
-    _call("hulc_seq_mean_bwd", dy, dx, _i(B), _i(S), _i(D))
+    _call("hulc_seq_mean_bwd", dy, dx, B, S, D)
 
 
 def add_pos_fwd(x, pos, pos_ids, y, B, S, D, drop_p, seed):
-    _call("hulc_add_pos_fwd", x, pos, pos_ids, y, _i(B), _i(S), _i(D), _f(drop_p), _u64(seed), _sd(x, drop_p))
+    _call("hulc_add_pos_fwd", x, pos, pos_ids, y, B, S, D, drop_p, seed, _sd(x, drop_p))
 
 
 def dropout_bwd(dy, dx, n, drop_p, seed):
-    _call("hulc_dropout_bwd", dy, dx, _l(n), _f(drop_p), _u64(seed), _sd(dy, drop_p))
+    _call("hulc_dropout_bwd", dy, dx, n, drop_p, seed, _sd(dy, drop_p))
 
 
 def relu_bwd(dy, y, dx, n, scale=1.0):
-    _call("hulc_relu_bwd", dy, y, _i(_dt(y)), dx, _l(n), _f(scale))
+    _call("hulc_relu_bwd", dy, y, _dt(y), dx, n, scale)
 
 
 def attention_fwd(qkv, out, probs, B, S, H, head_dim, drop_p, seed):
-    _call("hulc_attention_fwd", qkv, out, probs, _i(B), _i(S), _i(H), _i(head_dim), _f(drop_p), _u64(seed), _sd(qkv, drop_p))
+    _call("hulc_attention_fwd", qkv, out, probs, B, S, H, head_dim, drop_p, seed, _sd(qkv, drop_p))
 
 
 def attention_bwd(qkv, probs, dout, dqkv, B, S, H, head_dim, drop_p, seed):
-    _call("hulc_attention_bwd", qkv, probs, dout, dqkv, _i(B), _i(S), _i(H), _i(head_dim), _f(drop_p), _u64(seed), _sd(qkv, drop_p))
+    _call("hulc_attention_bwd", qkv, probs, dout, dqkv, B, S, H, head_dim, drop_p, seed, _sd(qkv, drop_p))
 
 
 def _mix_desc(T, A, n_mix, num_classes, ld, log_scale_min, gripper_alpha, act_min, act_max, nseg=1, time_major_B=0):
@@ -838,11 +808,11 @@ def _call_shared(share: int, name, *args, **kw):
     if share <= 1:
         return _call(name, *args, **kw)
     lib = _L.load()
-    lib.hulc_set_coop_share(_i(share))
+    lib.hulc_set_coop_share(share)
     try:
         _call(name, *args, **kw)
     finally:
-        lib.hulc_set_coop_share(_i(1))
+        lib.hulc_set_coop_share(1)
 
 
 def gemm_fuses_rowsum(M: int, a_kmajor: bool) -> bool:
@@ -902,22 +872,14 @@ def _chain_desc(x0, layers, M):
 def _chain_workspace(device, need: int):
     # persistent workspace per (device, stream): its header (barrier counters) is zero before the first launch and every launch leaves it
     # zero; check_faults clears it after a barrier timeout (the one case that leaves counts behind)
-    key = (device, _stream())
-    ws = _chain_ws.get(key)
-    if ws is None or ws.numel() * 4 < need:
-        ws = torch.zeros(max(need, 4 << 20) // 4 + 1, dtype=torch.float32, device=device)
-        if not torch.cuda.is_current_stream_capturing():
-            _chain_ws[key] = ws
-    return ws
+    return _cached_ws(_chain_ws, (device, _stream()), need, max(need, 4 << 20) // 4 + 1)
 
 
 def mlp_chain(x0, layers, M, share=None):
     """layers: [(W bf16 [N][K] k-major, bias fp32 or None, relu flag, mask fp32 (M, N) or None, mask_scale, out fp32 (M, N))]; one persistent
     launch (csrc/mlp_chain.hip).  x0 fp32 (M, K0), unit inner stride."""
     d, flops, nbytes = _chain_desc(x0, layers, M)
-    lib = _L.load()
-    lib.hulc_mlp_chain_workspace.restype = _c.c_long
-    ws = _chain_workspace(x0.device, int(lib.hulc_mlp_chain_workspace(_c.byref(d))))
+    ws = _chain_workspace(x0.device, _L.load().hulc_mlp_chain_workspace(_c.byref(d)))
     _call_shared(share, "hulc_mlp_chain", _c.byref(d), ws, fault_word(x0.device), key=("mlp_chain", M, int(x0.shape[1])) + tuple(int(l[0].shape[0]) for l in layers),
                  flops=flops, nbytes=nbytes)
 
@@ -935,8 +897,7 @@ def mlp_chain2(xa, layers_a, Ma, xb, layers_b, Mb, share=None):
     da, fa, na = _chain_desc(xa, layers_a, Ma)
     db, fb, nb = _chain_desc(xb, layers_b, Mb)
     lib = _L.load()
-    lib.hulc_mlp_chain_workspace.restype = _c.c_long
-    ws = _chain_workspace(xa.device, int(lib.hulc_mlp_chain_workspace(_c.byref(da))) + int(lib.hulc_mlp_chain_workspace(_c.byref(db))))
+    ws = _chain_workspace(xa.device, lib.hulc_mlp_chain_workspace(_c.byref(da)) + lib.hulc_mlp_chain_workspace(_c.byref(db)))
     _call_shared(share, "hulc_mlp_chain2", _c.byref(da), _c.byref(db), ws, fault_word(xa.device),
           key=("mlp_chain2", Ma, Mb, int(xa.shape[1]), int(xb.shape[1])) + tuple(int(l[0].shape[0]) for l in layers_a), flops=fa + fb, nbytes=na + nb)
 
@@ -1056,25 +1017,14 @@ def _wgrad_issue(dev) -> None:
         it.conv_taps_wp = rest[3] if len(rest) > 3 else 0
         flops += 2.0 * M * N * K * (9 if (len(rest) > 3 and rest[3]) else 1)
         nbytes += K * M * A.element_size() + K * N * B.element_size() + M * N * 4 * (2 if acc else 1)
-    lib = _L.load()
-    lib.hulc_wgrad_group_workspace.restype = _c.c_long
-    need = int(lib.hulc_wgrad_group_workspace(items, _i(n)))
+    need = _L.load().hulc_wgrad_group_workspace(items, n)
     with torch.cuda.device(dev):
-        key = (dev, _stream())
-        ws = _wg_ws.get(key)
-        if ws is None or ws.numel() * 4 < need:
-            ws = torch.zeros((need + (8 << 20)) // 4, dtype=torch.float32, device=dev)
-            if not torch.cuda.is_current_stream_capturing():      # (memory of a graph's pool must not outlive the graph in this cache)
-                _wg_ws[key] = ws
-        with _Timed(("wgrad_group", n), flops, nbytes):
-            _L.check(lib.hulc_wgrad_group(items, _i(n), _c.c_void_p(ws.data_ptr()), _l(ws.numel() * 4), _c.c_void_p(_stream())),
-                     "hulc_wgrad_group")
+        ws = _cached_ws(_wg_ws, (dev, _stream()), need, (need + (8 << 20)) // 4)
+        _call("hulc_wgrad_group", items, n, ws, ws.numel() * 4, key=("wgrad_group", n), flops=flops, nbytes=nbytes)
 
 
 def _ffn_ws(T, FF, device):
-    lib = _L.load()
-    lib.hulc_ffn_workspace.restype = _c.c_long
-    return _ws(lib.hulc_ffn_workspace(_i(T), _i(FF)), device)
+    return _ws(_L.load().hulc_ffn_workspace(T, FF), device)
 
 
 def ffn_fwd(x, W1, b1, W2, b2, T, D, FF, drop_p, seed, f):
@@ -1082,7 +1032,7 @@ def ffn_fwd(x, W1, b1, W2, b2, T, D, FF, drop_p, seed, f):
     unsummed in the returned workspace ((FF / 128, T, 128) fp32 at its start) for a consumer that sums them (layernorm_slab_fwd)."""
     fl = 2.0 * 2 * T * D * FF
     ws = _ffn_ws(T, FF, x.device)
-    _call("hulc_ffn_fwd", x, W1, b1, W2, b2, _i(T), _i(D), _i(FF), _f(drop_p), _u64(seed), _sd(x, drop_p), f, ws,
+    _call("hulc_ffn_fwd", x, W1, b1, W2, b2, T, D, FF, drop_p, seed, _sd(x, drop_p), f, ws,
           key=("ffn_fwd", T, D, FF), flops=fl, nbytes=_nbytes(x, W1, W2, f))
     return ws
 
@@ -1090,21 +1040,21 @@ def ffn_fwd(x, W1, b1, W2, b2, T, D, FF, drop_p, seed, f):
 def ffn_bwd(x, df, W1, b1, W1T, W2T, T, D, FF, drop_p, seed, dx, dW1, db1, dW2, accumulate_params=False, dx_accumulate=False):
     fl = 2.0 * 5 * T * D * FF                                  # recompute + two data-gradient + two weight-gradient products
     ws = _ffn_ws(T, FF, x.device)                              # dx = None: the slice partials of dx stay at the start of ws
-    _call("hulc_ffn_bwd", x, df, W1, b1, W1T, W2T, _i(T), _i(D), _i(FF), _f(drop_p), _u64(seed), _sd(x, drop_p), dx, _i(dx_accumulate),
-          dW1, db1, dW2, _i(accumulate_params), ws,
+    _call("hulc_ffn_bwd", x, df, W1, b1, W1T, W2T, T, D, FF, drop_p, seed, _sd(x, drop_p), dx, dx_accumulate,
+          dW1, db1, dW2, accumulate_params, ws,
           key=("ffn_bwd", T, D, FF), flops=fl, nbytes=_nbytes(x, df, W1, W1T, W2T, dx, dW1, dW2))
     return ws
 
 
 def layernorm_slab_fwd(x, o_slabs, n_o, o_stride, drop_p, seed, gamma, beta, eps, R, D, pre_out, y, mean, rstd):
     """y = LayerNorm(x + dropout(sum of the n_o partial slabs)) — slice sum + residual + norm in one launch"""
-    _call("hulc_layernorm_slab_fwd", x, o_slabs, _i(n_o), _l(o_stride), _f(drop_p), _u64(seed), _sd(x, drop_p), gamma, beta, _f(eps), _i(R), _i(D),
+    _call("hulc_layernorm_slab_fwd", x, o_slabs, n_o, o_stride, drop_p, seed, _sd(x, drop_p), gamma, beta, eps, R, D,
           pre_out, y, mean, rstd)
 
 
 def ln_partial_reduce(partial, P, D, dgamma, dbeta, accumulate=False):
     """partial (P, 2, D): rows of [dgamma | dbeta] partial sums -> the two parameter gradients, fixed order, one launch"""
-    _call("hulc_ln_partial_reduce", partial, _i(P), _i(D), dgamma, dbeta, _i(accumulate))
+    _call("hulc_ln_partial_reduce", partial, P, D, dgamma, dbeta, accumulate)
 
 
 def ln_partial_reduce_multi(partial, P, D, dgammas, dbetas, accumulates):
@@ -1114,7 +1064,7 @@ def ln_partial_reduce_multi(partial, P, D, dgammas, dbetas, accumulates):
     dg = (_c.c_void_p * n)(*[t.data_ptr() for t in dgammas])
     db = (_c.c_void_p * n)(*[t.data_ptr() for t in dbetas])
     acc = (_c.c_int * n)(*[int(bool(a)) for a in accumulates])
-    _call("hulc_ln_partial_reduce_multi", partial, _i(n), _i(P), _i(D), dg, db, acc)
+    _call("hulc_ln_partial_reduce_multi", partial, n, P, D, dg, db, acc)
 
 
 def _txl_desc(x, Wqkv, bqkv, gamma, B, S, H, drop_p, seed_attn, seed_ln, eps):
@@ -1177,13 +1127,13 @@ def mlp2_rows_ok(x, W1, W2) -> bool:
 
 def mlp2_rows_fwd(x, W1, b1, W2, b2, y, W1_lo=None, W2_lo=None):
     T, H, OUT = x.shape[0], W1.shape[0], W2.shape[0]
-    _call("hulc_mlp2_rows_fwd", x, W1, b1, W2, b2, W1_lo, W2_lo, _i(T), _i(128), _i(H), _i(OUT), y, key=("mlp2_rows_fwd", T, H, OUT, W1_lo is not None),
+    _call("hulc_mlp2_rows_fwd", x, W1, b1, W2, b2, W1_lo, W2_lo, T, 128, H, OUT, y, key=("mlp2_rows_fwd", T, H, OUT, W1_lo is not None),
           flops=2.0 * T * H * (128 + OUT) * (3 if W1_lo is not None else 1), nbytes=_nbytes(x, W1, W2, y))
 
 
 def mlp2_rows_bwd(x, dy, W1, b1, W1T, W2T, dx, h, dh):
     T, H, OUT = x.shape[0], W1.shape[0], W2T.shape[1]
-    _call("hulc_mlp2_rows_bwd", x, dy, W1, b1, W1T, W2T, _i(T), _i(128), _i(H), _i(OUT), dx, h, dh, key=("mlp2_rows_bwd", T, H, OUT),
+    _call("hulc_mlp2_rows_bwd", x, dy, W1, b1, W1T, W2T, T, 128, H, OUT, dx, h, dh, key=("mlp2_rows_bwd", T, H, OUT),
           flops=2.0 * T * H * (2 * 128 + OUT), nbytes=_nbytes(x, dy, W1, W1T, W2T, dx, h, dh))
 
 
@@ -1204,15 +1154,8 @@ def txl_block_desc(emb, pos, pos_ids, B, S, H, FF, drop_p, seed_pos, eps, layers
     import os
     d.exclusive = int(not concurrent_streams() and not os.environ.get("HULC_TXL_NO_SHARE"))
     if d.exclusive:
-        lib = _L.load()
-        lib.hulc_txl_block_workspace.restype = _c.c_long
-        need = int(lib.hulc_txl_block_workspace(_i(B), _i(len(layers))))
-        key = (emb.device, _stream(), "txl")
-        ws = _chain_ws.get(key)
-        if ws is None or ws.numel() * 4 < need:
-            ws = torch.zeros(need // 4 + 1, dtype=torch.float32, device=emb.device)
-            if not torch.cuda.is_current_stream_capturing():
-                _chain_ws[key] = ws
+        need = _L.load().hulc_txl_block_workspace(B, len(layers))
+        ws = _cached_ws(_chain_ws, (emb.device, _stream(), "txl"), need, need // 4 + 1)
         d._ws = ws                                   # (kept alive with the description)
         d.ws, d.err_sticky = ws.data_ptr(), fault_word(emb.device).data_ptr()
     for i, rec in enumerate(layers):
@@ -1248,31 +1191,30 @@ def txl_block_bwd(d, B, S, H, E, FF, L, share=None):
 
 def residual_bf16(p32, hi, lo, segments):
     """lo = bf16(p32 - float(hi)) on the segments {src offset, count, dst offset} (int64 (n, 3) device tensor)"""
-    _call("hulc_residual_bf16", p32, hi, lo, segments, _i(segments.shape[0]))
+    _call("hulc_residual_bf16", p32, hi, lo, segments, segments.shape[0])
 
 
 def gather_chunks(src0, src1, dst, idx):
     """dst 8-byte chunk c = chunk idx[c] of src0 (or of src1 when bit 31 is set): the packed weight copies of a step in one launch"""
-    _call("hulc_gather_chunks", src0, src1, dst, idx, _l(idx.numel()))
+    _call("hulc_gather_chunks", src0, src1, dst, idx, idx.numel())
 
 
 def ffn_frag_perm(layout: int, FF: int):
     """host: numpy int32 (FF * 128,) — hulc_ffn_frag_perm (include/hulc2_amd.h)"""
     import numpy as np
     out = np.empty(FF * 128, dtype=np.int32)
-    lib = _L.load()
-    _L.check(lib.hulc_ffn_frag_perm(_i(layout), _i(FF), out.ctypes.data_as(_c.c_void_p)), "hulc_ffn_frag_perm")
+    _L.check(_L.load().hulc_ffn_frag_perm(layout, FF, out.ctypes.data), "hulc_ffn_frag_perm")
     return out
 
 
 def repack_conv_weights(src_f32, dst_bf16, table):
     """table: int64 (n, 7) device tensor {src offset, dst offset, Cout, Cin, KH, KW, mode} (mode 0 oihw_flat, 1 ohwi, 2 ihwo)"""
-    _call("hulc_repack_conv_weights", src_f32, dst_bf16, table, _i(table.shape[0]))
+    _call("hulc_repack_conv_weights", src_f32, dst_bf16, table, table.shape[0])
 
 
 def transpose_bf16_tiles(src, dst, tiles):
     """tiles: int64 (ntiles, 5) device tensor {offset, rows, cols, tile row, tile col}"""
-    _call("hulc_transpose_bf16_tiles", src, dst, tiles, _i(tiles.shape[0]))
+    _call("hulc_transpose_bf16_tiles", src, dst, tiles, tiles.shape[0])
 
 
 def rnn_wavefront(z0, z_step, S, B, H, wA, wB1, wB2, transposed, add1=None, add1_step=0, ld_add1=0, bias1=(None, None), bias2=(None, None),
@@ -1303,20 +1245,17 @@ def rnn_wavefront(z0, z_step, S, B, H, wA, wB1, wB2, transposed, add1=None, add1
     d.add1c, d.ld_add1c = (add1c.data_ptr(), add1c.stride(0)) if add1c is not None else (None, 0)
     d.zero_edges = int(bool(zero_edges))
     lib = _L.load()
-    lib.hulc_rnn_wavefront_workspace.restype = _c.c_long
-    ws = _ws(lib.hulc_rnn_wavefront_workspace(_i(S), _i(B), _i(H)), z0.device)
+    ws = _ws(lib.hulc_rnn_wavefront_workspace(S, B, H), z0.device)
     # algorithmic work: S wave steps of a (B x 2H) x (2H x 2H) product with one H x H block structurally zero; bytes: the
     # three weight matrices once, per step the fp32 state row written + the bf16 copy written and read + add / masks read
     flops = 2.0 * B * 3 * H * H * S
     nbytes = 3.0 * H * H * 2 + S * B * (2 * H * 4 + 2 * 2 * H * 2 + (H * 4 if add1 is not None else 0)
                                         + (H * 4 if mask1 is not None else 0) + (H * 4 if mask2 is not None else 0))
     _call("hulc_rnn_wavefront", _c.byref(d), ws, key=("rnn_wavefront", S, B, H, int(bool(transposed))), flops=flops, nbytes=nbytes)
-    lib.hulc_rnn_wavefront_mirror_offset.restype = ctypes.c_long
-    lib.hulc_rnn_wavefront_mirror_t_offset.restype = ctypes.c_long
     off = lib.hulc_rnn_wavefront_mirror_offset() // 2
     w16 = ws.view(torch.bfloat16)
     z16 = w16[off:off + (S + 2) * B * 2 * H].view(S + 2, B, 2 * H)
-    offt = lib.hulc_rnn_wavefront_mirror_t_offset(_i(S), _i(B), _i(H)) // 2
+    offt = lib.hulc_rnn_wavefront_mirror_t_offset(S, B, H) // 2
     z16t = w16[offt:offt + (S + 2) * B * 2 * H].view(2 * H, (S + 2) * B) if (offt and mirror_t) else None     # (feature, token = row * B + b)
     return z16, z16t      # bf16 mirror of the S+2 state rows
 
@@ -1324,57 +1263,55 @@ def rnn_wavefront(z0, z_step, S, B, H, wA, wB1, wB2, transposed, add1=None, add1
 def mix_loss_fwd(y, act, out, T, A, n_mix, num_classes, ld, log_scale_min, gripper_alpha, act_min, act_max, nseg=1, time_major_B=0):
     """out: (nseg, 3) = {total, nll_mean, ce_mean} per segment of T / nseg tokens (time_major_B: see hulc_mix_desc)."""
     d = _mix_desc(T, A, n_mix, num_classes, ld, log_scale_min, gripper_alpha, act_min, act_max, nseg, time_major_B)
-    lib = _L.load()
-    lib.hulc_mix_loss_workspace.restype = _c.c_long
-    ws = _ws(lib.hulc_mix_loss_workspace(_c.byref(d)), y.device)
+    ws = _ws(_L.load().hulc_mix_loss_workspace(_c.byref(d)), y.device)
     _call("hulc_mix_loss_fwd", _c.byref(d), y, act, out, ws)
 
 
 def mix_loss_bwd(y, act, gout, dy, ld_dy, T, A, n_mix, num_classes, ld, log_scale_min, gripper_alpha, act_min, act_max, nseg=1, time_major_B=0):
     """writes every column of dy (the pad columns beyond 3 * A * n_mix + 2 as zeros)"""
     d = _mix_desc(T, A, n_mix, num_classes, ld, log_scale_min, gripper_alpha, act_min, act_max, nseg, time_major_B)
-    _call("hulc_mix_loss_bwd", _c.byref(d), y, act, gout, dy, _l(ld_dy))
+    _call("hulc_mix_loss_bwd", _c.byref(d), y, act, gout, dy, ld_dy)
 
 
 def cat_kl_fwd(pp, pr, B, G, CLS, beta, out, kl_group, nseg=1):
-    _call("hulc_cat_kl_fwd", pp, pr, _i(B), _i(G), _i(CLS), _f(beta), _i(nseg), out, kl_group)
+    _call("hulc_cat_kl_fwd", pp, pr, B, G, CLS, beta, nseg, out, kl_group)
 
 
 def cat_kl_bwd(pp, pr, kl_group, B, G, CLS, beta, mix, gout, dpp, dpr, nseg=1):
-    _call("hulc_cat_kl_bwd", pp, pr, kl_group, _i(B), _i(G), _i(CLS), _f(beta), _f(mix), gout, _i(nseg), dpp, dpr)
+    _call("hulc_cat_kl_bwd", pp, pr, kl_group, B, G, CLS, beta, mix, gout, nseg, dpp, dpr)
 
 
 def plan_sample_fwd(logits, idx_in, seed, NG, CLS, idx_out, plan):
-    _call("hulc_plan_sample_fwd", logits, idx_in, _u64(seed), step_state(logits.device) if idx_in is None else None, _i(NG), _i(CLS),
+    _call("hulc_plan_sample_fwd", logits, idx_in, seed, step_state(logits.device) if idx_in is None else None, NG, CLS,
           idx_out, plan)
 
 
 def plan_sample_bwd(logits, dplan, NG, CLS, dlogits, accumulate=False):
-    _call("hulc_plan_sample_bwd", logits, dplan, _i(NG), _i(CLS), dlogits, _i(accumulate))
+    _call("hulc_plan_sample_bwd", logits, dplan, NG, CLS, dlogits, accumulate)
 
 
 def clip_loss_fwd(im, tx, use, logit_scale, M, D, out, row0=0):
-    _call("hulc_clip_loss_fwd", im, tx, use, _i(row0), logit_scale, _i(M), _i(D), out)
+    _call("hulc_clip_loss_fwd", im, tx, use, row0, logit_scale, M, D, out)
 
 
 def clip_loss_bwd(im, tx, use, logit_scale, M, D, gout, dim, dtx, dscale, row0=0):
-    _call("hulc_clip_loss_bwd", im, tx, use, _i(row0), logit_scale, _i(M), _i(D), gout, dim, dtx, dscale)
+    _call("hulc_clip_loss_bwd", im, tx, use, row0, logit_scale, M, D, gout, dim, dtx, dscale)
 
 
 def loss_combine_fwd(kls, acts, clip, n, beta, out):
-    _call("hulc_loss_combine_fwd", kls, acts, clip, _i(n), _f(beta), out)
+    _call("hulc_loss_combine_fwd", kls, acts, clip, n, beta, out)
 
 
 def loss_combine_bwd(g, n, beta, dkls, dacts, dclip):
-    _call("hulc_loss_combine_bwd", g, _i(n), _f(beta), dkls, dacts, dclip)
+    _call("hulc_loss_combine_bwd", g, n, beta, dkls, dacts, dclip)
 
 
 def emb_fanout_fwd(emb, N, S, D, n_last, lo, hi, e0, elast, edec_t):
-    _call("hulc_emb_fanout_fwd", emb, _i(N), _i(S), _i(D), _i(n_last), _i(lo), _i(hi), e0, elast, edec_t)
+    _call("hulc_emb_fanout_fwd", emb, N, S, D, n_last, lo, hi, e0, elast, edec_t)
 
 
 def emb_fanin_bwd(g_rec, g0, g_last, g_dec_t, N, S, D, n_last, lo, hi, demb):
-    _call("hulc_emb_fanin_bwd", g_rec, g0, g_last, g_dec_t, _i(N), _i(S), _i(D), _i(n_last), _i(lo), _i(hi), demb)
+    _call("hulc_emb_fanin_bwd", g_rec, g0, g_last, g_dec_t, N, S, D, n_last, lo, hi, demb)
 
 
 def actions_time_major(acts, obss, B, S, obs_dim, to_tcp, out):
@@ -1385,58 +1322,56 @@ def actions_time_major(acts, obss, B, S, obs_dim, to_tcp, out):
     O = (_c.c_void_p * n)(*[o.data_ptr() for o in obss]) if to_tcp else None
     if to_tcp:
         _require_cuda(*obss)
-    _call("hulc_actions_time_major", A, O, _i(n), _i(B), _i(S), _i(obs_dim), _i(int(bool(to_tcp))), out)
+    _call("hulc_actions_time_major", A, O, n, B, S, obs_dim, int(bool(to_tcp)), out)
 
 
 def layernorm_fwd_ld(x, gamma, beta, eps, R, D, y, ld_y, mean, rstd):
-    _call("hulc_layernorm_fwd_ld", x, gamma, beta, _f(eps), _i(R), _i(D), y, _l(ld_y), mean, rstd)
+    _call("hulc_layernorm_fwd_ld", x, gamma, beta, eps, R, D, y, ld_y, mean, rstd)
 
 
 def layernorm_bwd_ld(dy, ld_dy, pre, mean, rstd, gamma, R, D, dpre, dgamma, dbeta, accumulate_params=False):
-    lib = _L.load()
-    lib.hulc_layernorm_bwd_workspace.restype = _c.c_long
-    ws = _ws(lib.hulc_layernorm_bwd_workspace(_i(R), _i(D)), dy.device)
-    _call("hulc_layernorm_bwd_ld", dy, _l(ld_dy), pre, mean, rstd, gamma, _i(R), _i(D), dpre, dgamma, dbeta, _i(accumulate_params), ws)
+    ws = _ws(_L.load().hulc_layernorm_bwd_workspace(R, D), dy.device)
+    _call("hulc_layernorm_bwd_ld", dy, ld_dy, pre, mean, rstd, gamma, R, D, dpre, dgamma, dbeta, accumulate_params, ws)
 
 
 def world_to_tcp(act, robot_obs, n, obs_dim, out):
-    _call("hulc_world_to_tcp", act, robot_obs, _i(n), _i(obs_dim), out)
+    _call("hulc_world_to_tcp", act, robot_obs, n, obs_dim, out)
 
 
 # ---- sentence encoder pieces (csrc/lang_encoder.hip) --------------------------------------------------------------
 def embed_ln_fwd(ids, word, pos, type0, gamma, beta, eps, T, S, D, out):
     if ids.dtype != torch.int64 or not ids.is_contiguous():
         raise TypeError("embed_ln_fwd: token ids are a contiguous int64 tensor")
-    _call("hulc_embed_ln_fwd", ids, word, pos, type0, gamma, beta, _f(eps), _i(T), _i(S), _i(D), out)
+    _call("hulc_embed_ln_fwd", ids, word, pos, type0, gamma, beta, eps, T, S, D, out)
     return out
 
 
 def ln_wide_fwd(x, add, gamma, beta, eps, R, D, y):
-    _call("hulc_ln_wide_fwd", x, add, gamma, beta, _f(eps), _i(R), _i(D), y)
+    _call("hulc_ln_wide_fwd", x, add, gamma, beta, eps, R, D, y)
     return y
 
 
 def mha_masked_fwd(qkv, mask, B, S, nhead, hd, out):
     if mask.dtype != torch.int32 or not mask.is_contiguous():
         raise TypeError("mha_masked_fwd: the padding mask is a contiguous int32 (B, S) tensor")
-    _call("hulc_mha_masked_fwd", qkv, mask, _i(B), _i(S), _i(nhead), _i(hd), out)
+    _call("hulc_mha_masked_fwd", qkv, mask, B, S, nhead, hd, out)
     return out
 
 
 def masked_mean_fwd(x, mask, B, S, D, out):
-    _call("hulc_masked_mean_fwd", x, mask, _i(B), _i(S), _i(D), out)
+    _call("hulc_masked_mean_fwd", x, mask, B, S, D, out)
     return out
 
 
 def tcp_to_world(act, robot_obs, n, obs_dim, out):
-    _call("hulc_tcp_to_world", act, robot_obs, _i(n), _i(obs_dim), out)
+    _call("hulc_tcp_to_world", act, robot_obs, n, obs_dim, out)
 
 
 def mix_sample(y, ld, T, A, n_mix, log_scale_min, gripper_bounds, act_out, seed, u_mix=None, u_inv=None, idx_out=None):
     """LogisticDecoderRNN._sample; u_mix / u_inv inject the uniforms (parity tests), else the counter RNG on `seed`."""
     d = _mix_desc(T, A, n_mix, 0, ld, log_scale_min, 0.0, gripper_bounds, gripper_bounds)
     # validation / rollout run outside the training graphs: the caller advances `seed` itself, no device step word involved
-    _call("hulc_mix_sample", _c.byref(d), y, u_mix, u_inv, _u64(seed), None, gripper_bounds, act_out, idx_out)
+    _call("hulc_mix_sample", _c.byref(d), y, u_mix, u_inv, seed, None, gripper_bounds, act_out, idx_out)
 
 
 def window_index(starts, sizes, B, S, out):
@@ -1444,7 +1379,7 @@ def window_index(starts, sizes, B, S, out):
     for t in (starts, sizes, out):
         if t.dtype != torch.int32 or not t.is_contiguous():
             raise TypeError("window_index: starts / sizes / out are contiguous int32 tensors")
-    _call("hulc_window_index", starts, sizes, _i(B), _i(S), out)
+    _call("hulc_window_index", starts, sizes, B, S, out)
     return out
 
 
@@ -1454,7 +1389,7 @@ def window_rows(store, starts, sizes, B, S, out, zero_cols=(0, 0)):
     if store.dtype != torch.float32 or out.dtype != torch.float32 or starts.dtype != torch.int32 or sizes.dtype != torch.int32:
         raise TypeError("window_rows: fp32 store / out, int32 starts / sizes")
     _require_contiguous(store=store, out=out, starts=starts, sizes=sizes)
-    _call("hulc_window_rows", store, _i(store.shape[-1]), starts, sizes, _i(B), _i(S), _i(zero_cols[0]), _i(zero_cols[1]), out)
+    _call("hulc_window_rows", store, store.shape[-1], starts, sizes, B, S, zero_cols[0], zero_cols[1], out)
     return out
 
 
@@ -1476,18 +1411,18 @@ def adam_step(p, g, m, v, shadow, n, lr, beta1, beta2, eps, weight_decay, step, 
         has_lo = lo is not None and bool(lo_ranges)
         flat = [int(x) for r in lo_ranges for x in r] if has_lo else [0, 0]
         arr = (_c.c_long * len(flat))(*flat)
-        _call("hulc_adam_step_amp", p, g, m, v, shadow, _l(n), _f(lr), _f(beta1), _f(beta2), _f(eps), _f(weight_decay), _i(step),
-              step_state_dev, _f(grad_scale), fault_word(p.device), lo if has_lo else None, arr if has_lo else None,
-              _i(len(lo_ranges) if has_lo else 0), loss_scale_dev, found_inf_dev, nbytes=nbytes)
+        _call("hulc_adam_step_amp", p, g, m, v, shadow, n, lr, beta1, beta2, eps, weight_decay, step,
+              step_state_dev, grad_scale, fault_word(p.device), lo if has_lo else None, arr if has_lo else None,
+              len(lo_ranges) if has_lo else 0, loss_scale_dev, found_inf_dev, nbytes=nbytes)
         return
     if lo is None or not lo_ranges:
-        _call("hulc_adam_step", p, g, m, v, shadow, _l(n), _f(lr), _f(beta1), _f(beta2), _f(eps), _f(weight_decay), _i(step),
-              step_state_dev, _f(grad_scale), fault_word(p.device), nbytes=nbytes)
+        _call("hulc_adam_step", p, g, m, v, shadow, n, lr, beta1, beta2, eps, weight_decay, step,
+              step_state_dev, grad_scale, fault_word(p.device), nbytes=nbytes)
         return
     flat = [int(x) for r in lo_ranges for x in r]
     arr = (_c.c_long * len(flat))(*flat)
-    _call("hulc_adam_step_lo", p, g, m, v, shadow, _l(n), _f(lr), _f(beta1), _f(beta2), _f(eps), _f(weight_decay), _i(step),
-          step_state_dev, _f(grad_scale), fault_word(p.device), lo, arr, _i(len(lo_ranges)), nbytes=nbytes)
+    _call("hulc_adam_step_lo", p, g, m, v, shadow, n, lr, beta1, beta2, eps, weight_decay, step,
+          step_state_dev, grad_scale, fault_word(p.device), lo, arr, len(lo_ranges), nbytes=nbytes)
 
 
 def step_count_advance_if(state, found_inf_dev=None) -> None:
@@ -1497,28 +1432,28 @@ def step_count_advance_if(state, found_inf_dev=None) -> None:
 
 def derive_copies(bf16, bf16_t, tiles, p32, conv_dst, conv_table):
     """the transposed tiles (bf16 -> bf16_t) and the conv repacks (p32 -> conv_dst) of a step as one launch; either table may be None"""
-    _call("hulc_derive_copies", bf16, bf16_t, tiles, _i(0 if tiles is None else tiles.shape[0]), p32, conv_dst, conv_table,
-          _i(0 if conv_table is None else conv_table.shape[0]))
+    _call("hulc_derive_copies", bf16, bf16_t, tiles, 0 if tiles is None else tiles.shape[0], p32, conv_dst, conv_table,
+          0 if conv_table is None else conv_table.shape[0])
 
 
 def gather_chunks2(a0, a1, ad, ai, b0, bd, bi):
     """two 8-byte-chunk gathers as one launch: (a0 | a1 by bit 31 of ai) -> ad, b0 -> bd; either index tensor may be None"""
-    _call("hulc_gather_chunks2", a0, a1, ad, ai, _l(0 if ai is None else ai.numel()), b0, bd, bi, _l(0 if bi is None else bi.numel()))
+    _call("hulc_gather_chunks2", a0, a1, ad, ai, 0 if ai is None else ai.numel(), b0, bd, bi, 0 if bi is None else bi.numel())
 
 
 def cast_f32_to_bf16(src, dst, n):
-    _call("hulc_cast_f32_to_bf16", src, dst, _l(n))
+    _call("hulc_cast_f32_to_bf16", src, dst, n)
 
 
 def cast_bf16_to_f32(src, dst, n):
-    _call("hulc_cast_bf16_to_f32", src, dst, _l(n))
+    _call("hulc_cast_bf16_to_f32", src, dst, n)
 
 
 def sum_chunks(src, W, chunk, dst):
     """dst (chunk,) = sum over the W rank chunks of src (W * chunk,), rank order, fp32 accumulation (direct gradient all-reduce)"""
     if src.dtype != dst.dtype:
         raise TypeError("sum_chunks: src and dst share a dtype")
-    _call("hulc_sum_chunks", src, _i(_dt(src)), _i(W), _l(chunk), dst)
+    _call("hulc_sum_chunks", src, _dt(src), W, chunk, dst)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1589,11 +1524,9 @@ def gridconv3x3(x: Grid, wt, Cout, want_stats=False, y: "Grid" = None, out0=None
         raise _L.HulcKernelError("gridconv3x3: weights are bf16 [Cout][9 * Cin]")
     if out0 is None and y is None:
         y = Grid(x.N, x.H, x.W, Cout, x.rows.device)
-    lib = _L.load()
-    lib.hulc_gridconv_stats_bytes.restype = _c.c_long
-    stats = _ws(lib.hulc_gridconv_stats_bytes(_i(x.N), _i(x.H), _i(x.W), _i(Cout)), x.rows.device) if want_stats else None
-    _call("hulc_gridconv3x3", x.t, _l(x.C), wt, (y.t if y is not None else None), _l(y.C if y is not None else 0), _i(x.N), _i(x.H), _i(x.W), _i(Cin), _i(Cout),
-          _i(flip), stats, out0, bias0, key=("gridconv3x3", x.N, x.H, x.W, Cin, Cout), flops=2.0 * x.R * 9 * Cin * Cout,
+    stats = _ws(_L.load().hulc_gridconv_stats_bytes(x.N, x.H, x.W, Cout), x.rows.device) if want_stats else None
+    _call("hulc_gridconv3x3", x.t, x.C, wt, (y.t if y is not None else None), y.C if y is not None else 0, x.N, x.H, x.W, Cin, Cout,
+          flip, stats, out0, bias0, key=("gridconv3x3", x.N, x.H, x.W, Cin, Cout), flops=2.0 * x.R * 9 * Cin * Cout,
           nbytes=float(x.R) * (x.C + Cout) * 2 + Cout * 9 * Cin * 2)
     return y, stats
 
@@ -1606,8 +1539,8 @@ def gridconv3x3_fused(x: Grid, wt, Cout, bias=None, add: "Grid" = None, relu=Fal
     if add is not None and (add.C != Cout or (add.N, add.H, add.W) != (x.N, x.H, x.W)):
         raise _L.HulcKernelError("gridconv3x3_fused: the residual branch must be a grid tensor shaped like the output")
     y = Grid(x.N, x.H, x.W, Cout, x.rows.device)
-    _call("hulc_gridconv3x3_fused", x.t, _l(x.C), wt, y.t, _l(Cout), _i(x.N), _i(x.H), _i(x.W), _i(x.C), _i(Cout), bias,
-          (add.t if add is not None else None), _l(add.C if add is not None else 0), _i(1 if relu else 0),
+    _call("hulc_gridconv3x3_fused", x.t, x.C, wt, y.t, Cout, x.N, x.H, x.W, x.C, Cout, bias,
+          (add.t if add is not None else None), add.C if add is not None else 0, 1 if relu else 0,
           key=("gridconv3x3", x.N, x.H, x.W, x.C, Cout), flops=2.0 * x.R * 9 * x.C * Cout, nbytes=float(x.R) * (x.C + Cout * (2 if add is not None else 1)) * 2 + Cout * 9 * x.C * 2)
     return y
 
@@ -1617,7 +1550,7 @@ def grid_from_nhwc(x) -> Grid:
     _require_contiguous(x=x)
     N, H, W, C = x.shape
     g = Grid(N, H, W, C, x.device)
-    _call("hulc_grid_from_nhwc", x, _i(N), _i(H), _i(W), _i(C), g.t, _l(C))
+    _call("hulc_grid_from_nhwc", x, N, H, W, C, g.t, C)
     return g
 
 
@@ -1637,24 +1570,22 @@ def grid_bn_finalize(stats, N, H, W, C, gamma, beta, run_mean=None, run_var=None
     bn = torch.empty(4 + 64, C, dtype=torch.float32, device=stats.device)          # the table, then the row groups' intermediate sums
     nb = (N * (H + 2) * (W + 2) + 127) // 128
     ctr = _bn_counters(stats.device)
-    _call("hulc_grid_bn_finalize", stats, _i(nb), _i(C), _l(N * H * W), gamma, beta, _f(eps), _f(momentum), bn, run_mean, run_var, bn[4:], ctr)
+    _call("hulc_grid_bn_finalize", stats, nb, C, N * H * W, gamma, beta, eps, momentum, bn, run_mean, run_var, bn[4:], ctr)
     return bn[:4]
 
 
 def grid_bn_relu_fwd(y: Grid, bn) -> Grid:
     out = Grid(y.N, y.H, y.W, y.C, y.rows.device)
-    _call("hulc_grid_bn_relu_fwd", y.t, _l(y.C), bn, _i(y.N), _i(y.H), _i(y.W), _i(y.C), out.t, _l(out.C), key=("grid_bn_relu_fwd", y.N, y.H, y.W, y.C),
+    _call("hulc_grid_bn_relu_fwd", y.t, y.C, bn, y.N, y.H, y.W, y.C, out.t, out.C, key=("grid_bn_relu_fwd", y.N, y.H, y.W, y.C),
           nbytes=float(y.R) * y.C * 4)
     return out
 
 
 def grid_bn_relu_bwd(dout: Grid, out: Grid, y: Grid, bn, dgamma, dbeta, accumulate=False) -> Grid:
     dz = Grid(y.N, y.H, y.W, y.C, y.rows.device)
-    lib = _L.load()
-    lib.hulc_grid_bn_bwd_workspace.restype = _c.c_long
-    ws = _ws(lib.hulc_grid_bn_bwd_workspace(_i(y.N), _i(y.H), _i(y.W), _i(y.C)), y.rows.device)
-    _call("hulc_grid_bn_relu_bwd", dout.t, _l(dout.C), out.t, _l(out.C), y.t, _l(y.C), bn, _i(y.N), _i(y.H), _i(y.W), _i(y.C), dz.t, _l(dz.C), dgamma, dbeta,
-          _i(accumulate), ws, _bn_counters(y.rows.device), key=("grid_bn_relu_bwd", y.N, y.H, y.W, y.C),      # (one shape per table row: ten layers of
+    ws = _ws(_L.load().hulc_grid_bn_bwd_workspace(y.N, y.H, y.W, y.C), y.rows.device)
+    _call("hulc_grid_bn_relu_bwd", dout.t, dout.C, out.t, out.C, y.t, y.C, bn, y.N, y.H, y.W, y.C, dz.t, dz.C, dgamma, dbeta,
+          accumulate, ws, _bn_counters(y.rows.device), key=("grid_bn_relu_bwd", y.N, y.H, y.W, y.C),      # (one shape per table row: ten layers of
           nbytes=float(y.R) * y.C * 14)                                                                         # different sizes must not be averaged)
     return dz
 
@@ -1662,8 +1593,8 @@ def grid_bn_relu_bwd(dout: Grid, out: Grid, y: Grid, bn, dgamma, dbeta, accumula
 def grid_upcat_fwd(x, xs, g, skip, ss, N, Ho, Wo, s, Cx, Cs) -> Grid:
     """x / skip: (tensor at pixel (0,0,0), stride_n, stride_y, stride_x) strided bf16 maps; g (N, Cx) fp32 or None"""
     out = Grid(N, Ho, Wo, Cx + Cs, x.device)
-    _call("hulc_grid_upcat_fwd", x, _l(xs[0]), _l(xs[1]), _l(xs[2]), g, skip, _l(ss[0] if skip is not None else 0), _l(ss[1] if skip is not None else 0),
-          _l(ss[2] if skip is not None else 0), _i(N), _i(Ho), _i(Wo), _i(s), _i(Cx), _i(Cs), out.t, key=("grid_upcat_fwd", N, Ho, Wo, Cx + Cs),
+    _call("hulc_grid_upcat_fwd", x, xs[0], xs[1], xs[2], g, skip, ss[0] if skip is not None else 0, ss[1] if skip is not None else 0,
+          ss[2] if skip is not None else 0, N, Ho, Wo, s, Cx, Cs, out.t, key=("grid_upcat_fwd", N, Ho, Wo, Cx + Cs),
           nbytes=float(out.R) * out.C * 4)
     return out
 
@@ -1671,34 +1602,34 @@ def grid_upcat_fwd(x, xs, g, skip, ss, N, Ho, Wo, s, Cx, Cs) -> Grid:
 def grid_upcat_bwd(dX: Grid, x, xs, g, N, Hi, Wi, s, Cx, want_dsmall=True, want_dg=True):
     dsmall = Grid(N, Hi, Wi, Cx, dX.rows.device) if want_dsmall else None
     dg = torch.empty(N, Cx, dtype=torch.float32, device=dX.rows.device) if want_dg else None
-    _call("hulc_grid_upcat_bwd", dX.t, _l(dX.C), x, _l(xs[0]), _l(xs[1]), _l(xs[2]), g, _i(N), _i(Hi), _i(Wi), _i(s), _i(Cx),
-          (dsmall.t if dsmall is not None else None), dg, _i(0), key=("grid_upcat_bwd", N, Hi, Wi, Cx), nbytes=float(dX.R) * Cx * 2)
+    _call("hulc_grid_upcat_bwd", dX.t, dX.C, x, xs[0], xs[1], xs[2], g, N, Hi, Wi, s, Cx,
+          (dsmall.t if dsmall is not None else None), dg, 0, key=("grid_upcat_bwd", N, Hi, Wi, Cx), nbytes=float(dX.R) * Cx * 2)
     return dsmall, dg
 
 
 def pixel_ce_fwd(logit0, p0, N, H, W):
     lse = torch.empty(N, dtype=torch.float32, device=logit0.device)
     picked = torch.empty(N, dtype=torch.float32, device=logit0.device)
-    _call("hulc_pixel_ce_fwd", logit0, p0, _i(N), _i(H), _i(W), lse, picked)
+    _call("hulc_pixel_ce_fwd", logit0, p0, N, H, W, lse, picked)
     return lse, picked
 
 
 def head_conv_fwd(x: Grid, w, bias):
     """the one-channel head on the grid: -> logit0 fp32 [R] (bias added on the pixels, zero on the border)"""
     out0 = torch.empty(x.R, dtype=torch.float32, device=x.rows.device)
-    _call("hulc_head_conv_fwd", x.t, _l(x.C), w, bias, _i(x.N), _i(x.H), _i(x.W), _i(x.C), out0, flops=2.0 * x.R * 9 * x.C, nbytes=float(x.R) * (x.C * 2 + 4))
+    _call("hulc_head_conv_fwd", x.t, x.C, w, bias, x.N, x.H, x.W, x.C, out0, flops=2.0 * x.R * 9 * x.C, nbytes=float(x.R) * (x.C * 2 + 4))
     return out0
 
 
 def pixel_ce_bwd_rows(logit0, p0, lse, upstream, N, H, W):
     g = torch.empty(N * (H + 2) * (W + 2), dtype=torch.float32, device=logit0.device)
-    _call("hulc_pixel_ce_bwd_rows", logit0, p0, lse, upstream, _i(N), _i(H), _i(W), g)
+    _call("hulc_pixel_ce_bwd_rows", logit0, p0, lse, upstream, N, H, W, g)
     return g
 
 
 def head_conv_dgrad(g, w, N, H, W, C) -> Grid:
     dx = Grid(N, H, W, C, g.device)
-    _call("hulc_head_conv_dgrad", g, w, _i(N), _i(H), _i(W), _i(C), dx.t, _l(C), flops=2.0 * dx.R * 9 * C, nbytes=float(dx.R) * (C * 2 + 4))
+    _call("hulc_head_conv_dgrad", g, w, N, H, W, C, dx.t, C, flops=2.0 * dx.R * 9 * C, nbytes=float(dx.R) * (C * 2 + 4))
     return dx
 
 
@@ -1706,16 +1637,9 @@ _head_ws = {}
 
 
 def head_conv_wgrad(x: Grid, g, dw, accumulate=False):
-    lib = _L.load()
-    lib.hulc_head_conv_wgrad_workspace.restype = _c.c_long
-    need = int(lib.hulc_head_conv_wgrad_workspace(_i(x.N), _i(x.H), _i(x.W), _i(x.C)))
-    key = (x.rows.device, _stream())
-    ws = _head_ws.get(key)
-    if ws is None or ws.numel() * 4 < need:
-        ws = torch.empty(need // 4 + 16, dtype=torch.float32, device=x.rows.device)
-        if not torch.cuda.is_current_stream_capturing():
-            _head_ws[key] = ws
-    _call("hulc_head_conv_wgrad", x.t, _l(x.C), g, _i(x.N), _i(x.H), _i(x.W), _i(x.C), dw, _i(1 if accumulate else 0), ws, flops=2.0 * x.R * 9 * x.C,
+    need = _L.load().hulc_head_conv_wgrad_workspace(x.N, x.H, x.W, x.C)
+    ws = _cached_ws(_head_ws, (x.rows.device, _stream()), need, need // 4 + 16, torch.empty)
+    _call("hulc_head_conv_wgrad", x.t, x.C, g, x.N, x.H, x.W, x.C, dw, 1 if accumulate else 0, ws, flops=2.0 * x.R * 9 * x.C,
           nbytes=float(x.R) * (x.C * 2 + 4))
 
 
@@ -1726,16 +1650,16 @@ def depth_nll_fwd(x, w_mu, b_mu, w_sigma, b_sigma, target):
     sigma = torch.empty(B, 1, dtype=torch.float32, device=x.device)
     ls = torch.empty(B, dtype=torch.float32, device=x.device)
     loss = torch.empty((), dtype=torch.float32, device=x.device)
-    _call("hulc_depth_nll_fwd", x, _i(B), _i(D), w_mu, b_mu, w_sigma, b_sigma, target, mu, sigma, ls, loss)
+    _call("hulc_depth_nll_fwd", x, B, D, w_mu, b_mu, w_sigma, b_sigma, target, mu, sigma, ls, loss)
     return mu, sigma, ls, loss
 
 
 def depth_nll_bwd(x, w_mu, w_sigma, mu, sigma, ls, target, gout, dx, dw_mu, db_mu, dw_sigma, db_sigma, accumulate_mask=0):
     B, D = x.shape
-    _call("hulc_depth_nll_bwd", x, _i(B), _i(D), w_mu, w_sigma, mu, sigma, ls, target, gout, dx, dw_mu, db_mu, dw_sigma, db_sigma, _i(accumulate_mask))
+    _call("hulc_depth_nll_bwd", x, B, D, w_mu, w_sigma, mu, sigma, ls, target, gout, dx, dw_mu, db_mu, dw_sigma, db_sigma, accumulate_mask)
 
 
 def pixel_ce_bwd(logit0, p0, lse, upstream, N, H, W, C) -> Grid:
     dz = Grid(N, H, W, C, logit0.device)
-    _call("hulc_pixel_ce_bwd", logit0, p0, lse, upstream, _i(N), _i(H), _i(W), _i(C), dz.t)
+    _call("hulc_pixel_ce_bwd", logit0, p0, lse, upstream, N, H, W, C, dz.t)
     return dz

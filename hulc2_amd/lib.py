@@ -6,6 +6,7 @@ from here).
 """
 import ctypes
 import os
+import re
 from pathlib import Path
 
 import torch  # noqa: F401  -- must be imported BEFORE the CDLL below: torch ships its own libamdhip64; loading ours first
@@ -45,6 +46,39 @@ def lib_path() -> Path:
     return _LIB_PATH
 
 
+_HEADER = Path(__file__).resolve().parent.parent / "include" / "hulc2_amd.h"
+_SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "unsigned long long": ctypes.c_ulonglong}
+_RETURNS = {"int": ctypes.c_int, "long": ctypes.c_long, "const char*": ctypes.c_char_p}
+
+
+def parse_prototypes(text: str) -> dict:
+    """{name: (restype, [argtypes])} of every function the header text declares.  Scalars by value keep their C type, anything with a `*` is
+    c_void_p (takes an address, None, byref(struct) or a ctypes array).  Strict: a statement that is not a recognised prototype raises."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    text = re.sub(r"typedef\s+struct\b[^{;]*\{[^}]*\}\s*\w+\s*;", " ", text)
+    text = re.sub(r'extern\s+"C"\s*\{', " ", text)
+    protos = {}
+    for stmt in text.split(";"):
+        stmt = " ".join(stmt.split())
+        if stmt in ("", "}"):                     # (the brace closes extern "C")
+            continue
+        m = re.fullmatch(r"(const char ?\*|int|long) ?(hulc_[a-z0-9_]+) ?\((.*)\)", stmt)
+        if not m:
+            raise HulcKernelError(f"include/hulc2_amd.h: cannot bind `{stmt}`")
+        argtypes = []
+        for par in ([] if m.group(3).strip() == "void" else m.group(3).split(",")):
+            if "*" in par:
+                argtypes.append(ctypes.c_void_p)
+                continue
+            base = re.fullmatch(r"\s*(?:const )?([a-z ]+?) [A-Za-z_]\w*\s*", par)
+            if not base or base.group(1) not in _SCALARS:
+                raise HulcKernelError(f"include/hulc2_amd.h: cannot bind parameter `{par.strip()}` of {m.group(2)}")
+            argtypes.append(_SCALARS[base.group(1)])
+        protos[m.group(2)] = (_RETURNS[m.group(1).replace(" *", "*")], argtypes)
+    return protos
+
+
 def load():
     """Load the shared library once; raise loudly when it has not been built."""
     global _lib
@@ -56,8 +90,14 @@ def load():
             "(hipcc --offload-arch=gfx950). hulc2_amd has no non-HIP fallback."
         )
     lib = ctypes.CDLL(os.fspath(_LIB_PATH))
-    lib.hulc_last_error.restype = ctypes.c_char_p
-    lib.hulc_abi_version.restype = ctypes.c_int
+    if not _HEADER.exists():
+        raise HulcKernelError(f"{_HEADER} is missing: the binding takes every prototype from it")
+    for name, (restype, argtypes) in parse_prototypes(_HEADER.read_text()).items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise HulcKernelError(f"{_LIB_PATH} does not export {name}, which {_HEADER.name} declares: rebuild the library") from None
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 

@@ -85,6 +85,75 @@ def test_abi_library_exports_every_declared_symbol():
     assert so.hulc_abi_version() == 7
 
 
+def _declared_prototypes():
+    """{name: (return text, parameter text)} of the header's functions, read without the loader's parser"""
+    header = re.sub(r"/\*.*?\*/|//[^\n]*", " ", (ROOT / "include" / "hulc2_amd.h").read_text(), flags=re.S)
+    return {m.group(2): (" ".join(m.group(1).split()), " ".join(m.group(3).split()))
+            for m in re.finditer(r"([A-Za-z_][A-Za-z_ ]*\*?)\s*\b(hulc_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", header)}
+
+
+def test_binding_declares_every_prototype_of_the_header():
+    """after lib.load() every function the header declares carries argtypes (one per declared parameter, counted here by the commas) and
+    the restype of its declaration; a handful of signatures, one per scalar kind at least, written out in full"""
+    from hulc2_amd import build, lib
+
+    build.build(verbose=False)
+    so = lib.load()
+    header = (ROOT / "include" / "hulc2_amd.h").read_text()
+    names = sorted(set(re.findall(r"\b(hulc_[a-z0-9_]+)\s*\(", header)))
+    decl = _declared_prototypes()
+    assert sorted(decl) == names and len(names) >= 100
+    rets = {"int": ctypes.c_int, "long": ctypes.c_long, "const char*": ctypes.c_char_p}
+    for n in names:
+        fn, (ret, params) = getattr(so, n), decl[n]
+        assert fn.argtypes is not None, n
+        assert len(fn.argtypes) == (0 if params == "void" else params.count(",") + 1), (n, params, fn.argtypes)
+        assert fn.restype is rets[ret], (n, ret, fn.restype)
+    i, l, f, u, p = ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_ulonglong, ctypes.c_void_p
+    by_hand = {
+        "hulc_colsum": (i, [p, i, l, i, l, p, i, p, p]),
+        "hulc_layernorm_fwd": (i, [p, p, f, u, p, p, p, f, i, i, p, p, p, p, p]),
+        "hulc_rnn_wavefront_mirror_offset": (l, []),
+        "hulc_rnn_wavefront_mirror_t_offset": (l, [i, i, i]),
+        "hulc_last_error": (ctypes.c_char_p, []),
+        "hulc_mlp_chain_workspace": (l, [p]),
+        "hulc_wgrad_group": (i, [p, i, p, l, p]),
+        "hulc_adam_step": (i, [p, p, p, p, p, l, f, f, f, f, f, i, p, f, p, p]),
+    }
+    for n, (ret, args) in by_hand.items():
+        fn = getattr(so, n)
+        assert fn.restype is ret and list(fn.argtypes) == args, (n, fn.restype, fn.argtypes)
+
+
+def test_binding_converts_plain_python_values_like_explicit_casts():
+    """host-only entry points through the binding, with plain Python / numpy values, against explicitly cast calls on a fresh CDLL; a float
+    where the header says int is an error, not a truncation; the parser refuses what it cannot classify"""
+    import numpy
+    from hulc2_amd import build, lib
+
+    build.build(verbose=False)
+    so, raw = lib.load(), ctypes.CDLL(str(lib.lib_path()))
+    assert raw.hulc_colsum_workspace.argtypes is None
+    for fn in (raw.hulc_colsum_workspace, raw.hulc_rnn_wavefront_mirror_t_offset):
+        fn.restype = ctypes.c_long
+    want = raw.hulc_colsum_workspace(ctypes.c_long(2 ** 33), ctypes.c_int(8))
+    assert so.hulc_colsum_workspace(2 ** 33, 8) == want != raw.hulc_colsum_workspace(ctypes.c_long(0), ctypes.c_int(8))   # (2^33 cut to an int is 0)
+    assert so.hulc_rnn_wavefront_mirror_t_offset(32, 64, 2048) == raw.hulc_rnn_wavefront_mirror_t_offset(
+        ctypes.c_int(32), ctypes.c_int(64), ctypes.c_int(2048)) > 0
+    assert so.hulc_r3m_packed_width(numpy.int64(200)) == raw.hulc_r3m_packed_width(ctypes.c_int(200)) > 0
+    assert so.hulc_r3m_packed_width(True) == raw.hulc_r3m_packed_width(ctypes.c_int(1))
+    with pytest.raises(ctypes.ArgumentError):
+        so.hulc_r3m_packed_width(200.0)
+    with pytest.raises(TypeError):
+        so.hulc_colsum_workspace(2 ** 33)                                            # (a forgotten argument is an error too)
+    with pytest.raises(lib.HulcKernelError):
+        lib.parse_prototypes("double hulc_x(double a);")
+    with pytest.raises(lib.HulcKernelError):
+        lib.parse_prototypes("int hulc_x(double a);")
+    assert lib.parse_prototypes("/* c */ long hulc_x(const int* a, long n,\n unsigned long long s, float f); int hulc_y(void);") == {
+        "hulc_x": (ctypes.c_long, [ctypes.c_void_p, ctypes.c_long, ctypes.c_ulonglong, ctypes.c_float]), "hulc_y": (ctypes.c_int, [])}
+
+
 def test_product_never_imports_oracle():
     for p in (ROOT / "hulc2_amd").rglob("*.py"):
         txt = p.read_text()
@@ -133,7 +202,8 @@ _C2CT = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "u
 
 
 def _parse_struct(text: str, name: str):
-    """-> [(field, ctypes type)] of `typedef struct name { ... } name;` — handles `const T *a, *b;`, `T a, b;`, `T* a; long b, c;` on one line"""
+    """-> [(field, ctypes type)] of `typedef struct name { ... } name;` — handles `const T *a, *b;`, `T a, b;`, `T* a; long b, c;` on one line;
+    an array of a struct comes back as (field, (element struct's C name, length))"""
     end = re.search(r"\}\s*" + name + r"\s*;", text)
     assert end, f"struct {name} not found"
     start = text.rfind("typedef struct", 0, end.start())
@@ -142,6 +212,15 @@ def _parse_struct(text: str, name: str):
     for decl in body.split(";"):
         decl = decl.strip()
         if not decl:
+            continue
+        arr = re.fullmatch(r"(hulc_\w+)\s+(\w+)\[(\w+)\]", decl)          # an array of a struct: `hulc_x name[LEN]`, LEN a number or a #define
+        if arr:
+            n = arr.group(3)
+            if not n.isdigit():
+                d = re.search(r"^#define\s+" + n + r"\s+(\d+)\s*$", text, re.M)
+                assert d, f"{n} is not #defined as a number"
+                n = d.group(1)
+            fields.append((arr.group(2), (arr.group(1), int(n))))
             continue
         m2 = re.match(r"(?:const\s+)?(unsigned long long|void|float|int|long|unsigned)\s*(.*)$", decl, re.S)
         assert m2, decl
@@ -153,9 +232,13 @@ def _parse_struct(text: str, name: str):
     return fields
 
 
+_MIRRORS = {"hulc_txl_block_layer": "TxlBlockLayer", "hulc_mlp_chain_layer": "MlpChainLayer"}
+
+
 @pytest.mark.parametrize("cname,pyname", [("hulc_gemm_desc", "GemmDesc"), ("hulc_conv_desc", "ConvDesc"), ("hulc_rnn_wave_desc", "RnnWaveDesc"),
                                           ("hulc_mix_desc", "MixDesc"), ("hulc_txl_attn_desc", "TxlAttnDesc"), ("hulc_wgrad_item", "WgradItem"),
-                                          ("hulc_mlp_chain_layer", "MlpChainLayer")])
+                                          ("hulc_mlp_chain_layer", "MlpChainLayer"), ("hulc_txl_block_layer", "TxlBlockLayer"),
+                                          ("hulc_txl_block_desc", "TxlBlockDesc"), ("hulc_mlp_chain_desc", "MlpChainDesc")])
 def test_ctypes_structures_mirror_the_header(cname, pyname):
     """field count, order, names and C types of every descriptor struct == its ctypes.Structure in hulc2_amd/lib.py: a field added on one
     side only makes the kernel read past the caller's struct (the INTEGRATION.md stub was 3 fields short)"""
@@ -165,7 +248,11 @@ def test_ctypes_structures_mirror_the_header(cname, pyname):
     got = [(n, t) for n, t in getattr(lib, pyname)._fields_]
     assert [n for n, _ in got] == [n for n, _ in want], (cname, [n for n, _ in got], [n for n, _ in want])
     for (n, tg), (_, tw) in zip(got, want):
-        assert tg is tw, (cname, n, tg, tw)
+        if isinstance(tw, tuple):                 # array of a struct: element mirror and length
+            elem = getattr(lib, _MIRRORS[tw[0]])
+            assert issubclass(tg, ctypes.Array) and tg._type_ is elem and tg._length_ == tw[1], (cname, n, tg, tw)
+        else:
+            assert tg is tw, (cname, n, tg, tw)
 
 
 def test_integration_doc_binding_lists_every_gemm_field():
@@ -229,7 +316,6 @@ def test_wgrad_group_workspace_counts_the_nine_tap_slabs():
     import ctypes
     from hulc2_amd import lib as L
     lib = L.load()
-    lib.hulc_wgrad_group_workspace.restype = ctypes.c_long
     buf = (ctypes.c_char * 64)()                                   # any 16-byte aligned, non-null address: nothing is dereferenced
     base = ctypes.addressof(buf) // 16 * 16 + 16
 
