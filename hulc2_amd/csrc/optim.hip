@@ -33,7 +33,8 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
                                                    float b2, float eps, float wd, float bc1, float bc2_sqrt, float gscale,
                                                    const unsigned long long* __restrict__ step_state, const int* __restrict__ skip_flag,
                                                    uint16_t* __restrict__ lo, LoRanges lr_, float omb1, float omb2, double b1d, double b2d,
-                                                   const float* __restrict__ loss_scale, const float* __restrict__ found_inf) {
+                                                   const float* __restrict__ loss_scale, const float* __restrict__ found_inf,
+                                                   const float* __restrict__ lr_dev) {
     // omb1 / omb2 = 1 - beta as torch forms them: in DOUBLE from the decimal the caller meant (0.999), then rounded to fp32 — 1.f - 0.999f is
     // 4.7e-5 (relative) away from that, and exp_avg_sq with it; the bias corrections likewise come from double powers (torch: Python floats)
     if (skip_flag && *skip_flag) return;    // an upstream kernel reported a fault (barrier timeout): keep the weights, the host raises
@@ -41,6 +42,9 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     // the gradients are still multiplied by the loss scale S: unscaled here by 1 / S formed as torch's unscale_ forms it (double reciprocal)
     if (found_inf && *found_inf != 0.f) return;
     if (loss_scale) gscale *= (float)(1.0 / (double)*loss_scale);
+    // the learning rate as a device scalar (hulc_adam_step_sched): a captured launch follows a schedule the host writes between replays.  One
+    // uniform 4-byte read per thread; the arithmetic below is the scalar argument's, so lr_dev == (float)lr gives the same bits
+    if (lr_dev) lr = *lr_dev;
     if (step_state) {                       // bias corrections from the device-resident step count (graph replay)
         const double t = (double)step_state[1];
         bc1 = (float)(1.0 - pow(b1d, t));
@@ -317,10 +321,11 @@ extern "C" int hulc_step_count_advance_if(unsigned long long* state, const float
     return hulc_check_launch("hulc_step_count_advance_if");
 }
 
-// see include/hulc2_amd.h
-extern "C" int hulc_adam_step_amp(float* p, const float* g, float* m, float* v, void* bf16_shadow, long n, float lr, float beta1, float beta2,
-                                  float eps, float weight_decay, int step, const unsigned long long* step_state, float grad_scale, const int* skip_flag,
-                                  void* lo_shadow, const long* lo_ranges, int n_ranges, const float* loss_scale, const float* found_inf, void* stream) {
+// every hulc_adam_step* entry point ends here; lr_dev == nullptr is the scalar-lr path
+static int adam_launch(float* p, const float* g, float* m, float* v, void* bf16_shadow, long n, float lr, float beta1, float beta2,
+                       float eps, float weight_decay, int step, const unsigned long long* step_state, float grad_scale, const int* skip_flag,
+                       void* lo_shadow, const long* lo_ranges, int n_ranges, const float* loss_scale, const float* found_inf, const float* lr_dev,
+                       void* stream) {
     if (!p || !g || !m || !v) return hulc_fail(-1, "hulc_adam_step: null pointer");
     LoRanges lr_;
     lr_.n = 0;
@@ -350,8 +355,27 @@ extern "C" int hulc_adam_step_amp(float* p, const float* g, float* m, float* v, 
     long blocks = (n / 4 + 255) / 256; if (blocks > cap) blocks = cap; if (blocks < 1) blocks = 1;
     adam_kernel<7><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(p, g, m, v, (uint16_t*)bf16_shadow, n, lr, beta1, beta2, eps, weight_decay,
                                                                     bc1, bc2s, grad_scale, step_state, skip_flag, (uint16_t*)lo_shadow, lr_,
-                                                                    (float)(1.0 - b1d), (float)(1.0 - b2d), b1d, b2d, loss_scale, found_inf);
+                                                                    (float)(1.0 - b1d), (float)(1.0 - b2d), b1d, b2d, loss_scale, found_inf, lr_dev);
     return hulc_check_launch("hulc_adam_step");
+}
+
+// see include/hulc2_amd.h
+extern "C" int hulc_adam_step_amp(float* p, const float* g, float* m, float* v, void* bf16_shadow, long n, float lr, float beta1, float beta2,
+                                  float eps, float weight_decay, int step, const unsigned long long* step_state, float grad_scale, const int* skip_flag,
+                                  void* lo_shadow, const long* lo_ranges, int n_ranges, const float* loss_scale, const float* found_inf, void* stream) {
+    return adam_launch(p, g, m, v, bf16_shadow, n, lr, beta1, beta2, eps, weight_decay, step, step_state, grad_scale, skip_flag, lo_shadow, lo_ranges,
+                       n_ranges, loss_scale, found_inf, nullptr, stream);
+}
+
+// see include/hulc2_amd.h
+extern "C" int hulc_adam_step_sched(float* p, const float* g, float* m, float* v, void* bf16_shadow, long n, float lr, float beta1, float beta2,
+                                    float eps, float weight_decay, int step, const unsigned long long* step_state, float grad_scale,
+                                    const int* skip_flag, void* lo_shadow, const long* lo_ranges, int n_ranges, const float* loss_scale,
+                                    const float* found_inf, const float* lr_dev, void* stream) {
+    if (!lr_dev) return hulc_fail(-1, "hulc_adam_step_sched: null lr_dev");
+    if ((uintptr_t)lr_dev % 4) return hulc_fail(-4, "hulc_adam_step_sched: lr_dev must be 4-byte aligned");
+    return adam_launch(p, g, m, v, bf16_shadow, n, lr, beta1, beta2, eps, weight_decay, step, step_state, grad_scale, skip_flag, lo_shadow, lo_ranges,
+                       n_ranges, loss_scale, found_inf, lr_dev, stream);
 }
 
 extern "C" int hulc_cast_f32_to_bf16(const float* src, void* dst, long n, void* stream) {

@@ -1394,26 +1394,32 @@ def window_rows(store, starts, sizes, B, S, out, zero_cols=(0, 0)):
 
 
 def adam_step(p, g, m, v, shadow, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, step_state_dev=None, lo=None, lo_ranges=(),
-              loss_scale_dev=None, found_inf_dev=None):
+              loss_scale_dev=None, found_inf_dev=None, lr_dev=None):
     """step_state_dev: device {rng, step} words (see step_state); when given, the step count is read on device.  The update is skipped
     on the device while the fault word is set (a barrier kernel timed out upstream) — check_faults() then raises on the host.
     lo (bf16 arena like shadow) + lo_ranges (<= 8 (begin, end) element ranges): the rounding remainders w - bf16(w) of the updated weights
-    inside the ranges are written by the same pass (hulc_adam_step_lo)."""
+    inside the ranges are written by the same pass (hulc_adam_step_lo).
+    lr_dev: one-element fp32 tensor on the parameters' device holding the learning rate (hulc_adam_step_sched); `lr` is then ignored and a
+    captured launch follows whatever the host writes into lr_dev between replays."""
     # algorithmic bytes per element (bench.py's roofline): p, g, m, v read (16 B), p, m, v written (12 B), the bf16 shadow (2 B) and, inside
     # lo_ranges, the remainder (2 B)
     n_lo = sum(int(e) - int(b) for b, e in lo_ranges) if (lo is not None and lo_ranges) else 0
     nbytes = float(n) * (16 + 12 + (2 if shadow is not None else 0)) + 2.0 * n_lo
-    if loss_scale_dev is not None or found_inf_dev is not None:
-        # torch.amp.GradScaler's device scalars (hulc_adam_step_amp, ABI 5): fp32 tensors of one element on the arena's device
-        for t in (loss_scale_dev, found_inf_dev):
-            if t is not None and (t.dtype != torch.float32 or t.numel() != 1 or t.device != p.device):
-                raise _L.HulcKernelError("adam_step: loss_scale / found_inf are one-element fp32 tensors on the parameters' device")
+    if lr_dev is not None or loss_scale_dev is not None or found_inf_dev is not None:
+        # device scalars: torch.amp.GradScaler's (hulc_adam_step_amp, ABI 5) and the learning rate (hulc_adam_step_sched) — fp32 tensors of
+        # one element on the arena's device
+        for t in (lr_dev, loss_scale_dev, found_inf_dev):
+            if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != 1 or t.device != p.device):
+                raise _L.HulcKernelError("adam_step: lr_dev / loss_scale / found_inf are one-element fp32 tensors on the parameters' device")
         has_lo = lo is not None and bool(lo_ranges)
         flat = [int(x) for r in lo_ranges for x in r] if has_lo else [0, 0]
         arr = (_c.c_long * len(flat))(*flat)
-        _call("hulc_adam_step_amp", p, g, m, v, shadow, n, lr, beta1, beta2, eps, weight_decay, step,
-              step_state_dev, grad_scale, fault_word(p.device), lo if has_lo else None, arr if has_lo else None,
-              len(lo_ranges) if has_lo else 0, loss_scale_dev, found_inf_dev, nbytes=nbytes)
+        args = (p, g, m, v, shadow, n, lr, beta1, beta2, eps, weight_decay, step, step_state_dev, grad_scale, fault_word(p.device),
+                lo if has_lo else None, arr if has_lo else None, len(lo_ranges) if has_lo else 0, loss_scale_dev, found_inf_dev)
+        if lr_dev is not None:
+            _call("hulc_adam_step_sched", *args, lr_dev, nbytes=nbytes)
+        else:
+            _call("hulc_adam_step_amp", *args, nbytes=nbytes)
         return
     if lo is None or not lo_ranges:
         _call("hulc_adam_step", p, g, m, v, shadow, n, lr, beta1, beta2, eps, weight_decay, step,

@@ -90,9 +90,21 @@ class Hulc2(LightningModule):
             pf = distribution.plan_features
         plan_proposal.plan_features = plan_recognition.plan_features = action_decoder.plan_features = pf
 
+    @property
+    def num_training_steps(self) -> int:
+        """hulc2.py:160-162: what Lightning estimates for the whole fit"""
+        return int(self.trainer.estimated_stepping_batches)
+
+    def compute_warmup(self, num_training_steps: int, num_warmup_steps) -> Tuple[int, int]:
+        """hulc2.py:164-183: a negative num_training_steps is inferred from the trainer, a float num_warmup_steps is a fraction of the
+        training steps; the warm-up is cut to an int."""
+        from ..optim import resolve_warmup
+        return resolve_warmup(num_training_steps, num_warmup_steps, lambda: self.num_training_steps)
+
     def configure_optimizers(self):
-        """hulc2.py:185-198 (Adam lr 2e-4 + constant schedule).  The native trainer (hulc2_amd/trainer.py) replaces this
-        with the fused arena Adam; under Lightning any torch optimizer works (the keeper re-derives the weight copies)."""
+        """hulc2.py:185-198 (Adam lr 2e-4 + the configured lr_scheduler, stepped every optimizer step).  The native trainer
+        (hulc2_amd/trainer.py) replaces this with the fused arena Adam and ArenaTrainer.set_lr_schedule; under Lightning any torch optimizer
+        works (the keeper re-derives the weight copies)."""
         cfg = self.optimizer_config
         tgt = cfg.get("_target_") if hasattr(cfg, "get") else None
         if tgt == "torch.optim.Adam" and not os.environ.get("HULC_TORCH_ADAM"):
@@ -105,7 +117,13 @@ class Hulc2(LightningModule):
             opt = Adam(self.parameters(), **{k: v for k, v in cfg.items() if not str(k).startswith("_")})
         else:
             opt = instantiate(cfg, params=self.parameters())
-        sched = torch.optim.lr_scheduler.LambdaLR(opt, lambda _: 1.0)
+        from ..optim import make_lr_scheduler
+        sc = self.lr_scheduler
+        if "num_warmup_steps" in sc:                        # hulc2.py:187-193: -1 training steps = the trainer's estimate, a float warm-up = a fraction
+            sc["num_training_steps"], sc["num_warmup_steps"] = self.compute_warmup(sc["num_training_steps"], sc["num_warmup_steps"])
+            logger.info("Inferring number of training steps, set to %d", sc["num_training_steps"])
+            logger.info("Inferring number of warmup steps from ratio, set to %d", sc["num_warmup_steps"])
+        sched = make_lr_scheduler(sc, opt)
         return {"optimizer": opt, "lr_scheduler": {"scheduler": sched, "interval": "step", "frequency": 1}}
 
     # ---- hot path ----------------------------------------------------------------------------------

@@ -18,13 +18,61 @@ synchronising on `found_inf.item()`, and the Adam kernel applies them itself —
 Whenever the fused form does not apply — parameters not (yet) in an arena, a parameter that has state and no gradient, a parameter whose
 FIRST gradient arrives after the others have stepped (torch starts its step count at 1 then), amsgrad / maximize / decoupled weight decay /
 `fused=True`, several parameter groups, CPU — `step()` is torch.optim.Adam.step(), on the same state tensors."""
-from typing import Optional
+import importlib
+from typing import Callable, Optional, Tuple
 
 import torch
 
 from . import kernels as kn
 from . import shadow
+from .compat import instantiate
 from .trainer import arena_of
+
+CONSTANT_SCHEDULE = "transformers.get_constant_schedule"
+
+
+def resolve_warmup(num_training_steps: int, num_warmup_steps, inferred_steps: Callable[[], int]) -> Tuple[int, int]:
+    """Hulc2.compute_warmup's rule (reference: hulc2/models/hulc2.py:164-183) for any caller that knows the length of the run: a negative
+    num_training_steps is replaced by inferred_steps(), a float num_warmup_steps is a fraction of the training steps, cut to an int."""
+    if num_training_steps < 0:
+        num_training_steps = int(inferred_steps())
+    if isinstance(num_warmup_steps, float):
+        num_warmup_steps = num_warmup_steps * num_training_steps
+    return num_training_steps, int(num_warmup_steps)
+
+
+def make_lr_scheduler(cfg, optimizer):
+    """The configured `lr_scheduler._target_` on `optimizer` (reference: hulc2.py:194, conf/model/lr_scheduler/*.yaml: three
+    transformers.get_*_schedule* functions, each a LambdaLR).  Without an importable target only the constant schedule has a stand-in
+    (LambdaLR with factor 1.0, the same numbers); any other target raises — a warm-up / decay config never trains at a constant rate."""
+    tgt = cfg.get("_target_") if hasattr(cfg, "get") else None
+    if not tgt:
+        raise ValueError("lr_scheduler config without a _target_")
+    try:
+        importlib.import_module(tgt.rpartition(".")[0])
+    except ImportError as e:
+        if tgt == CONSTANT_SCHEDULE:
+            return torch.optim.lr_scheduler.LambdaLR(optimizer, lambda _: 1.0)
+        raise ImportError(f"lr_scheduler target {tgt!r} cannot be imported ({e}); only {CONSTANT_SCHEDULE} has a built-in stand-in") from e
+    return instantiate(cfg, optimizer)
+
+
+def lr_lambda_from_config(cfg, num_training_steps: Optional[int] = None) -> Callable[[int], float]:
+    """The factor function of an `lr_scheduler` config for ArenaTrainer.set_lr_schedule: the configured target is instantiated on a
+    throw-away one-parameter optimizer and its `lr_lambdas[0]` handed back — the reference's own Python function, not a copy of it.
+    num_training_steps: the length of the run, used where the config says -1 (Lightning's estimated_stepping_batches in the reference)."""
+    cfg = dict(cfg)
+    if "num_warmup_steps" in cfg:
+        def inferred():
+            if num_training_steps is None:
+                raise ValueError("lr_scheduler.num_training_steps < 0 needs num_training_steps")
+            return num_training_steps
+        cfg["num_training_steps"], cfg["num_warmup_steps"] = resolve_warmup(cfg["num_training_steps"], cfg["num_warmup_steps"], inferred)
+    sched = make_lr_scheduler(cfg, torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=1.0))
+    lambdas = getattr(sched, "lr_lambdas", None)
+    if not lambdas:
+        raise TypeError(f"lr_scheduler target {cfg.get('_target_')!r} is not a LambdaLR: no lr_lambdas to take the factor from")
+    return lambdas[0]
 
 
 class Adam(torch.optim.Adam):

@@ -16,6 +16,7 @@ backward -> DDP bucketed all-reduce -> Adam step).  Lightning is a third-party l
 from typing import Dict, List, Optional
 
 import contextlib
+import ctypes
 import os
 import weakref
 
@@ -367,6 +368,7 @@ class ArenaTrainer:
         if prev is not None:                               # an earlier trainer of this model: its load hook would keep re-homing weights into a
             prev.close()                                   # dead arena (and keep that arena alive) — ADVICE r02
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
+        self.base_lr = lr                                  # what a schedule's factor multiplies (torch: the group's initial_lr)
         self.params = [p for p in model.parameters() if p.requires_grad]
         dev = self.params[0].device
         # arena order = registration order, except that modules may ask for groups of parameters to sit back to back
@@ -685,7 +687,9 @@ class ArenaTrainer:
             st[names[id(p)]] = {"exp_avg": self.exp_avg[off:off + n].view(p.shape).clone(),
                                 "exp_avg_sq": self.exp_avg_sq[off:off + n].view(p.shape).clone()}
         words = kn.step_state(self.dev).tolist() if self.dev.type == "cuda" else [0, self.step_count]
-        return {"state": st, "step": int(self.step_count), "rng_word": int(words[0]), "device_step": int(words[1]),
+        # (the schedule's function is not state, as with torch's LambdaLR: the resumed run attaches the same one, before or after loading)
+        return {"lr_schedule": {"base_lr": float(self.base_lr), "position": int(self._opt_steps), "device_lr": self._lr_dev is not None},
+                "state": st, "step": int(self.step_count), "rng_word": int(words[0]), "device_step": int(words[1]),
                 "comm": ({"algo": self.comm.algo, "payload": self.comm.payload, "chosen_by": self.comm.chosen_by} if self.comm is not None else None),
                 "hparams": {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd}}
 
@@ -705,6 +709,11 @@ class ArenaTrainer:
                 self.exp_avg_sq[off:off + k].copy_(rec["exp_avg_sq"].reshape(-1))
         self.step_count = int(sd["step"])
         hp = sd.get("hparams", {})
+        sched = sd.get("lr_schedule")
+        if sched is not None:                                     # the resumed run continues the same learning-rate sequence
+            self.base_lr, self._opt_steps = float(sched["base_lr"]), int(sched["position"])
+            if sched.get("device_lr") and self._lr_dev is None:
+                self.set_lr(hp.get("lr", self.lr))
         self._set_hparams(hp.get("lr", self.lr), hp.get("betas", self.betas), hp.get("eps", self.eps), hp.get("weight_decay", self.wd))
         algo = (sd.get("comm") or {}).get("algo")
         if algo in ("ring", "direct") and self.comm is not None and self.comm.active and not os.environ.get("HULC_ALLREDUCE"):
@@ -731,9 +740,14 @@ class ArenaTrainer:
                 state[i] = {"step": torch.tensor(float(self.step_count)),
                             "exp_avg": self.exp_avg[off:off + n].view(p.shape).clone(),
                             "exp_avg_sq": self.exp_avg_sq[off:off + n].view(p.shape).clone()}
-        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd, "amsgrad": False, "maximize": False,
+        lr = self.lr
+        if self._lr_lambda is not None:                           # what a torch scheduler leaves behind k steps: base * lambda(k) and initial_lr
+            lr = float(self.base_lr) * self._lr_lambda(self._opt_steps)
+        group = {"lr": lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd, "amsgrad": False, "maximize": False,
                  "foreach": None, "capturable": False, "differentiable": False, "fused": None, "decoupled_weight_decay": False,
                  "params": list(range(len(order)))}
+        if self._lr_lambda is not None:
+            group["initial_lr"] = float(self.base_lr)
         return {"state": state, "param_groups": [group]}
 
     def from_torch_adam_state_dict(self, sd: Dict) -> None:
@@ -766,7 +780,10 @@ class ArenaTrainer:
         if len(steps) > 1:
             raise ValueError(f"per-parameter Adam steps differ ({sorted(steps)}): the arena optimizer keeps one step count")
         self.step_count = steps.pop() if steps else 0
+        self._opt_steps = self.step_count                         # (a scheduler stepped once per optimizer step stands at the same count)
         g0 = groups[0]
+        if "initial_lr" in g0:
+            self.base_lr = float(g0["initial_lr"])
         if g0.get("amsgrad") or g0.get("maximize"):
             raise NotImplementedError("amsgrad / maximize are not built (conf/model/optimizer/adam.yaml uses neither)")
         self._set_hparams(g0["lr"], g0["betas"], g0["eps"], g0.get("weight_decay", 0.0))
@@ -780,9 +797,41 @@ class ArenaTrainer:
         (the lr in a Lightning checkpoint is the scheduler's current value, not the constructor's)."""
         new = (float(lr), tuple(float(b) for b in betas), float(eps), float(wd))
         old = (float(self.lr), tuple(float(b) for b in self.betas), float(self.eps), float(self.wd))
+        if self._lr_dev is not None:                              # device-lr mode (set_lr): the learning rate is no kernel argument
+            self.set_lr(lr)
+            new, old = new[1:], old[1:]
         self.lr, self.betas, self.eps, self.wd = lr, tuple(betas), eps, wd
         if new != old and getattr(self, "graph_opt", None) is not None:
             self.graph_fb = self.graph_enc = self.graph_opt = None
+
+    # ---- learning-rate schedules: the learning rate as a device scalar the captured optimizer launch reads --------------------------------
+    _lr_dev = None                 # one fp32 element on the arena's device once set_lr() was called (device-lr mode); None = scalar kernel argument
+    _lr_lambda = None              # the attached schedule (set_lr_schedule)
+    _opt_steps = 0                 # optimizer steps this trainer has RUN (eager or replayed; a capture runs none): the schedule position
+
+    def set_lr(self, lr: float) -> None:
+        """The learning rate of the following optimizer steps, written into a device scalar the Adam kernel reads (hulc_adam_step_sched): a
+        stream-ordered one-element fill, no host synchronisation, and captured graphs follow it.  The first call switches the trainer to this
+        mode and drops graphs captured with the learning rate as a kernel argument (as _set_hparams does); later calls never drop one."""
+        if self._lr_dev is None:
+            self._lr_dev = torch.zeros(1, dtype=torch.float32, device=self.dev)
+            if getattr(self, "graph_opt", None) is not None:
+                self.graph_fb = self.graph_enc = self.graph_opt = None
+        self._lr_dev.fill_(ctypes.c_float(lr).value)              # (rounded as the scalar kernel argument would be)
+        self.lr = lr
+
+    def set_lr_schedule(self, lr_lambda, base_lr: Optional[float] = None) -> None:
+        """torch.optim.lr_scheduler.LambdaLR's contract (reference: hulc2/models/hulc2.py:185-198, `interval: step`): the trainer's k-th
+        optimizer step, k from 0 and the warm-up steps of capture() included, runs with base_lr * lr_lambda(k), the product formed in Python
+        floats.  step() and replay() write it in front of the optimizer launch / graph.  base_lr: default the trainer's current base."""
+        if base_lr is not None:
+            self.base_lr = float(base_lr)
+        self._lr_lambda = lr_lambda
+        self._apply_lr_schedule()
+
+    def _apply_lr_schedule(self) -> None:
+        if self._lr_lambda is not None:
+            self.set_lr(float(self.base_lr) * self._lr_lambda(self._opt_steps))
 
     def close(self) -> None:
         """Detach this trainer from the model: the load_state_dict post-hook (which keeps the trainer, hence its four arenas, alive through the
@@ -918,7 +967,8 @@ class ArenaTrainer:
         kn.adam_step(self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.flat_bf16, self.total, self.lr, self.betas[0],
                      self.betas[1], self.eps, self.wd, self.step_count, grad_scale=1.0 / self.world,
                      step_state_dev=kn.step_state(self.dev),       # step count lives on the device (graph replay)
-                     lo=self.flat_lo, lo_ranges=self.lo_ranges)    # (the split operands' remainders come out of the same pass)
+                     lo=self.flat_lo, lo_ranges=self.lo_ranges,    # (the split operands' remainders come out of the same pass)
+                     lr_dev=self._lr_dev)                          # (None unless set_lr / set_lr_schedule was called)
         # the derived copies: two launches behind Adam (were five: transposed tiles, fragment gather, residual, remainder gather, conv repack)
         if self.tiles_t is not None or self.conv_table is not None:
             kn.derive_copies(self.flat_bf16, self.flat_bf16_t, self.tiles_t, self.flat_p, self.conv_shadow, self.conv_table)
@@ -978,7 +1028,9 @@ class ArenaTrainer:
         self.buckets.finish()
         self._comm_wait_end(ev)
         with self.gpu_section():
+            self._apply_lr_schedule()
             self.optimizer_step()
+            self._opt_steps += 1
             self._poll_faults()
         return loss
 
@@ -1061,6 +1113,8 @@ class ArenaTrainer:
             self.buckets.finish()
             self._comm_wait_end(ev)
         with self.gpu_section():
+            self._apply_lr_schedule()                # (outside the captured region: the graph reads the device scalar)
             self.graph_opt.replay()
+            self._opt_steps += 1
             self._poll_faults()
         return self.static_loss

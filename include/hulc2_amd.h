@@ -647,6 +647,16 @@ int hulc_adam_step_lo(float* p, const float* g, float* m, float* v, void* bf16_s
 int hulc_adam_step_amp(float* p, const float* g, float* m, float* v, void* bf16_shadow, long n, float lr, float beta1, float beta2,
                        float eps, float weight_decay, int step, const unsigned long long* step_state, float grad_scale, const int* skip_flag,
                        void* lo_shadow, const long* lo_ranges, int n_ranges, const float* loss_scale, const float* found_inf, void* stream);
+/* (added under ABI 7 — a new symbol only; every earlier prototype and hulc_abi_version() are unchanged, so callers built against the ABI 7
+ * header keep working.)  The same step with the LEARNING RATE read from device memory: lr_dev (required, 4-byte aligned device float) replaces
+ * the scalar `lr`, which is then ignored.  Every thread reads it once at kernel start, next to found_inf / loss_scale; the arithmetic is that of
+ * the scalar entry points (lr / bias_correction1 in fp32), so *lr_dev == (float)lr gives bit-identical results.  A captured launch therefore
+ * follows a learning-rate schedule the host writes into lr_dev between replays (reference: the LambdaLR of hulc2/models/hulc2.py:185-198,
+ * stepped every optimizer step).  All other arguments as in hulc_adam_step_amp (loss_scale / found_inf / lo_shadow optional). */
+int hulc_adam_step_sched(float* p, const float* g, float* m, float* v, void* bf16_shadow, long n, float lr, float beta1, float beta2,
+                         float eps, float weight_decay, int step, const unsigned long long* step_state, float grad_scale, const int* skip_flag,
+                         void* lo_shadow, const long* lo_ranges, int n_ranges, const float* loss_scale, const float* found_inf,
+                         const float* lr_dev, void* stream);
 int hulc_step_count_advance_if(unsigned long long* state, const float* found_inf, void* stream);
 /* Device-resident step state {rng word, optimizer step count}: advanced by one kernel per training step so that
  * a captured hipGraph replays with fresh dropout masks / plan samples and the right Adam bias correction.
