@@ -8,7 +8,15 @@ the reference's own class paths (resolved to this package by hulc2_amd.compat).
 from .compat import Config
 
 
-def default_model_config(gripper_control: bool = True, dropout_p: float = 0.1, static_hw=(200, 200)) -> Config:
+DISTRIBUTIONS = {
+    # conf/model/distribution/discrete.yaml, conf/model/distribution/continuous.yaml
+    "discrete": {"_target_": "hulc2.utils.distributions.Distribution", "dist": "discrete", "category_size": 32, "class_size": 32},
+    "continuous": {"_target_": "hulc2.utils.distributions.Distribution", "dist": "continuous", "plan_features": 256},
+}
+
+
+def default_model_config(gripper_control: bool = True, dropout_p: float = 0.1, static_hw=(200, 200), distribution: str = "discrete") -> Config:
+    """distribution: "discrete" (the headline config) or "continuous" (`model/distribution=continuous`)"""
     act7 = [1.0] * 7
     return Config.wrap({
         "_target_": "hulc2.models.hulc2.Hulc2",
@@ -34,7 +42,7 @@ def default_model_config(gripper_control: bool = True, dropout_p: float = 0.1, s
             "num_heads": 8, "num_layers": 2, "encoder_hidden_size": 2048, "fc_hidden_size": 4096, "in_features": None,
             "plan_features": None, "action_space": 7, "dropout_p": dropout_p, "encoder_normalize": False,
             "positional_normalize": False, "position_embedding": True, "max_position_embeddings": 32},
-        "distribution": {"_target_": "hulc2.utils.distributions.Distribution", "dist": "discrete", "category_size": 32, "class_size": 32},
+        "distribution": dict(DISTRIBUTIONS[distribution]),
         "visual_goal": {
             "_target_": "hulc2.models.encoders.goal_encoders.VisualGoalEncoder", "in_features": None, "hidden_size": 2048,
             "latent_goal_features": 32, "l2_normalize_goal_embeddings": False, "activation_function": "ReLU"},

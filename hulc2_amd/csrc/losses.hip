@@ -6,6 +6,8 @@
 //       reference: Hulc2.compute_kl_loss, hulc2/models/hulc2.py:444-466 (+ torch.distributions categorical KL)
 //   straight-through one-hot sample of the 32x32 latent plan
 //       reference: hulc2/utils/distributions.py:23-27 + hulc2.py:235-237
+//   reparameterised sample of the continuous (diagonal Gaussian) latent plan + its balanced KL
+//       reference: hulc2/utils/distributions.py:28-29,55-59 + hulc2.py:235-237,444-466
 //   CLIP-style symmetric contrastive loss on projected features
 //       reference: Hulc2.clip_auxiliary_loss, hulc2.py:472-508
 //   world -> tcp frame change of the relative actions
@@ -273,6 +275,103 @@ __global__ __launch_bounds__(256) void plan_sample_bwd_kernel(const float* __res
     const float v = p * (gd - dot);
     const long i = (long)g * 32 + lane;
     dlogits[i] = accumulate ? dlogits[i] + v : v;
+}
+
+// ------------------------------------------------------------------------------------------------
+// continuous (diagonal Gaussian) latent plan: head outputs [B][2P] = [mean | r], std = softplus(r) + min_std
+//     reference: hulc2/utils/distributions.py:28-29,55-59 (state), hulc2.py:235-237 (rsample), hulc2.py:444-466 + torch's
+//     kl_divergence(Normal, Normal) (balanced KL)
+// A lane owns the PAIR of features (2k, 2k + 1) of a row: one Box-Muller transform of one pair of uniform draws gives both of its
+// normals.  The pair's counter is b * ceil(P / 2) + k in the forward and the backward kernel, so the noise is regenerated, never stored.
+// ------------------------------------------------------------------------------------------------
+HULC_DEVICE float softplus_grad(float r) { return r > 20.f ? 1.f : sigmoid_f(r); }   // d softplus / d r with torch's threshold
+HULC_DEVICE void gauss_pair(uint64_t seed, uint64_t pair, float& z0, float& z1) {
+    const float u1 = hulc_uniform01(seed, 2 * pair), u2 = hulc_uniform01(seed, 2 * pair + 1);
+    // u1 is a multiple of 2^-24 in [0, 1 - 2^-24]: 1 - u1 is exact and at least 2^-24, the radius finite (<= 5.77)
+    const float rad = sqrtf(-2.f * logf(1.f - u1));
+    float sn, cs;
+    sincospif(2.f * u2, &sn, &cs);                   // the angle 2 pi u2, reduced exactly
+    z0 = rad * cs; z1 = rad * sn;
+}
+
+// one workgroup per row; plan / eps_out / kl_row are each optional (NULL: that part is off); pp is read only for the KL
+__global__ __launch_bounds__(128) void gauss_plan_row_kernel(const float* __restrict__ pp, const float* __restrict__ pr,
+                                                             const float* __restrict__ eps_in, unsigned long long seed,
+                                                             const unsigned long long* __restrict__ seed_dev, int P, float min_std,
+                                                             float* __restrict__ plan, float* __restrict__ eps_out, float* __restrict__ kl_row) {
+    __shared__ float sh[16];
+    const int b = blockIdx.x, NP = (P + 1) >> 1;
+    if (seed_dev) seed ^= seed_dev[0];
+    const float* q = pr + (long)b * 2 * P;
+    const float* p = kl_row ? pp + (long)b * 2 * P : nullptr;      // (pp is required with the KL part)
+    const bool sample = plan || eps_out;
+    float acc = 0.f;
+    for (int k = threadIdx.x; k < NP; k += blockDim.x) {
+        float z[2] = {0.f, 0.f};
+        if (sample && !eps_in) gauss_pair(seed, (uint64_t)b * NP + k, z[0], z[1]);
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int j = 2 * k + e;
+            if (j >= P) break;
+            const float mq = q[j], sq = softplus_t(q[P + j]) + min_std;
+            if (sample) {
+                const float eps = eps_in ? eps_in[(long)b * P + j] : z[e];
+                if (plan) plan[(long)b * P + j] = mq + sq * eps;
+                if (eps_out) eps_out[(long)b * P + j] = eps;
+            }
+            if (kl_row) {                              // torch's kl_divergence(Normal q, Normal p): equal heads give exactly 0
+                const float mp = p[j], sp = softplus_t(p[P + j]) + min_std;
+                const float ratio = sq / sp, t = (mq - mp) / sp, r2 = ratio * ratio;
+                acc += 0.5f * (r2 + t * t - 1.f - logf(r2));
+            }
+        }
+    }
+    if (kl_row) {
+        acc = block_sum(acc, sh);
+        if (threadIdx.x == 0) kl_row[b] = acc;
+    }
+}
+
+// one lane per feature pair; dpr = KL part (gout) + sample part (dplan) summed here, dpp = KL part (written only with gout)
+__global__ __launch_bounds__(256) void gauss_plan_bwd_kernel(const float* __restrict__ pp, const float* __restrict__ pr,
+                                                             const float* __restrict__ eps_in, unsigned long long seed,
+                                                             const unsigned long long* __restrict__ seed_dev, int B, int P, float min_std,
+                                                             float beta, float mix, int nseg, const float* __restrict__ dplan,
+                                                             const float* __restrict__ gout, float* __restrict__ dpp, float* __restrict__ dpr) {
+    const int NP = (P + 1) >> 1;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)B * NP) return;
+    const int b = (int)(i / NP), k = (int)(i % NP);
+    if (seed_dev) seed ^= seed_dev[0];
+    float z[2] = {0.f, 0.f};
+    if (dplan && !eps_in) gauss_pair(seed, (uint64_t)i, z[0], z[1]);
+    const int Bs = B / nseg;
+    const float s = gout ? gout[b / Bs] * beta / Bs : 0.f;
+    const long row = (long)b * 2 * P;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const int j = 2 * k + e;
+        if (j >= P) break;
+        const float rq = pr[row + P + j], gq = softplus_grad(rq);
+        float dm = 0.f, dr = 0.f;
+        if (gout) {
+            const float mq = pr[row + j], sq = softplus_t(rq) + min_std;
+            const float mp = pp[row + j], rp = pp[row + P + j], sp = softplus_t(rp) + min_std;
+            const float ratio = sq / sp, t = (mq - mp) / sp, r2 = ratio * ratio;
+            dm = s * (1.f - mix) * t / sp;
+            dr = s * (1.f - mix) * (r2 - 1.f) / sq * gq;
+            dpp[row + j] = -s * mix * t / sp;
+            dpp[row + P + j] = s * mix * (1.f - r2 - t * t) / sp * softplus_grad(rp);
+        }
+        if (dplan) {
+            const float g = dplan[(long)b * P + j];
+            const float eps = eps_in ? eps_in[(long)b * P + j] : z[e];
+            dm += g;
+            dr += g * eps * gq;
+        }
+        dpr[row + j] = dm;
+        dpr[row + P + j] = dr;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -560,6 +659,30 @@ extern "C" int hulc_plan_sample_bwd(const float* logits, const float* dplan, int
     if (CLS != 32) return hulc_fail(-2, "hulc_plan_sample_bwd: class_size must be 32");
     plan_sample_bwd_kernel<<<(NG + 7) / 8, 256, 0, (hipStream_t)stream>>>(logits, dplan, NG, dlogits, accumulate);
     return hulc_check_launch("hulc_plan_sample_bwd");
+}
+
+extern "C" int hulc_gauss_plan_fwd(const float* pp, const float* pr, const float* eps_in, unsigned long long seed,
+                                   const unsigned long long* seed_dev, int B, int P, float min_std, float beta, int nseg, float* plan,
+                                   float* eps_out, float* out, float* kl_row, void* stream) {
+    if (!plan && !eps_out && !out) return hulc_fail(-1, "hulc_gauss_plan_fwd: nothing to compute (plan, eps_out and out are all null)");
+    if (!pr || (out && (!pp || !kl_row))) return hulc_fail(-1, "hulc_gauss_plan_fwd: null pointer");
+    if (B < 1 || P < 1) return hulc_fail(-2, "hulc_gauss_plan_fwd: needs B >= 1 and plan_features >= 1");
+    if (out && (nseg < 1 || B % nseg)) return hulc_fail(-2, "hulc_gauss_plan_fwd: the batch must split evenly into nseg segments");
+    gauss_plan_row_kernel<<<B, 128, 0, (hipStream_t)stream>>>(pp, pr, eps_in, seed, seed_dev, P, min_std, plan, eps_out, out ? kl_row : nullptr);
+    if (out) cat_kl_sum_kernel<<<nseg, 1024, 0, (hipStream_t)stream>>>(kl_row, B / nseg, B / nseg, beta, out);
+    return hulc_check_launch("hulc_gauss_plan_fwd");
+}
+extern "C" int hulc_gauss_plan_bwd(const float* pp, const float* pr, const float* eps_in, unsigned long long seed,
+                                   const unsigned long long* seed_dev, int B, int P, float min_std, float beta, float mix, int nseg,
+                                   const float* dplan, const float* gout, float* dpp, float* dpr, void* stream) {
+    if (!dplan && !gout) return hulc_fail(-1, "hulc_gauss_plan_bwd: nothing to compute (dplan and gout are both null)");
+    if (!pr || !dpr || (gout && (!pp || !dpp))) return hulc_fail(-1, "hulc_gauss_plan_bwd: null pointer");
+    if (B < 1 || P < 1) return hulc_fail(-2, "hulc_gauss_plan_bwd: needs B >= 1 and plan_features >= 1");
+    if (gout && (nseg < 1 || B % nseg)) return hulc_fail(-2, "hulc_gauss_plan_bwd: the batch must split evenly into nseg segments");
+    const long n = (long)B * ((P + 1) / 2);
+    gauss_plan_bwd_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(pp, pr, eps_in, seed, seed_dev, B, P, min_std, beta, mix,
+                                                                                        gout ? nseg : 1, dplan, gout, dpp, dpr);
+    return hulc_check_launch("hulc_gauss_plan_bwd");
 }
 
 static size_t clip_smem(int M) { return ((size_t)4 * M * (CLIP_D + 1) + (size_t)M * (M + 1) + 5 * (size_t)M) * sizeof(float); }

@@ -799,6 +799,88 @@ class PlanSampleKLFn(torch.autograd.Function):
         return dpp, dpr, None, None, None, None, None, None, None
 
 
+@_scoped
+class GaussPlanKLFn(torch.autograd.Function):
+    """PlanSampleKLFn for the continuous plan (conf/model/distribution/continuous.yaml): pp_raw / pr_raw are the heads' raw (B, 2P) outputs
+    [mean | r], std = softplus(r) + 1e-4 (distributions.py:55-59) -> (plan (B, P), kl (nseg,)).  Forward: the row kernel + the segment sum;
+    backward: ONE launch, the sample's gradient summed onto the KL's inside it.  The noise is never kept: the backward regenerates it from
+    (seed, device step word), or reads the injected eps_in."""
+
+    @staticmethod
+    def forward(ctx, pp, pr, eps_in, seed: int, beta: float, mix: float, nseg: int):
+        pp, pr = _c(pp), _c(pr)
+        B, P = pr.shape[0], pr.shape[1] // 2
+        eps_in = _c(eps_in) if eps_in is not None else None
+        plan = _f32(B, P, like=pr)
+        out = _f32(nseg, like=pp)
+        klr = _f32(B, like=pp)
+        kn.gauss_plan_fwd(pp, pr, eps_in, seed, B, P, beta, nseg, plan, None, out, klr)
+        ctx.save_for_backward(pp, pr, eps_in)
+        ctx.meta = (B, P, seed, beta, mix, nseg)
+        ctx.set_materialize_grads(False)
+        return plan, out
+
+    @staticmethod
+    def backward(ctx, dplan, gkl=None):
+        pp, pr, eps_in = ctx.saved_tensors
+        B, P, seed, beta, mix, nseg = ctx.meta
+        if dplan is None and gkl is None:
+            return None, None, None, None, None, None, None
+        dpr = torch.empty_like(pr)
+        dpp = torch.empty_like(pp) if gkl is not None else None
+        kn.gauss_plan_bwd(pp, pr, eps_in, seed, B, P, beta, mix, nseg, _c(dplan) if dplan is not None else None,
+                          _c(gkl.reshape(nseg)) if gkl is not None else None, dpp, dpr)
+        return dpp, dpr, None, None, None, None, None
+
+
+@_scoped
+class GaussPlanSampleFn(torch.autograd.Function):
+    """the sample alone: raw (B, 2P) head output -> plan (B, P) = mean + std * eps"""
+
+    @staticmethod
+    def forward(ctx, raw, eps_in, seed: int):
+        raw = _c(raw)
+        B, P = raw.shape[0], raw.shape[1] // 2
+        eps_in = _c(eps_in) if eps_in is not None else None
+        plan = _f32(B, P, like=raw)
+        kn.gauss_plan_fwd(None, raw, eps_in, seed, B, P, 0.0, 1, plan, None, None, None)
+        ctx.save_for_backward(raw, eps_in)
+        ctx.meta = (B, P, seed)
+        return plan
+
+    @staticmethod
+    def backward(ctx, dplan):
+        raw, eps_in = ctx.saved_tensors
+        B, P, seed = ctx.meta
+        draw = torch.empty_like(raw)
+        kn.gauss_plan_bwd(None, raw, eps_in, seed, B, P, 0.0, 0.0, 1, _c(dplan), None, None, draw)
+        return draw, None, None
+
+
+@_scoped
+class GaussKLFn(torch.autograd.Function):
+    """CatKLFn for the continuous plan: balanced KL of hulc2.py:444-466 on the raw (B, 2P) head outputs of prior (pp) and posterior (pr)"""
+
+    @staticmethod
+    def forward(ctx, pp, pr, beta: float, mix: float, nseg: int = 1):
+        pp, pr = _c(pp), _c(pr)
+        B, P = pr.shape[0], pr.shape[1] // 2
+        out = _f32(nseg, like=pp)
+        klr = _f32(B, like=pp)
+        kn.gauss_plan_fwd(pp, pr, None, 0, B, P, beta, nseg, None, None, out, klr)
+        ctx.save_for_backward(pp, pr)
+        ctx.meta = (B, P, beta, mix, nseg)
+        return out[0] if nseg == 1 else out
+
+    @staticmethod
+    def backward(ctx, g):
+        pp, pr = ctx.saved_tensors
+        B, P, beta, mix, nseg = ctx.meta
+        dpp, dpr = torch.empty_like(pp), torch.empty_like(pr)
+        kn.gauss_plan_bwd(pp, pr, None, 0, B, P, beta, mix, nseg, None, _c(g.reshape(nseg)), dpp, dpr)
+        return dpp, dpr, None, None, None
+
+
 # ------------------------------------------------------------------------------------------------
 # transformer pieces
 # ------------------------------------------------------------------------------------------------

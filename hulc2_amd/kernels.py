@@ -1290,6 +1290,31 @@ def plan_sample_bwd(logits, dplan, NG, CLS, dlogits, accumulate=False):
     _call("hulc_plan_sample_bwd", logits, dplan, NG, CLS, dlogits, accumulate)
 
 
+GAUSS_MIN_STD = 1e-4           # distributions.py:57
+
+
+def _first_device(*ts):
+    """the device of the first tensor given (a launcher refuses a missing operand itself: the wrapper must get that far)"""
+    for t in ts:
+        if t is not None:
+            _require_cuda(t)
+            return t.device
+    raise _L.HulcKernelError("no tensor operand")
+
+
+def gauss_plan_fwd(pp, pr, eps_in, seed, B, P, beta, nseg, plan, eps_out, out, kl_row, min_std=GAUSS_MIN_STD):
+    """continuous latent plan: sample (plan / eps_out) from the head `pr` and / or balanced KL (out, kl_row) against `pp`; parts are switched
+    off by None.  Without eps_in the noise follows the device step word: a replayed graph draws fresh noise."""
+    word = step_state(_first_device(pr, pp, plan, eps_out, out)) if eps_in is None else None
+    _call("hulc_gauss_plan_fwd", pp, pr, eps_in, seed, word, B, P, min_std, beta, nseg, plan, eps_out, out, kl_row)
+
+
+def gauss_plan_bwd(pp, pr, eps_in, seed, B, P, beta, mix, nseg, dplan, gout, dpp, dpr, min_std=GAUSS_MIN_STD):
+    """one launch: dpr = KL part (gout) + sample part (dplan), dpp = KL part; the noise is regenerated from (seed, step word) or read from eps_in"""
+    word = step_state(_first_device(pr, pp, dplan, gout, dpr)) if eps_in is None else None
+    _call("hulc_gauss_plan_bwd", pp, pr, eps_in, seed, word, B, P, min_std, beta, mix, nseg, dplan, gout, dpp, dpr)
+
+
 def clip_loss_fwd(im, tx, use, logit_scale, M, D, out, row0=0):
     _call("hulc_clip_loss_fwd", im, tx, use, row0, logit_scale, M, D, out)
 

@@ -8,7 +8,9 @@ metric names and the same attribute names (hence state_dict keys); and for valid
 
 Differences that do not change results:
   * the categorical plan sample can be injected through `dataset_batch["plan_idx"]` (parity tests); otherwise it
-    is drawn on-device by the counter RNG (the reference uses torch.multinomial — no shared RNG stream exists)
+    is drawn on-device by the counter RNG (the reference uses torch.multinomial — no shared RNG stream exists).
+    With the continuous distribution the injected quantity is the Gaussian noise, `dataset_batch["plan_eps"]` of shape
+    (B, plan_features) (`plan_eps_pp` / `plan_eps_pr` in validation); `plan_idx` is ignored there
   * `use_for_aux_lang_loss` is applied inside the CLIP loss kernel instead of boolean-mask indexing, so the step
     has no host synchronisation (the reference's `torch.any` / dynamic shapes, hulc2.py:391-394,490-493)
 """
@@ -136,13 +138,13 @@ class Hulc2(LightningModule):
             return kn.site_scope("goal")
         return contextlib.nullcontext()
 
-    def lmp_train(self, perceptual_emb, latent_goal, train_acts, robot_obs, plan_idx: Optional[torch.Tensor] = None
-                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, State, State, torch.Tensor]:
+    def lmp_train(self, perceptual_emb, latent_goal, train_acts, robot_obs, plan_idx: Optional[torch.Tensor] = None,
+                  plan_eps: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, State, State, torch.Tensor]:
         """hulc2.py:200-245; returns the prior/posterior *states* in place of torch.distributions objects."""
         pp_state = self.plan_proposal(perceptual_emb[:, 0], latent_goal)
         pr_state, seq_feat = self.plan_recognition(perceptual_emb, seed=trunk_site(self.modality_scope))
         site = 0xA11CE if "lang" in self.modality_scope else 0xB0B       # distinct RNG sites for the two modalities
-        sampled_plan, _ = self.dist.rsample_plan(pr_state, seed=site, idx=plan_idx)
+        sampled_plan, _ = self.dist.rsample_plan(pr_state, seed=site, idx=plan_idx, eps=plan_eps)
         action_loss = self.action_decoder.loss(sampled_plan, perceptual_emb, latent_goal, train_acts, robot_obs)
         kl_loss = self.compute_kl_loss(pp_state, pr_state)
         return kl_loss, action_loss, action_loss + kl_loss, pp_state, pr_state, seq_feat
@@ -293,7 +295,7 @@ class Hulc2(LightningModule):
                     pp_all = self.plan_proposal(emb0, goal_all)
             if fork:
                 cur.wait_stream(side)                      # join: sample + KL consume both branches
-                for t_ in (pr_all.logit, seq_all):
+                for t_ in (self.dist.state_tensor(pr_all), seq_all):
                     t_.record_stream(cur)
             else:
                 pr_all, seq_all = self.plan_recognition(emb_rec)
@@ -322,9 +324,12 @@ class Hulc2(LightningModule):
                 clip_forked = True
             # sample, KL and decoder once over the stacked rows; the KL / decoder kernels return one mean per modality.  Sample + KL are ONE
             # autograd node (both consume the posterior's logits: their gradients meet inside the kernels, not in a fan-in add)
-            idxs = [db.get("plan_idx") for _, db in mods]
-            idx_all = torch.cat(idxs, dim=0) if all(i is not None for i in idxs) else None
-            plan_all, _, kls = self.dist.rsample_plan_and_kl(pp_all, pr_all, 0xA11CE, idx_all, self.kl_beta, self.kl_balancing_mix, len(mods))
+            # (injected sample, parity tests: class indices for the categorical plan, Gaussian noise for the continuous one)
+            cont = self.dist.dist == "continuous"
+            inj = [db.get("plan_eps" if cont else "plan_idx") for _, db in mods]
+            inj_all = torch.cat(inj, dim=0) if all(i is not None for i in inj) else None
+            plan_all, _, kls = self.dist.rsample_plan_and_kl(pp_all, pr_all, 0xA11CE, None if cont else inj_all, self.kl_beta,
+                                                             self.kl_balancing_mix, len(mods), eps=inj_all if cont else None)
             kl_stacked = kls
             act_losses = self.action_decoder.loss_stacked(plan_all, emb_dec_t if fan else emb_all, goal_all,
                                                           [db["actions"] for _, db in mods], [db["state_info"]["robot_obs"] for _, db in mods],
@@ -339,7 +344,7 @@ class Hulc2(LightningModule):
                     pp_state = self.plan_proposal(emb[:, 0], latent_goal)
                 pr_state, seq_feat = self.plan_recognition(emb, seed=trunk_site(self.modality_scope))
                 site = 0xA11CE if "lang" in self.modality_scope else 0xB0B
-                plan, _ = self.dist.rsample_plan(pr_state, seed=site, idx=db.get("plan_idx"))
+                plan, _ = self.dist.rsample_plan(pr_state, seed=site, idx=db.get("plan_idx"), eps=db.get("plan_eps"))
                 per.append((self.modality_scope, db, emb, latent_goal, seq_feat, plan, self.compute_kl_loss(pp_state, pr_state)))
             # the action decoder sees all modalities at once (shared weights, independent sequences); it returns one loss per
             # modality, each the mean over that modality's own tokens as in the reference (hulc2.py:239-241)
@@ -415,16 +420,17 @@ class Hulc2(LightningModule):
     # ---- validation and rollout inference on the same kernels ------------------------
     _plan_calls = 0
 
-    def _sample_plan(self, state: State, idx: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """dist.sample_latent_plan(dist.get_dist(state)) (distributions.py:23-35, hulc2.py:287,302): a one-hot draw per category,
-        no gradient.  A fresh counter-RNG stream per call; `idx` injects the class indices (parity tests)."""
+    def _sample_plan(self, state: State, idx: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """dist.sample_latent_plan(dist.get_dist(state)) (distributions.py:23-35, hulc2.py:287,302): a one-hot draw per category (a Gaussian
+        draw for the continuous plan), no gradient.  A fresh counter-RNG stream per call; `idx` injects the class indices, `eps` the
+        Gaussian noise (parity tests)."""
         Hulc2._plan_calls += 1
         with torch.no_grad():
-            plan, _ = self.dist.rsample_plan(state, seed=0xC0FFEE00 + Hulc2._plan_calls, idx=idx)
+            plan, _ = self.dist.rsample_plan(state, seed=0xC0FFEE00 + Hulc2._plan_calls, idx=idx, eps=eps)
         return plan
 
     @torch.no_grad()
-    def lmp_val(self, perceptual_emb, latent_goal, actions, robot_obs, plan_idx_pp=None, plan_idx_pr=None):
+    def lmp_val(self, perceptual_emb, latent_goal, actions, robot_obs, plan_idx_pp=None, plan_idx_pr=None, plan_eps_pp=None, plan_eps_pr=None):
         """hulc2.py:247-334: plans sampled from the prior and the posterior, decoder loss + one sampled action sequence for each,
         KL, per-dimension mean absolute errors and gripper success rates."""
         def metrics(sample_act):
@@ -433,11 +439,11 @@ class Hulc2(LightningModule):
             return mae, torch.mean((actions[..., -1] == grip).float())
 
         pp_state = self.plan_proposal(perceptual_emb[:, 0], latent_goal)
-        sampled_plan_pp = self._sample_plan(pp_state, plan_idx_pp)
+        sampled_plan_pp = self._sample_plan(pp_state, plan_idx_pp, plan_eps_pp)
         action_loss_pp, sample_act_pp = self.action_decoder.loss_and_act(sampled_plan_pp, perceptual_emb, latent_goal, actions, robot_obs)
         mae_pp, gripper_sr_pp = metrics(sample_act_pp)
         pr_state, seq_feat = self.plan_recognition(perceptual_emb)
-        sampled_plan_pr = self._sample_plan(pr_state, plan_idx_pr)
+        sampled_plan_pr = self._sample_plan(pr_state, plan_idx_pr, plan_eps_pr)
         action_loss_pr, sample_act_pr = self.action_decoder.loss_and_act(sampled_plan_pr, perceptual_emb, latent_goal, actions, robot_obs)
         mae_pr, gripper_sr_pr = metrics(sample_act_pr)
         kl_loss = self.compute_kl_loss(pp_state, pr_state)
@@ -455,7 +461,8 @@ class Hulc2(LightningModule):
             emb = self.perceptual_encoder(db["rgb_obs"], db["depth_obs"], db["robot_obs"])
             latent_goal = self.language_goal(db["lang"]) if "lang" in self.modality_scope else self.visual_goal(emb[:, -1])
             (plan_pp, act_loss_pp, plan_pr, act_loss_pr, kl_loss, mae_pp, mae_pr, grip_pp, grip_pr, seq_feat) = self.lmp_val(
-                emb, latent_goal, db["actions"], db["state_info"]["robot_obs"], db.get("plan_idx_pp"), db.get("plan_idx_pr"))
+                emb, latent_goal, db["actions"], db["state_info"]["robot_obs"], db.get("plan_idx_pp"), db.get("plan_idx_pr"),
+                db.get("plan_eps_pp"), db.get("plan_eps_pr"))
             if "lang" in self.modality_scope and self.use_clip_auxiliary_loss:
                 self.log("val/val_pred_clip_loss", self.clip_auxiliary_loss(seq_feat, latent_goal, db["use_for_aux_lang_loss"]), sync_dist=True)
             val_total_act_loss_pp = act_loss_pp if val_total_act_loss_pp is None else val_total_act_loss_pp + act_loss_pp

@@ -1,9 +1,10 @@
 """Latent-plan distribution helper.
 
 Mirrors hulc2.utils.distributions.Distribution (reference hulc2/utils/distributions.py:15-60) for the
-configured discrete 32x32 one-hot categorical.  `get_dist` still returns torch.distributions objects for
-callers outside the hot path (validation / t-SNE); the training step itself uses the fused HIP kernels
-through `rsample_plan` / `kl_balanced`.
+discrete 32x32 one-hot categorical (conf/model/distribution/discrete.yaml) and the continuous diagonal Gaussian
+(conf/model/distribution/continuous.yaml).  `get_dist` still returns torch.distributions objects for callers outside
+the hot path (validation / t-SNE); the training step itself uses the fused HIP kernels through `rsample_plan` /
+`kl_balanced` / `rsample_plan_and_kl`, which dispatch on `dist`.
 """
 from collections import namedtuple
 from typing import Optional, Union
@@ -17,49 +18,124 @@ DiscState = namedtuple("DiscState", ["logit"])
 ContState = namedtuple("ContState", ["mean", "std"])
 State = Union[DiscState, ContState]
 
+MIN_STD = 0.0001                 # distributions.py:57
+
+
+class RawContState(ContState):
+    """The ContState `forward_dist` returns in continuous mode: `.mean` / `.std`, unpacking and isinstance are the reference's
+    (mean, std = chunk(x, 2, -1); std = softplus(std) + 1e-4, distributions.py:55-59), and `.raw` is the head's output [mean | r] the fused
+    kernels read.  mean (a view of raw) and std are formed on first access: a training step, which hands `.raw` to one autograd node,
+    launches no chunk / softplus / add for them."""
+
+    def __new__(cls, raw):
+        self = tuple.__new__(cls, (None, None))
+        self.raw = raw
+        self._fields_made = None
+        return self
+
+    def _made(self):
+        if self._fields_made is None:
+            import torch.nn.functional as F
+            mean, r = torch.chunk(self.raw, 2, dim=-1)
+            self._fields_made = (mean, F.softplus(r) + MIN_STD)
+        return self._fields_made
+
+    mean = property(lambda self: self._made()[0])
+    std = property(lambda self: self._made()[1])
+
+    def __iter__(self):
+        return iter(self._made())
+
+    def __getitem__(self, i):
+        return self._made()[i]
+
+    def __repr__(self):
+        return f"ContState(mean={self.mean!r}, std={self.std!r})"
+
+    def __reduce__(self):
+        return (RawContState, (self.raw,))
+
 
 class Distribution:
     def __init__(self, **kwargs):
         self.dist = kwargs.get("dist")
         assert self.dist == "discrete" or self.dist == "continuous"
-        if self.dist == "continuous":
-            raise NotImplementedError("continuous latent plans are not on the configured path (conf/model/distribution/discrete.yaml)")
-        self.category_size = kwargs.get("category_size")
-        self.class_size = kwargs.get("class_size")
+        if self.dist == "discrete":
+            self.category_size = kwargs.get("category_size")
+            self.class_size = kwargs.get("class_size")
+        else:
+            self.plan_features = kwargs.get("plan_features")
 
     # ---- reference API -------------------------------------------------------------------------
     def get_dist(self, state):
-        from torch.distributions import Independent, OneHotCategoricalStraightThrough
+        from torch.distributions import Independent, Normal, OneHotCategoricalStraightThrough
+        if self.dist == "continuous":
+            return Independent(Normal(state.mean, state.std), 1)
         shape = state.logit.shape
         logits = torch.reshape(state.logit, shape=(*shape[:-1], self.category_size, self.class_size))
         return Independent(OneHotCategoricalStraightThrough(logits=logits), 1)
 
     def detach_state(self, state):
+        if self.dist == "continuous":
+            if isinstance(state, RawContState):
+                return RawContState(state.raw.detach())
+            return ContState(state.mean.detach(), state.std.detach())
         return DiscState(state.logit.detach())
 
     def sample_latent_plan(self, distribution):
-        return torch.flatten(distribution.sample(), start_dim=-2, end_dim=-1)
+        sampled_plan = distribution.sample()
+        if self.dist == "discrete":
+            sampled_plan = torch.flatten(sampled_plan, start_dim=-2, end_dim=-1)
+        return sampled_plan
 
     def build_state(self, hidden_size, plan_features):
+        if self.dist == "continuous":
+            return nn.Sequential(nn.Linear(hidden_size, 2 * plan_features))
         return nn.Sequential(nn.Linear(hidden_size, plan_features))
 
     def forward_dist(self, x):
+        if self.dist == "continuous":
+            return RawContState(x)
         return DiscState(x)
 
     # ---- fused hot-path entry points -----------------------------------------------------------
-    def rsample_plan(self, state: DiscState, seed: int, idx: Optional[torch.Tensor] = None):
-        """pr_dist.rsample() flattened (hulc2.py:235-237): straight-through one-hot; returns (plan, idx)."""
+    @staticmethod
+    def _raw(state: ContState) -> torch.Tensor:
+        """the head output [mean | r] behind a continuous state (the fused kernels apply softplus themselves)"""
+        raw = getattr(state, "raw", None)
+        if raw is None:
+            from hulc2_amd.lib import HulcKernelError
+            raise HulcKernelError("the continuous hot path reads the raw head output: pass the state Distribution.forward_dist returned")
+        return raw
+
+    def state_tensor(self, state: State) -> torch.Tensor:
+        """the one tensor a state hangs on (stream bookkeeping of the training step)"""
+        return self._raw(state) if self.dist == "continuous" else state.logit
+
+    def rsample_plan(self, state: State, seed: int, idx: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None):
+        """pr_dist.rsample() flattened (hulc2.py:235-237) -> (plan, idx).  discrete: straight-through one-hot, `idx` injects the classes;
+        continuous: mean + std * eps, `eps` injects the noise (idx is ignored and returned as None)."""
+        if self.dist == "continuous":
+            return HF.GaussPlanSampleFn.apply(self._raw(state), eps, int(seed)), None
         return HF.PlanSampleFn.apply(state.logit, idx, self.category_size, self.class_size, int(seed))
 
-    def kl_balanced(self, pp_state: DiscState, pr_state: DiscState, kl_beta: float, mix: float) -> torch.Tensor:
+    def kl_balanced(self, pp_state: State, pr_state: State, kl_beta: float, mix: float) -> torch.Tensor:
         """Hulc2.compute_kl_loss (hulc2.py:444-466) in one kernel pair."""
+        if self.dist == "continuous":
+            return HF.GaussKLFn.apply(self._raw(pp_state), self._raw(pr_state), float(kl_beta), float(mix))
         return HF.CatKLFn.apply(pp_state.logit, pr_state.logit, self.category_size, self.class_size, float(kl_beta), float(mix))
 
-    def kl_balanced_segments(self, pp_state: DiscState, pr_state: DiscState, kl_beta: float, mix: float, nseg: int) -> torch.Tensor:
+    def kl_balanced_segments(self, pp_state: State, pr_state: State, kl_beta: float, mix: float, nseg: int) -> torch.Tensor:
         """the same loss for nseg modalities stacked on the batch axis: (nseg,) values, each the mean over its own rows"""
+        if self.dist == "continuous":
+            out = HF.GaussKLFn.apply(self._raw(pp_state), self._raw(pr_state), float(kl_beta), float(mix), int(nseg))
+            return out.reshape(1) if nseg == 1 else out
         return HF.CatKLFn.apply(pp_state.logit, pr_state.logit, self.category_size, self.class_size, float(kl_beta), float(mix), int(nseg))
 
-    def rsample_plan_and_kl(self, pp_state: DiscState, pr_state: DiscState, seed: int, idx, kl_beta: float, mix: float, nseg: int = 1):
+    def rsample_plan_and_kl(self, pp_state: State, pr_state: State, seed: int, idx, kl_beta: float, mix: float, nseg: int = 1, eps=None):
         """rsample_plan + kl_balanced_segments as one autograd node -> (plan, idx, kl (nseg,))"""
+        if self.dist == "continuous":
+            plan, kl = HF.GaussPlanKLFn.apply(self._raw(pp_state), self._raw(pr_state), eps, int(seed), float(kl_beta), float(mix), int(nseg))
+            return plan, None, kl
         return HF.PlanSampleKLFn.apply(pp_state.logit, pr_state.logit, idx, self.category_size, self.class_size, int(seed), float(kl_beta),
                                        float(mix), int(nseg))

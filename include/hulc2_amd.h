@@ -228,6 +228,30 @@ int hulc_cat_kl_bwd(const float* pp, const float* pr, const float* kl_group, int
 int hulc_plan_sample_fwd(const float* logits, const long* idx_in, unsigned long long seed, const unsigned long long* seed_dev,
                          int NG, int CLS, long* idx_out, float* plan, void* stream);
 int hulc_plan_sample_bwd(const float* logits, const float* dplan, int NG, int CLS, float* dlogits, int accumulate, void* stream);
+/* (added under ABI 7 — new symbols only; every earlier prototype and hulc_abi_version() are unchanged.)  The CONTINUOUS latent plan
+ * (conf/model/distribution/continuous.yaml; distributions.py:28-29,55-59, hulc2.py:235-237,444-466): reparameterised Gaussian sample and
+ * KL-balanced diagonal-Gaussian KL on the raw head outputs pp (prior) / pr (posterior), [B][2P] fp32 contiguous = [mean | r], with
+ * std = softplus(r) + min_std (torch's softplus: r for r > 20, else log1p(exp(r)); d std / d r = sigmoid(r), 1 past the threshold).
+ * fwd — each part is switched off by a null pointer (at least one of plan / eps_out / out must be given):
+ *   sample  plan[b][j] = mean_pr + std_pr * eps (plan and/or eps_out, [B][P]); eps from eps_in [B][P] when given (parity hook, the counterpart
+ *           of idx_in), else standard normal by Box-Muller from the counter RNG at seed ^ seed_dev[0] (seed_dev optional; one pair of draws
+ *           per pair of consecutive features; a zero draw stays finite); eps_out receives the noise used.  pr is the head to sample from.
+ *   KL      (out given; pp and kl_row [B] required) kl_row[b] = sum_j KL(N(mean_pr, std_pr) || N(mean_pp, std_pp)) formed as torch's
+ *           kl_divergence(Normal, Normal): ratio = std_q / std_p, t = (mean_q - mean_p) / std_p, 0.5 (ratio^2 + t^2 - 1 - log ratio^2), so
+ *           pp == pr gives exactly 0; out[seg] = beta * mean over the segment's rows, nseg equal segments as in hulc_cat_kl_fwd.
+ *   Two launches with the KL (row kernel + segment sum), one without; every sum in a fixed order, no atomics.
+ * bwd — one launch; dplan [B][P] and/or gout [nseg] (at least one).  dpr [B][2P] is always written: the KL part scaled by (1 - mix) plus the
+ *   sample part (d mean += dplan, d r += dplan * eps * sigmoid(r_pr)) summed inside the kernel; dpp [B][2P] (required with gout) gets the KL
+ *   part scaled by mix — the two detached copies of hulc2.py:460-461.  With s = gout[seg] * beta / rows per segment:
+ *   d mean_q = s (1 - mix) t / std_p, d mean_p = -s mix t / std_p, d std_q = s (1 - mix)(ratio^2 - 1) / std_q,
+ *   d std_p = s mix (1 - ratio^2 - t^2) / std_p, each std gradient times sigmoid(r): pp == pr gives exactly 0.  eps is never stored: the
+ *   backward regenerates it from the same (seed, seed_dev, index) or reads eps_in. */
+int hulc_gauss_plan_fwd(const float* pp, const float* pr, const float* eps_in, unsigned long long seed, const unsigned long long* seed_dev,
+                        int B, int P, float min_std, float beta, int nseg, float* plan, float* eps_out, float* out, float* kl_row,
+                        void* stream);
+int hulc_gauss_plan_bwd(const float* pp, const float* pr, const float* eps_in, unsigned long long seed, const unsigned long long* seed_dev,
+                        int B, int P, float min_std, float beta, float mix, int nseg, const float* dplan, const float* gout, float* dpp,
+                        float* dpr, void* stream);
 /* CLIP-style symmetric contrastive loss on projected features im/tx [M][32] restricted to rows with
  * use[m] != 0 (hulc2.py:472-508); dscale = d loss / d logit_scale.  out[2] = {loss, number of rows with use != 0 (1 when none): the weight
  * `batch_size["aux_lang"]` the step logs the loss with, hulc2.py:391-394 — a device value, no host synchronisation}. */
