@@ -40,22 +40,11 @@ def _conv_wgrad(dz: "kn.Grid", x: "kn.Grid", w: torch.Tensor, cin: int):
     """dW (Cout, cin, 3, 3) (+)= nine products dZ^T X[. + off_t] over the grid rows, written straight into the OIHW layout (col_mul = 9):
     into the trainer's gradient arena at the end of the pass when a sink is registered, else into a fresh tensor handed to autograd"""
     cout = dz.C
-    sink = gradsink.get(w)
-    out = sink.view(cout, cin * 9) if sink is not None else torch.empty(cout, cin * 9, dtype=torch.float32, device=dz.rows.device)
-    acc = sink is not None and not gradsink.first_write(w)
+    out, acc, ret = gradsink.dest(w, (cout, cin * 9), dz.rows)
     A = dz.rows[dz.guard:dz.guard + dz.Rpad]
     B = x.rows[x.guard:x.guard + x.Rpad]                               # tap u reads it shifted by (dy (W + 2) + dx) rows: inside the zero guards
-    kn.wgrad(A, B, out, cout, cin, x.Rpad, cout, x.C, cin * 9, accumulate=acc, defer=sink is not None, col_mul=9, conv_taps_wp=x.W + 2)
-    return None if sink is not None else out.view(cout, cin, 3, 3)
-
-
-def _vec_grad(param, like):
-    """(destination, accumulate flag, tensor to return to autograd or None) of a 1-D parameter gradient"""
-    sink = gradsink.get(param)
-    if sink is None:
-        t = torch.empty_like(param, dtype=torch.float32)                  # (same shape as the parameter: (1, D) weights included)
-        return t, False, t
-    return sink, not gradsink.first_write(param), None
+    kn.wgrad(A, B, out, cout, cin, x.Rpad, cout, x.C, cin * 9, accumulate=acc, defer=ret is None, col_mul=9, conv_taps_wp=x.W + 2)
+    return None if ret is None else ret.view(cout, cin, 3, 3)
 
 
 def _eval_bn(gamma, beta, run_mean, run_var, eps: float = 1e-5):
@@ -124,24 +113,17 @@ class AffDecoderLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dloss, _dlogits):
         saved, logit0, lse, p0i, blocks, head_w, head_b, N, out_hw = ctx.saved
-        dev = logit0.device
         chans = block_channels()
         grads_blocks: List = [None] * 30
         up = dloss.reshape(1).to(torch.float32).contiguous()
         g = kn.pixel_ce_bwd_rows(logit0, p0i, lse, up, N, out_hw, out_hw)              # (softmax - onehot) / (N H W) per grid row, fp32
         last = saved[-1][6]
         # head: dW[ci][t] = sum_r g[r] x[r + off_t][ci]; the bias gradient is the sum of (softmax - onehot) = 0
-        sink_h = gradsink.get(head_w)
-        ci = head_w.shape[1]
-        dwh = sink_h.view(-1) if sink_h is not None else torch.empty(ci * 9, dtype=torch.float32, device=dev)
-        kn.head_conv_wgrad(last, g, dwh, accumulate=sink_h is not None and not gradsink.first_write(head_w))
-        d_head_w = None if sink_h is not None else dwh.view(1, ci, 3, 3)
-        d_head_b = torch.zeros_like(head_b, dtype=torch.float32)
-        sink_hb = gradsink.get(head_b)
-        if sink_hb is not None:
-            if gradsink.first_write(head_b):
-                sink_hb.zero_()
-            d_head_b = None
+        dwh, acc, d_head_w = gradsink.dest(head_w, None, logit0)
+        kn.head_conv_wgrad(last, g, dwh.view(-1), accumulate=acc)
+        dbh, acc, d_head_b = gradsink.dest(head_b, None, logit0)
+        if not acc:
+            dbh.zero_()
         dO2 = kn.head_conv_dgrad(g, head_w.detach().contiguous(), N, out_hw, out_hw, last.C)
         dgs = [None, None, None]
         want_maps = ctx.needs_input_grad[6:11]                          # (f_stem, f1, f2, f3, f4)
@@ -151,16 +133,12 @@ class AffDecoderLossFn(torch.autograd.Function):
             cin, cs, cout = chans[i]
             X, Y1, bn1, O1, Y2, bn2, O2, x_map, x_str, g, hi, s = saved[i]
             w1, ga1, be1, w2, ga2, be2 = blocks[6 * i:6 * i + 6]
-            d_ga2, a1, r1 = _vec_grad(ga2, bn2)
-            d_be2, a2, r2 = _vec_grad(be2, bn2)
-            DZ2 = kn.grid_bn_relu_bwd(dO2, O2, Y2, bn2, d_ga2, d_be2, accumulate=a1 or a2)
-            grads_blocks[6 * i + 4], grads_blocks[6 * i + 5] = r1, r2
+            (d_ga2, d_be2), acc, grads_blocks[6 * i + 4:6 * i + 6] = gradsink.joint((ga2, be2), None, bn2)
+            DZ2 = kn.grid_bn_relu_bwd(dO2, O2, Y2, bn2, d_ga2, d_be2, accumulate=acc)
             grads_blocks[6 * i + 3] = _conv_wgrad(DZ2, O1, w2, cout)
             dO1, _ = kn.gridconv3x3(DZ2, _dgrad_w(w2), cout, flip=True)
-            d_ga1, a1, r1 = _vec_grad(ga1, bn1)
-            d_be1, a2, r2 = _vec_grad(be1, bn1)
-            DZ1 = kn.grid_bn_relu_bwd(dO1, O1, Y1, bn1, d_ga1, d_be1, accumulate=a1 or a2)
-            grads_blocks[6 * i + 1], grads_blocks[6 * i + 2] = r1, r2
+            (d_ga1, d_be1), acc, grads_blocks[6 * i + 1:6 * i + 3] = gradsink.joint((ga1, be1), None, bn1)
+            DZ1 = kn.grid_bn_relu_bwd(dO1, O1, Y1, bn1, d_ga1, d_be1, accumulate=acc)
             grads_blocks[6 * i] = _conv_wgrad(DZ1, X, w1, cin + cs)
             need_small = i > 0 or want_maps[4]                          # block 0's input is the trunk's last map
             need_dg = i < 3
@@ -200,7 +178,7 @@ class DepthNllFn(torch.autograd.Function):
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         dst, rets, mask = [], [], 0
         for bit, p in zip((1, 2, 4, 8), ctx.params):
-            d, acc, r = _vec_grad(p, None)
+            d, acc, r = gradsink.dest(p, None, x)
             dst.append(d); rets.append(r)
             mask |= bit if acc else 0
         kn.depth_nll_bwd(x, w_mu.detach().contiguous(), w_s.detach().contiguous(), mu, sigma, ls, t, dloss.reshape(1).float().contiguous(), dx,

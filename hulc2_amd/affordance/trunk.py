@@ -151,30 +151,11 @@ class TrunkStemFn(torch.autograd.Function):
         S = ctx.stem
         dp = kn.maxpool_nhwc_bwd(S.y, da0, torch.empty(S.y.shape, dtype=adt, device=dev), n, S.oh, S.ow, 64, 3, 2, 1)
 
-        def vec(param):                                        # (destination, accumulate, what autograd gets)
-            sink = gradsink.get(param)
-            if sink is None:
-                t = torch.empty(param.shape, dtype=torch.float32, device=dev)
-                return t, False, t
-            return sink, not gradsink.first_write(param), None
-        dga, acc_g, ret_g = vec(g_stem)
-        dbe, acc_b, ret_b = vec(b_stem)
-        if acc_g != acc_b:                                     # one flag for both: make the one that must not accumulate zero first
-            (dga if not acc_g else dbe).zero_()
-            acc_g = acc_b = True
-        dz, _ = bn_bwd(dp, S, relu=True, dgamma=dga, dbeta=dbe, acc=acc_g)
+        (dga, dbe), acc, (ret_g, ret_b) = gradsink.joint((g_stem, b_stem), None, da0)    # one launch, one flag for both
+        dz, _ = bn_bwd(dp, S, relu=True, dgamma=dga, dbeta=dbe, acc=acc)
         # d conv1.weight: 7 x 7 stride 2 over the zero-padded NHWC-8 input (channels 3..7 are zero: their gradient columns are dropped)
         xp = kn.nhwc_scatter(ctx.a_in, torch.empty((n, h + 6, w + 6, 8), dtype=ctx.a_in.dtype, device=dev), 1, 3)
         dw8 = torch.empty((64, 8 * 49), dtype=torch.float32, device=dev)
         kn.conv2d_bwd_weight(xp, dz, dw8, None, n, h + 6, w + 6, 8, 64, 7, 7, 2, False, dw_oihw=True)
-        dw = dw8.view(64, 8, 7, 7)[:, :3]
-        sink = gradsink.get(w_stem)
-        if sink is not None:
-            if gradsink.first_write(w_stem):
-                sink.copy_(dw)
-            else:
-                sink.add_(dw)
-            ret_w = None
-        else:
-            ret_w = dw.contiguous()
-        return None, ret_w, ret_g, ret_b, None
+        ret_w = gradsink.deliver(w_stem, dw8.view(64, 8, 7, 7)[:, :3])
+        return None, (None if ret_w is None else ret_w.contiguous()), ret_g, ret_b, None

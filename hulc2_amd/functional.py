@@ -147,16 +147,11 @@ def _mlp_backward(x2, acts, params, relus, drops, g, need_x, chain, gs=None):
         W = params[2 * i]
         N, K = W.shape
         inp = x2 if i == 0 else acts[i - 1]
-        sw, sb = gradsink.get(W), gradsink.get(params[2 * i + 1])
-        dW = sw if sw is not None else _f32(N, K, like=g)
-        db = sb if sb is not None else _f32(N, like=g)
-        acc_w = sw is not None and not gradsink.first_write(W)
-        acc_b = sb is not None and not gradsink.first_write(params[2 * i + 1])
+        dW, acc_w, grads[2 * i] = gradsink.dest(W, None, g)
+        db, acc_b, grads[2 * i + 1] = gradsink.dest(params[2 * i + 1], None, g)
         # dW (+)= g^T inp, db (+)= column sums of g: part of the pass's grouped weight-gradient launch when both land in the arena
         kn.wgrad(g, inp, dW, N, K, M, g.stride(0), inp.stride(0), K, accumulate=acc_w, rowsum=db, rowsum_accumulate=acc_b,
-                 defer=sw is not None and sb is not None)
-        grads[2 * i] = None if sw is not None else dW          # written straight into the gradient arena
-        grads[2 * i + 1] = None if sb is not None else db
+                 defer=grads[2 * i] is None and grads[2 * i + 1] is None)
         if (i - 1) in gs:
             continue                                       # produced by the chain launch
         if i > 0 or need_x:
@@ -278,36 +273,25 @@ class FlattenLinearFn(torch.autograd.Function):
         sw, sb = gradsink.get(W), gradsink.get(b)
         if sw is not None and sb is not None and kn.wgrad_group_ok(g, x2, sw, O, K, N, O, K, K):
             # straight into the arena with the parameter's (c, h*w) column order: one item of the pass's grouped weight-gradient launch
-            kn.wgrad(g, x2, sw.view(O, K), O, K, N, O, K, K, accumulate=not gradsink.first_write(W), rowsum=sb,
-                     rowsum_accumulate=not gradsink.first_write(b), defer=True, col_perm=C)
-            dW = db = None
+            (dW, acc_w, rW), (db, acc_b, rb) = gradsink.dest(W, (O, K), g), gradsink.dest(b, None, g)
+            kn.wgrad(g, x2, dW, O, K, N, O, K, K, accumulate=acc_w, rowsum=db, rowsum_accumulate=acc_b, defer=True, col_perm=C)
         else:
             dWh = _f32(O, K, like=g)                                   # (h, w, c) column order
-            db = sb if sb is not None else _f32(O, like=g)
-            acc_b = sb is not None and not gradsink.first_write(b)
+            db, acc_b, rb = gradsink.dest(b, None, g)
             fused = kn.gemm_fuses_rowsum(O, False)
             kn.gemm(g, x2, dWh, O, K, N, O, K, K, a_kmajor=False, b_kmajor=False, rowsum=db if fused else None, rowsum_accumulate=acc_b)
             if not fused:
                 kn.colsum(g, N, O, O, db, accumulate=acc_b)
-            src = dWh.view(O, K // C, C).transpose(1, 2)                # -> the parameter's (c, h*w) order
-            if sw is not None:
-                dst = sw.view(O, C, K // C)
-                if gradsink.first_write(W):
-                    dst.copy_(src)
-                else:
-                    dst.add_(src)
-                dW = None
-            else:
-                dW = src.reshape(O, K)
-            if sb is not None:
-                db = None
+            rW = gradsink.deliver(W, dWh.view(O, K // C, C).transpose(1, 2))       # -> the parameter's (c, h*w) order
+            if rW is not None:
+                rW = rW.reshape(O, K)
         da = None
         if ctx.needs_input_grad[0]:
             # in the activation's own storage type: autograd would otherwise cast the 2048 x 3136 gradient in a launch of its own
             da = torch.empty(N, K, dtype=ctx.a_dtype, device=g.device)
             kn.gemm(g, weight_operand(W, "hwc_t", chw=(C, ctx.ashape[1], ctx.ashape[2])), da, N, K, O, O, O, K, mask=x2, ld_mask=K, mask_scale=1.0)   # x (a > 0): conv3's ReLU
             da = da.view(ctx.ashape)
-        return da, dW, db, None
+        return da, rW, rb, None
 
 
 def flatten_linear_relu(a_nhwc, W, b):
@@ -351,7 +335,7 @@ class Mlp2RowsFn(torch.autograd.Function):
         kn.mlp2_rows_bwd(x, dy, weight_operand(W1), b1, weight_operand(W1, "t"), weight_operand(W2, "t"), dx, h, dh)
         ret = []
         for left, right, W, b, M, N in ((dh, x, W1, b1, H, 128), (dy, h, W2, b2, OUT, H)):
-            (dW, a1, rW), (db, a2, rb) = _sink_or_new(W, (M, N), dy), _sink_or_new(b, (M,), dy)
+            (dW, a1, rW), (db, a2, rb) = gradsink.dest(W, (M, N), dy), gradsink.dest(b, (M,), dy)
             kn.wgrad(left, right, dW, M, N, T, M, N, N, accumulate=a1, rowsum=db, rowsum_accumulate=a2, defer=rW is None and rb is None)
             ret += [rW, rb]
         return (dx, *ret, None)
@@ -547,14 +531,8 @@ class ConvStackFn(torch.autograd.Function):
         grads_w, grads_b = [None] * 3, [None] * 3
         for li in (2, 1, 0):
             h, w_, cin, cout, k, s, nchw = dims[li]
-            sw, sb = gradsink.get(ctx.conv_w[li]), gradsink.get(ctx.conv_b[li])
-            sunk = sw is not None and sb is not None      # the reduce pass writes OIHW straight into the gradient arena
-            dw = sw.view(cout, cin * k * k) if sunk else _f32(cout, cin * k * k, like=g)
-            db = sb if sunk else _f32(cout, like=g)
-            acc = sunk
-            if sunk:                                     # dW and db leave one launch: one flag for both
-                fw, fb = gradsink.first_write(ctx.conv_w[li]), gradsink.first_write(ctx.conv_b[li])
-                acc = not (fw and fb)
+            # dW and db leave one launch: one flag for both (sunk: the reduce pass writes OIHW straight into the gradient arena)
+            (dw, db), acc, (rw, grads_b[li]) = gradsink.joint((ctx.conv_w[li], ctx.conv_b[li]), ((cout, cin * k * k), None), g)
             if li == 0:                                  # per input tensor: the second one accumulates
                 off = 0
                 pad, shifts, indices = ctx.aug
@@ -575,8 +553,7 @@ class ConvStackFn(torch.autograd.Function):
                         off += n
             else:
                 kn.conv2d_bwd_weight(inputs[li], g, dw, db, N, h, w_, cin, cout, k, k, s, nchw, dw_oihw=True, accumulate=acc)
-            grads_w[li] = None if sunk else dw.view(cout, cin, k, k)
-            grads_b[li] = None if sunk else db
+            grads_w[li] = None if rw is None else rw.view(cout, cin, k, k)
             if li > 0:
                 inp = inputs[li]
                 wt = weight_operand(weights[li], "ihwo")
@@ -667,19 +644,13 @@ class LayerNormFn(torch.autograd.Function):
         dy2 = _c(dy.reshape(R, D))
         dpre = _f32(R, D, like=dy2)
         do = _f32(R, D, like=dy2) if (has_o and drop_p > 0) else None
-        sg, sb = gradsink.get(gamma), gradsink.get(ctx.beta)
-        sunk = sg is not None and sb is not None                  # straight into the gradient arena (no AccumulateGrad adds)
-        dg, db = (sg, sb) if sunk else (_f32(D, like=dy2), _f32(D, like=dy2))
-        acc = sunk
-        if sunk:
-            fg, fb = gradsink.first_write(gamma), gradsink.first_write(ctx.beta)
-            acc = not (fg and fb)
+        (dg, db), acc, (rg, rb) = gradsink.joint((gamma, ctx.beta), None, dy2)      # sunk: straight into the gradient arena (no AccumulateGrad adds)
         kn.layernorm_bwd(dy2, pre, mean, rstd, gamma, R, D, dpre, do, drop_p, seed, dg, db, accumulate_params=acc)
         dx = dpre.reshape(shape)
         d_o = None
         if has_o:
             d_o = (do if do is not None else dpre).reshape(shape)
-        return dx, d_o, (None if sunk else dg), (None if sunk else db), None, None, None
+        return dx, d_o, rg, rb, None, None, None
 
 
 def layer_norm(x, gamma, beta, eps=1e-5):
@@ -741,16 +712,10 @@ class LayerNormCatFn(torch.autograd.Function):
             x, gamma, beta = xs[i], gammas[i], ctx.betas[i]
             r, d = x.shape
             dx = _f32(r, d, like=dyf)
-            sg, sb = gradsink.get(gamma), gradsink.get(beta)
-            sunk = sg is not None and sb is not None
-            dg, db = (sg, sb) if sunk else (_f32(d, like=dyf), _f32(d, like=dyf))
-            acc = sunk
-            if sunk:
-                fg, fb = gradsink.first_write(gamma), gradsink.first_write(beta)
-                acc = not (fg and fb)
+            (dg, db), acc, rets = gradsink.joint((gamma, beta), None, dyf)
             kn.layernorm_bwd_ld(dyf[offs[i]:], ld, x, stats[2 * i], stats[2 * i + 1], gamma, r, d, dx, dg, db, accumulate_params=acc)
             dxs.append(dx.reshape(shapes[i]))
-            dps += [None if sunk else dg, None if sunk else db]
+            dps += rets
         return (None, None, None, *dxs, *dps)
 
 
@@ -884,6 +849,24 @@ class GaussKLFn(torch.autograd.Function):
 # ------------------------------------------------------------------------------------------------
 # transformer pieces
 # ------------------------------------------------------------------------------------------------
+def _pos_table_grad(demb, pos, pshape, pos_ids):
+    """gradient of the position table (pshape) from demb (B, S, D), the gradient of emb + pos[pos_ids]: -> value for autograd.
+    pos: the table when pos_ids is arange(S) and its sink may take the gradient, else None"""
+    B, S, D = demb.shape
+    if pos is not None and gradsink.get(pos) is not None:
+        # rows 0 .. S-1 of the table's gradient = the sum over the batch, written (first writer of the step) or added in place
+        sink, acc, _ = gradsink.dest(pos, None, demb)
+        kn.colsum(demb, B, S * D, S * D, sink[:S].view(-1), accumulate=acc)
+        if not acc and pshape[0] > S:
+            sink[S:].zero_()
+        return None
+    dsum = _f32(S, D, like=demb)
+    kn.colsum(demb, B, S * D, S * D, dsum)                   # sum over the batch
+    dpos = torch.zeros(pshape, dtype=torch.float32, device=demb.device)
+    dpos.index_copy_(0, pos_ids, dsum)                       # row placement by (unique) position id: a copy, no arithmetic
+    return dpos
+
+
 @_scoped
 class AddPosFn(torch.autograd.Function):
     """dropout(x + pos[position_ids]) — plan_recognition_net.py:133-136,142.  identity: position_ids is arange(S) (what the reference passes):
@@ -909,19 +892,7 @@ class AddPosFn(torch.autograd.Function):
             kn.dropout_bwd(dy, dx, dy.numel(), drop_p, seed)
         else:
             dx = dy
-        sink = gradsink.get(ctx.pos) if ctx.pos is not None else None
-        if sink is not None and dx.dtype == torch.float32:
-            # rows 0 .. S-1 of the table's gradient = the sum over the batch, written (first writer of the step) or added in place
-            first = gradsink.first_write(ctx.pos)
-            kn.colsum(dx, B, S * D, S * D, sink[:S].view(-1), accumulate=not first)
-            if first and pshape[0] > S:
-                sink[S:].zero_()
-            return dx, None, None, None, None, None
-        dsum = _f32(S, D, like=dy)
-        kn.colsum(dx, B, S * D, S * D, dsum)                 # sum over the batch
-        dpos = torch.zeros(pshape, dtype=torch.float32, device=dy.device)
-        dpos.index_copy_(0, pos_ids, dsum)                   # row placement by (unique) position id: a copy, no arithmetic
-        return dx, dpos, None, None, None, None
+        return dx, _pos_table_grad(dx, ctx.pos if dx.dtype == torch.float32 else None, pshape, pos_ids), None, None, None, None
 
 
 @_scoped
@@ -988,28 +959,13 @@ class FFNFn(torch.autograd.Function):
         x2, W1, b1, W2, b2 = ctx.saved_tensors
         shape, T, D, FF, drop_p, seed = ctx.meta
         df2 = _c(df.reshape(T, D))
-        sinks = [gradsink.get(t) for t in (W1, b1, W2, b2)]
-        sunk = all(s is not None for s in sinks)
-        dW1, db1, dW2, db2 = sinks if sunk else (_f32(FF, D, like=df2), _f32(FF, like=df2), _f32(D, FF, like=df2), _f32(D, like=df2))
+        (dW1, db1, dW2), acc, rets = gradsink.joint((W1, b1, W2), None, df2)
+        db2, acc_b2, rb2 = gradsink.dest(b2, None, df2)
         dx = _f32(T, D, like=df2)
-        acc, acc_b2 = sunk, sunk
-        if sunk:
-            f = [gradsink.first_write(t) for t in (W1, b1, W2, b2)]
-            acc, acc_b2 = not all(f[:3]), not f[3]
         kn.ffn_bwd(x2, df2, weight_operand(W1), b1, weight_operand(W1, "t"), weight_operand(W2, "t"), T, D, FF, drop_p, seed, dx, dW1, db1, dW2,
                    accumulate_params=acc)
         kn.colsum(df2, T, D, D, db2, accumulate=acc_b2)
-        g = (None, None, None, None) if sunk else (dW1, db1, dW2, db2)
-        return (dx.reshape(shape), *g, None, None)
-
-
-def _sink_or_new(param, shape, like):
-    """-> (tensor the kernels write, accumulate flag, None-or-tensor to hand back to autograd)"""
-    sk = gradsink.get(param)
-    if sk is None:
-        t = _f32(*shape, like=like)
-        return t, False, t
-    return sk.view(*shape), not gradsink.first_write(param), None
+        return (dx.reshape(shape), *rets, rb2, None, None)
 
 
 @_scoped
@@ -1050,22 +1006,17 @@ class TxlLayerFn(torch.autograd.Function):
         FF = w1.shape[0]
         dy2 = _c(dy.reshape(T, E))
         like = dy2
-        outs = {}
-
-        def sink(name, param, shape):
-            t, acc, ret = _sink_or_new(param, shape, like)
-            outs[name] = ret
-            return t, acc
         # LayerNorm2 backward: dpre2 = gradient of y1 through the residual, df = gradient of the feed-forward output
         dpre2 = _f32(T, E, like=like)
         df = _f32(T, E, like=like) if drop_p > 0 else dpre2
-        (dg2, a1), (db2n, a2) = sink("g2", g2, (E,)), sink("be2", be2, (E,))
-        kn.layernorm_bwd(dy2, pre2, mean2, rstd2, g2, T, E, dpre2, df if drop_p > 0 else None, drop_p, seed + 15, dg2, db2n, accumulate_params=a1 or a2)
+        (dg2, db2n), acc, r_ln2 = gradsink.joint((g2, be2), None, like)
+        kn.layernorm_bwd(dy2, pre2, mean2, rstd2, g2, T, E, dpre2, df if drop_p > 0 else None, drop_p, seed + 15, dg2, db2n, accumulate_params=acc)
         # feed-forward backward: weight gradients complete, input gradient left as FF / 128 slice partials
-        (dW1, c1), (db1, c2), (dW2, c3), (db2, c4) = sink("w1", w1, (FF, E)), sink("b1", b1, (FF,)), sink("w2", w2, (E, FF)), sink("b2", b2, (E,))
+        (dW1, db1, dW2), acc, r_ffn = gradsink.joint((w1, b1, w2), None, like)
+        db2, acc_b2, r_b2 = gradsink.dest(b2, None, like)
         ws = kn.ffn_bwd(y1, df, weight_operand(w1), b1, weight_operand(w1, "t"), weight_operand(w2, "t"), T, E, FF, drop_p, seed + 13, None, dW1, db1,
-                        dW2, accumulate_params=c1 or c2 or c3)
-        kn.colsum(df, T, E, E, db2, accumulate=c4)
+                        dW2, accumulate_params=acc)
+        kn.colsum(df, T, E, E, db2, accumulate=acc_b2)
         # attention half backward
         dx = _f32(T, E, like=like)
         d_o = torch.empty(T, E, dtype=torch.bfloat16, device=like.device)
@@ -1073,17 +1024,14 @@ class TxlLayerFn(torch.autograd.Function):
         lnp = _f32(B, 2, E, like=like)
         kn.txl_attn_bwd(x2, weight_operand(w_in), weight_operand(w_in, "t"), weight_operand(w_out, "t"), b_in, g1, 1e-5, B, S, H, drop_p, seed + 11,
                         seed + 12, pre1, mean1, rstd1, dpre2, ws, FF // 128, T * E, dx, d_o, dqkv, lnp)
-        (dg1, e1), (db1n, e2) = sink("g1", g1, (E,)), sink("be1", be1, (E,))
-        kn.ln_partial_reduce(lnp, B, E, dg1, db1n, accumulate=e1 or e2)
+        (dg1, db1n), acc, r_ln1 = gradsink.joint((g1, be1), None, like)
+        kn.ln_partial_reduce(lnp, B, E, dg1, db1n, accumulate=acc)
         # weight gradients of the two projections over all tokens; the row sums of the left operand are the bias gradients
-        (dWin, f1), (dbin, f2) = sink("w_in", w_in, (3 * E, E)), sink("b_in", b_in, (3 * E,))
-        kn.wgrad(dqkv, x2, dWin, 3 * E, E, T, 3 * E, E, E, accumulate=f1, rowsum=dbin, rowsum_accumulate=f2,
-                 defer=outs["w_in"] is None and outs["b_in"] is None)
-        (dWo, h1), (dbo, h2) = sink("w_out", w_out, (E, E)), sink("b_out", b_out, (E,))
-        kn.wgrad(d_o, ctxb, dWo, E, E, T, E, E, E, accumulate=h1, rowsum=dbo, rowsum_accumulate=h2,
-                 defer=outs["w_out"] is None and outs["b_out"] is None)
-        g = [outs[k] for k in ("w_in", "b_in", "w_out", "b_out", "w1", "b1", "w2", "b2", "g1", "be1", "g2", "be2")]
-        return (dx.reshape(xshape), None, None, None, None, None, *g)
+        (dWin, f1, r_win), (dbin, f2, r_bin) = gradsink.dest(w_in, None, like), gradsink.dest(b_in, None, like)
+        kn.wgrad(dqkv, x2, dWin, 3 * E, E, T, 3 * E, E, E, accumulate=f1, rowsum=dbin, rowsum_accumulate=f2, defer=r_win is None and r_bin is None)
+        (dWo, h1, r_wo), (dbo, h2, r_bo) = gradsink.dest(w_out, None, like), gradsink.dest(b_out, None, like)
+        kn.wgrad(d_o, ctxb, dWo, E, E, T, E, E, E, accumulate=h1, rowsum=dbo, rowsum_accumulate=h2, defer=r_wo is None and r_bo is None)
+        return (dx.reshape(xshape), None, None, None, None, None, r_win, r_bin, r_wo, r_bo, *r_ffn, r_b2, *r_ln1, *r_ln2)
 
 
 def _txl_fused_ok(x, p: dict, S: int, nhead: int) -> bool:
@@ -1197,47 +1145,26 @@ class TxlBlockFn(torch.autograd.Function):
         demb = _f32(B, S, E, like=like)
         d = kn.txl_block_desc(emb, pos, pos_ids, B, S, H, FF, drop_p, seed, 1e-5, recs, dpooled=dpooled, demb=demb)
         kn.txl_block_bwd(d, B, S, H, E, FF, L, share=ctx.share)
-        grads = []
-        rets = []
+        grads = [None] * (12 * L)                           # per layer in _TXL_KEYS order
         dgs, dbs, accs = [], [], []
         for li in range(L):
-            w_in, b_in, w_out, b_out, w1, b1, w2, b2, g1, be1, g2, be2 = params[12 * li:12 * li + 12]
-            ret = {}
-            rets.append(ret)
-            for gm, bt, kg, kb in ((g1, be1, "g1", "be1"), (g2, be2, "g2", "be2")):
-                (dg, a1, ret[kg]), (db, a2, ret[kb]) = _sink_or_new(gm, (E,), like), _sink_or_new(bt, (E,), like)
-                dgs.append(dg); dbs.append(db); accs.append(a1 or a2)
+            for j in (8, 10):                               # (g1, be1), (g2, be2): one flag per LayerNorm
+                k = 12 * li + j
+                (dg, db), acc, grads[k:k + 2] = gradsink.joint(params[k:k + 2], None, like)
+                dgs.append(dg); dbs.append(db); accs.append(acc)
         kn.ln_partial_reduce_multi(lnp, B, E, dgs, dbs, accs)
         for li in range(L):
-            w_in, b_in, w_out, b_out, w1, b1, w2, b2, g1, be1, g2, be2 = params[12 * li:12 * li + 12]
+            w_in, b_in, w_out, b_out, w1, b1, w2, b2 = params[12 * li:12 * li + 8]
             o, xin, y1, ctxb = outs[li]
-            ret = rets[li]
-
-            def sink(name, param, shape):
-                t, acc, r = _sink_or_new(param, shape, like)
-                ret[name] = r
-                return t, acc
             # dW = (left operand)^T (right operand) over all T tokens, bias gradient = the left operand's column sums
-            for left, right, W, bias, kw, kb_, M, N in ((o["dqkv"], xin, w_in, b_in, "w_in", "b_in", 3 * E, E), (o["d_o"], ctxb, w_out, b_out, "w_out", "b_out", E, E),
-                                                        (o["dh"], y1, w1, b1, "w1", "b1", FF, E), (o["df"], o["h"], w2, b2, "w2", "b2", E, FF)):
-                (dW, f1), (dbias, f2) = sink(kw, W, (M, N)), sink(kb_, bias, (M,))
-                kn.wgrad(left, right, dW, M, N, T, M, N, N, accumulate=f1, rowsum=dbias, rowsum_accumulate=f2, defer=ret[kw] is None and ret[kb_] is None)
-            grads += [ret[k] for k in ("w_in", "b_in", "w_out", "b_out", "w1", "b1", "w2", "b2", "g1", "be1", "g2", "be2")]
+            for j, (left, right, W, bias, M, N) in enumerate(((o["dqkv"], xin, w_in, b_in, 3 * E, E), (o["d_o"], ctxb, w_out, b_out, E, E),
+                                                              (o["dh"], y1, w1, b1, FF, E), (o["df"], o["h"], w2, b2, E, FF))):
+                k = 12 * li + 2 * j
+                (dW, f1, grads[k]), (dbias, f2, grads[k + 1]) = gradsink.dest(W, None, like), gradsink.dest(bias, None, like)
+                kn.wgrad(left, right, dW, M, N, T, M, N, N, accumulate=f1, rowsum=dbias, rowsum_accumulate=f2,
+                         defer=grads[k] is None and grads[k + 1] is None)
         # the position table: rows pos_ids of its gradient = the sum of demb over the batch (AddPosFn.backward)
-        dpos = None
-        sk = gradsink.get(pos)
-        identity = ctx.needs_input_grad[1] and sk is not None and ctx.pos_identity
-        if ctx.needs_input_grad[1]:
-            if identity:
-                first = gradsink.first_write(pos)
-                kn.colsum(demb, B, S * E, S * E, sk[:S].view(-1), accumulate=not first)
-                if first and pos.shape[0] > S:
-                    sk[S:].zero_()
-            else:
-                dsum = _f32(S, E, like=like)
-                kn.colsum(demb, B, S * E, S * E, dsum)
-                dpos = torch.zeros(pos.shape, dtype=torch.float32, device=dev)
-                dpos.index_copy_(0, pos_ids, dsum)
+        dpos = _pos_table_grad(demb, pos if ctx.pos_identity else None, pos.shape, pos_ids) if ctx.needs_input_grad[1] else None
         return (demb if ctx.needs_input_grad[0] else None, dpos, None, None, None, None, *grads)
 
 
@@ -1414,26 +1341,20 @@ class DecoderRNNFn(torch.autograd.Function):
 
         def wgrad_t(d_feat0, d_tok0, z_feat0, z_tok0, ncols, param, bias):
             """the same as wgrad() on the transposed mirrors: rows of dT = delta features, rows of zT = input features, k = S*B tokens"""
-            sink, bsink = gradsink.get(param), gradsink.get(bias)
-            out = sink if sink is not None else torch.empty(Hd, ncols, **f32)
-            bout = bsink if bsink is not None else torch.empty(Hd, **f32)
+            (out, acc, ret), (bout, acc_b, bret) = gradsink.dest(param, None, dbuf), gradsink.dest(bias, None, dbuf)
             kn.gemm(d16t[d_feat0:, d_tok0 * B:], z16t[z_feat0:, z_tok0 * B:], out, Hd, ncols, M, ldt, ldt, ncols, a_kmajor=True, b_kmajor=True,
-                    accumulate=sink is not None and not gradsink.first_write(param), rowsum=bout,
-                    rowsum_accumulate=bsink is not None and not gradsink.first_write(bias))
-            return (None if sink is not None else out), (None if bsink is not None else bout)
+                    accumulate=acc, rowsum=bout, rowsum_accumulate=acc_b)
+            return ret, bret
 
         def wgrad(dlt, inp_rows, ncols, param, bias):
             """param.grad (+)= dlt^T inp_rows, bias.grad (+)= column sums of dlt (the row sums of the GEMM's A operand, fused into
             the same launch); straight into the gradient arena when the trainer registered sinks"""
-            sink, bsink = gradsink.get(param), gradsink.get(bias)
-            out = sink if sink is not None else torch.empty(Hd, ncols, **f32)
-            bout = bsink if bsink is not None else torch.empty(Hd, **f32)
-            acc_b = bsink is not None and not gradsink.first_write(bias)
+            (out, acc, ret), (bout, acc_b, bret) = gradsink.dest(param, None, dbuf), gradsink.dest(bias, None, dbuf)
             kn.gemm(dlt, inp_rows, out, Hd, ncols, M, 2 * Hd, 2 * Hd, ncols, a_kmajor=False, b_kmajor=False,
-                    accumulate=sink is not None and not gradsink.first_write(param), rowsum=bout if fuse_b else None, rowsum_accumulate=acc_b)
+                    accumulate=acc, rowsum=bout if fuse_b else None, rowsum_accumulate=acc_b)
             if not fuse_b:
                 kn.colsum(dlt, M, Hd, 2 * Hd, bout, accumulate=acc_b)
-            return (None if sink is not None else out), (None if bsink is not None else bout)
+            return ret, bret
 
         b_ih0, b_hh0, b_ih1, b_hh1 = ctx.biases
         # round 6, OPT-IN (HULC_WGRAD_FORK=1, native trainer only): the three 2048^3 recurrent weight gradients feed nothing downstream (they land in
@@ -1472,26 +1393,18 @@ class DecoderRNNFn(torch.autograd.Function):
         dc = dcs[:, Hd:]                                                            # (B, H) strided view, ld 2H
         kn.strided_seq_sum(d0, dc, B, S, Hd, 2 * Hd, B * 2 * Hd, 2 * Hd)            # dc = sum_t delta0_t
         wih0 = weight_operand(w_ih0)
-        s_ih0 = gradsink.get(w_ih0)
-        dw_ih0 = s_ih0 if s_ih0 is not None else torch.empty(Hd, Kin, **f32)
-        acc0 = s_ih0 is not None and not gradsink.first_write(w_ih0)     # three GEMMs, each the only writer of its column slice
-        kn.wgrad(dc, plan, dw_ih0, Hd, P, B, 2 * Hd, P, Kin, accumulate=acc0, defer=s_ih0 is not None)
-        sb_ih0 = gradsink.get(b_ih0)
-        db_ih0 = sb_ih0 if sb_ih0 is not None else torch.empty(Hd, **f32)
-        acc_b0 = sb_ih0 is not None and not gradsink.first_write(b_ih0)
+        dw_ih0, acc0, r_ih0 = gradsink.dest(w_ih0, None, dbuf)                       # three GEMMs, each the only writer of its column slice
+        kn.wgrad(dc, plan, dw_ih0, Hd, P, B, 2 * Hd, P, Kin, accumulate=acc0, defer=r_ih0 is None)
+        db_ih0, acc_b0, rb_ih0 = gradsink.dest(b_ih0, None, dbuf)
         if kn.wgrad_group_ok(d0w, emb_t, dw_ih0[:, P:P + E], Hd, E, M, 2 * Hd, E, Kin):
             kn.wgrad(d0w, emb_t, dw_ih0[:, P:P + E], Hd, E, M, 2 * Hd, E, Kin, accumulate=acc0, rowsum=db_ih0, rowsum_accumulate=acc_b0,
-                     defer=s_ih0 is not None and sb_ih0 is not None)
+                     defer=r_ih0 is None and rb_ih0 is None)
         else:
             kn.gemm(d0w, emb_t, dw_ih0[:, P:P + E], Hd, E, M, 2 * Hd, E, Kin, a_kmajor=False, b_kmajor=False, accumulate=acc0,
                     rowsum=db_ih0 if fuse_b else None, rowsum_accumulate=acc_b0)
             if not fuse_b:
                 kn.colsum(d0, M, Hd, 2 * Hd, db_ih0, accumulate=acc_b0)
-        if sb_ih0 is not None:
-            db_ih0 = None
-        kn.wgrad(dc, goal, dw_ih0[:, P + E:], Hd, G, B, 2 * Hd, G, Kin, accumulate=acc0, defer=s_ih0 is not None)
-        if s_ih0 is not None:                 # written straight into the gradient arena
-            dw_ih0 = None
+        kn.wgrad(dc, goal, dw_ih0[:, P + E:], Hd, G, B, 2 * Hd, G, Kin, accumulate=acc0, defer=r_ih0 is None)
         wih0_t = weight_operand(w_ih0, "t")                                         # (Kin, H): rows = input features, k-major
         dplan = torch.empty(B, P, **f32)
         kn.gemm(dc, wih0_t, dplan, B, P, Hd, 2 * Hd, Hd, P)
@@ -1504,7 +1417,7 @@ class DecoderRNNFn(torch.autograd.Function):
         else:
             demb = torch.zeros(B, S, Etot, **f32)
             demb[:, :, lo:hi] = demb_t.permute(1, 0, 2)
-        return (dplan, demb, dgoal, None, None, dw_ih0, dw_hh0, db_ih0, db_hh0, dw_ih1, dw_hh1, db_ih1, db_hh1, None, None)
+        return (dplan, demb, dgoal, None, None, r_ih0, dw_hh0, rb_ih0, db_hh0, dw_ih1, dw_hh1, db_ih1, db_hh1, None, None)
 
 
 @_scoped
@@ -1669,13 +1582,9 @@ class ClipLossFn(torch.autograd.Function):
         im, tx, use_u8, ls = ctx.saved_tensors
         M, D = im.shape
         dim, dtx = torch.empty_like(im), torch.empty_like(tx)
-        sink = gradsink.get(ctx.scale_param)
-        if sink is not None and gradsink.first_write(ctx.scale_param):
-            dscale, ret = sink.reshape(1), None            # the step's only writer: straight into the gradient arena (no AccumulateGrad add)
-        else:
-            dscale = _f32(1, like=im)
-            ret = dscale.reshape(())
-        kn.clip_loss_bwd(im, tx, use_u8, ls, M, D, _c(g.reshape(1)), dim, dtx, dscale, ctx.row0)
+        # the kernel only overwrites: as the step's first writer straight into the gradient arena (no AccumulateGrad add), else through autograd
+        dscale, _, ret = gradsink.dest(ctx.scale_param, None, im, overwrite_only=True)
+        kn.clip_loss_bwd(im, tx, use_u8, ls, M, D, _c(g.reshape(1)), dim, dtx, dscale.reshape(1), ctx.row0)
         return dim, dtx, None, ret, None
 
 

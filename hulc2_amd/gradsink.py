@@ -6,6 +6,21 @@ When the native trainer owns a flat gradient arena it registers each parameter's
 kernels (wgrad GEMM epilogue `accumulate`, column-sum kernels) then add straight into the slice and the autograd
 Function returns None for that parameter.  Only enabled when no per-parameter all-reduce hooks depend on
 AccumulateGrad (single GPU, or graph mode where the arena is reduced in one piece).
+
+Every backward asks for its gradient destinations through three functions and never spells the lookup out itself:
+
+  dest(param, shape, like)     one parameter, a flag of its own.  Sink registered and active: (sink.view(shape), not first_write(param), None).
+                               Else a fresh fp32 tensor, flag False, and the same tensor for autograd.  shape=None: the parameter's own shape.
+  joint(params, shapes, like)  several parameters behind ONE accumulate flag (one launch writes them all).  All sunk: views, every parameter
+                               marked as written; the flag is False when all are the step's first writes and True when none is.  Mixed: the
+                               first-write destinations are zeroed and the flag is True — a shared flag of False would overwrite what an
+                               earlier writer of this step left, and True without the zeroing would add onto the previous step's gradient,
+                               because the trainer stops zeroing a slice once its writers overwrite (first_write).  Not all sunk: fresh tensors
+                               for all, flag False, all handed to autograd, nothing marked.
+  deliver(param, value)        a gradient Python already holds (a temporary, a permuted view).  Sunk: sink.view_as(value) takes copy_ on a
+                               first write and add_ otherwise, autograd gets None.  Else `value` goes to autograd as it is.
+
+`get` stays for yes / no questions (is this parameter sunk?) that select a code path.
 """
 import weakref
 from typing import Dict, Optional, Tuple
@@ -108,6 +123,48 @@ def first_write(param: torch.Tensor) -> bool:
     first = k not in _written
     _written.add(k)
     return first and _overwrite
+
+
+def dest(param: torch.Tensor, shape, like: torch.Tensor, overwrite_only: bool = False):
+    """-> (tensor the kernel writes, accumulate flag, None-or-tensor to hand back to autograd).  overwrite_only: for a kernel without an
+    accumulate epilogue — the sink only as the step's first writer, else a fresh tensor (the parameter still counts as written)"""
+    sink = get(param)
+    if sink is not None:
+        acc = not first_write(param)
+        if not (acc and overwrite_only):
+            return (sink if shape is None else sink.view(shape)), acc, None
+    t = torch.empty(param.shape if shape is None else shape, dtype=torch.float32, device=like.device)
+    return t, False, t
+
+
+def joint(params, shapes, like: torch.Tensor):
+    """-> (tensors the launch writes, its ONE accumulate flag, values for autograd); shapes: one per parameter (None: its own) or None for all"""
+    shapes = shapes or [None] * len(params)
+    sinks = [get(p) for p in params]
+    if any(s is None for s in sinks):
+        ts = [torch.empty(p.shape if sh is None else sh, dtype=torch.float32, device=like.device) for p, sh in zip(params, shapes)]
+        return ts, False, ts
+    ts = [s if sh is None else s.view(sh) for s, sh in zip(sinks, shapes)]
+    first = [first_write(p) for p in params]
+    acc = not all(first)
+    if acc and any(first):                # mixed: the destinations that must not accumulate start from zero
+        for t, f in zip(ts, first):
+            if f:
+                t.zero_()
+    return ts, acc, [None] * len(params)
+
+
+def deliver(param: torch.Tensor, value: torch.Tensor):
+    """hands a finished gradient over: copied (first write) or added into the sink -> None, else -> value"""
+    sink = get(param)
+    if sink is None:
+        return value
+    dst = sink.view_as(value)
+    if first_write(param):
+        dst.copy_(value)
+    else:
+        dst.add_(value)
+    return None
 
 
 def written(param: torch.Tensor) -> bool:

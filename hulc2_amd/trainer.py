@@ -1059,7 +1059,7 @@ class ArenaTrainer:
     def _plan_partial_zero(self) -> None:
         """After a fully zeroed step: the arena slices NOT written through a gradient sink are the only ones the next steps need zeroed
         (autograd's `param.grad += g` lands there); sinks written by the backward kernels are overwritten by their first writer
-        (gradsink.first_write).  Neighbouring must-zero slices are merged across small written ones — zeroing a slice that is overwritten
+        (hulc2_amd/gradsink.py).  Neighbouring must-zero slices are merged across small written ones — zeroing a slice that is overwritten
         later is harmless, one fill launch per slice is not."""
         spans = []                                                 # arena ranges of fused groups whose single sink was written
         for pv, gv, off, shape in self.fused:

@@ -214,3 +214,49 @@ def test_shared_layer_at_two_row_counts_under_sinks():
         finally:
             gradsink.clear()
             gradsink.begin_step(False)
+
+
+def _shared_gamma_under_sinks(dev, D, forward):
+    """two LayerNorms that share `gamma` and own their `beta`s, sinks on all three: whichever of the two backward launches runs second finds
+    gamma written and its own beta not — one accumulate flag for both.  forward(x1, x2, gamma, beta1, beta2) -> a tensor"""
+    torch.manual_seed(17)
+    gamma, beta1, beta2 = (torch.nn.Parameter(torch.randn(D, device=dev)) for _ in range(3))
+    params = (gamma, beta1, beta2)
+    x1, x2 = torch.randn(8, D, device=dev), torch.randn(8, D, device=dev)
+    y = forward(x1, x2, *params).detach()
+    r = torch.randn(y.shape, device=dev)
+
+    def run():
+        (forward(x1, x2, *params) * r).sum().backward()
+        torch.cuda.synchronize()
+
+    run()                                              # no sinks: gradients come back through autograd
+    want = [p.grad.clone() for p in params]
+    for p in params:
+        p.grad = None
+    arena = torch.full((3 * D,), float("nan"), device=dev)
+    try:
+        for i, p in enumerate(params):
+            gradsink.register(p, arena[i * D:(i + 1) * D])
+        gradsink.begin_step(True)
+        run()
+        assert all(p.grad is None for p in params) and torch.isfinite(arena).all()
+        assert torch.equal(arena[D:2 * D], want[1]) and torch.equal(arena[2 * D:], want[2])      # the same kernel in the same order
+        got, w = arena[:D], want[0]                    # written twice: the bound of test_shared_layer_at_two_row_counts_under_sinks
+        assert (got - w).abs().max().item() <= 2e-2 * w.abs().max().item()
+        assert (got - w).norm().item() <= 5e-3 * w.norm().item()
+    finally:
+        gradsink.clear()
+        gradsink.begin_step(False)
+
+
+def test_shared_layernorm_weight_under_sinks():
+    _shared_gamma_under_sinks(_dev(), 128, lambda x1, x2, g, b1, b2: HF.layer_norm(x1, g, b1) + HF.layer_norm(x2, g, b2))
+
+
+def test_shared_layernorm_cat_weight_under_sinks():
+    def forward(x1, x2, g, b1, b2):
+        n1, n2 = torch.nn.LayerNorm(64), torch.nn.LayerNorm(64)
+        n1.weight, n1.bias, n2.weight, n2.bias = g, b1, g, b2
+        return HF.layer_norm_cat([x1, x2], [n1, n2], dim=-1)
+    _shared_gamma_under_sinks(_dev(), 64, forward)
