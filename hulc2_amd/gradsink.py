@@ -29,7 +29,7 @@ import torch
 
 _sinks: Dict[int, Tuple["weakref.ref", torch.Tensor, object]] = {}
 # Sinks registered with an `owner` are visible only while that owner is active (`with gradsink.active(owner):`).  The weight keeper of an
-# externally optimized model (ArenaTrainer(shadows_only=True, step_node=True)) registers its sinks that way: they exist for the forward and
+# externally optimized model (arena.WeightKeeper(model, step_node=True)) registers its sinks that way: they exist for the forward and
 # backward the step node runs (hulc2_amd/stepnode.py) and for nothing else — a user's own forward / backward through parts of the model
 # (validation with gradients, a probe of one encoder) gets its gradients from autograd as always.
 _active_owners: Dict[int, int] = {}

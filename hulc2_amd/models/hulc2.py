@@ -25,8 +25,10 @@ import torch.nn as nn
 
 from hulc2_amd import functional as HF
 from hulc2_amd import kernels as kn
+from hulc2_amd.arena import WeightKeeper
 from hulc2_amd.compat import LightningModule, instantiate
 from hulc2_amd.models.plan_encoders.plan_recognition_net import trunk_site
+from hulc2_amd.trainer import ArenaTrainer
 from hulc2_amd.utils.distributions import State
 
 logger = logging.getLogger(__name__)
@@ -155,7 +157,7 @@ class Hulc2(LightningModule):
         """Under an EXTERNAL optimizer (Lightning + torch.optim.Adam, hulc2/training.py:79-82) nobody maintains the kernel-side copies of the
         weights (bf16 shadows, transposed tiles, packed fragments, split-operand remainders, conv repacks): shadow.weight_operand re-derives
         each of them per parameter and layout with torch ops when the parameter's version has changed — ~200 small launches per step.  The
-        first training-mode step on a GPU without an ArenaTrainer therefore installs ArenaTrainer(shadows_only=True): the parameters move into
+        first training-mode step on a GPU without an ArenaTrainer therefore installs a WeightKeeper (hulc2_amd/arena.py): the parameters move into
         one arena (same Parameter objects, same values: optimizers, DDP and checkpoints are unaffected) and all copies are re-made by five
         launches whenever the optimizer has stepped.  bf16 arithmetic modes only; HULC_NO_AUTO_SHADOWS=1 keeps the lazy per-parameter path.
         Round 5: the keeper also owns the gradient arena of the step node (hulc2_amd/stepnode.py; HULC_NO_STEP_NODE=1: weight copies only).
@@ -167,10 +169,9 @@ class Hulc2(LightningModule):
         if tr is not None and tr.model is not self:               # (a deep copy of a model carries the original's weak reference along)
             tr = None
         if tr is None:
-            from ..trainer import ArenaTrainer
-            tr = self.__dict__["_hulc_shadow_keeper"] = ArenaTrainer(self, shadows_only=True,     # the model owns its keeper (a deepcopy of the
-                                                                     step_node=not os.environ.get("HULC_NO_STEP_NODE"))    # model gets None here and builds its own)
-        if getattr(tr, "shadows_only", False):
+            # the model owns its keeper (a deepcopy of the model gets None here and builds its own)
+            tr = self.__dict__["_hulc_shadow_keeper"] = WeightKeeper(self, step_node=not os.environ.get("HULC_NO_STEP_NODE"))
+        if not isinstance(tr, ArenaTrainer):
             tr.refresh_if_stale()
             return tr
         return None
@@ -180,7 +181,7 @@ class Hulc2(LightningModule):
         re-derived when a parameter has been written since (optimizer.step(), an EMA swap, weight surgery) — the arena views the kernels
         read carry no version of their own"""
         tr = self.__dict__.get("_hulc_shadow_keeper")
-        if tr is not None and getattr(tr, "shadows_only", False):
+        if tr is not None:                                        # (only ever a WeightKeeper: _keep_weight_copies_fresh put it there)
             ref = self.__dict__.get("_hulc_arena_trainer")
             if ref is not None and ref() is tr:
                 tr.refresh_if_stale()

@@ -28,9 +28,8 @@ from typing import Callable, Optional, Tuple
 import torch
 
 from . import kernels as kn
-from . import shadow
+from .arena import MAX_KERNEL_RANGES, arena_of
 from .compat import instantiate
-from .trainer import arena_of
 
 CONSTANT_SCHEDULE = "transformers.get_constant_schedule"
 
@@ -217,18 +216,9 @@ class _ArenaStep:
     def _skip_ranges(self, tr, idx) -> Optional[list]:
         """arena ranges of the parameters WITHOUT a gradient (all of them have never had one when this is called), neighbours merged; None
         when they do not fit the kernel's 8 ranges or start off a multiple of 4"""
-        have, ranges = set(idx), []
-        for i in range(len(tr.params)):
-            if i in have:
-                continue
-            a, b = tr.offsets[i], tr.offsets[i + 1] if i + 1 < len(tr.params) else tr.total
-            if ranges and ranges[-1][1] == a:
-                ranges[-1][1] = b
-            else:
-                ranges.append([a, b])
-        if len(ranges) > 8 or any(a % 4 for a, _ in ranges):
-            return None
-        return [(a, b) for a, b in ranges]
+        have = set(idx)
+        ranges = tr.span_ranges(i for i in range(len(tr.params)) if i not in have)
+        return None if len(ranges) > MAX_KERNEL_RANGES or any(a % 4 for a, _ in ranges) else ranges
 
     # ---- torch.optim.Optimizer interface --------------------------------------------------------------------------------------------------
     def _torch_step(self):
@@ -321,11 +311,7 @@ class _ArenaStep:
         self._fused_steps += 1
         kn.step_count_advance_if(self._dev_steps, found_inf)
         self._launch(tr, flat_g, arena[3:], g, grad_scale, found_inf, skip)
-        if tr.tiles_t is not None or tr.conv_table is not None:
-            kn.derive_copies(tr.flat_bf16, tr.flat_bf16_t, tr.tiles_t, tr.flat_p, tr.conv_shadow, tr.conv_table)
-        if tr.frag_idx is not None or tr.lo_frag_idx is not None:
-            kn.gather_chunks2(tr.flat_bf16, tr.flat_bf16_t, tr.frag_shadow, tr.frag_idx, tr.flat_lo, tr.lo_frag, tr.lo_frag_idx)
-        shadow.bump_epoch()
+        tr.derive_after_step()
         # the kernel wrote the arena directly: the parameters' version counters did not move, so the keeper's staleness check (sum of the
         # versions) sees nothing to refresh — which is right, its copies came out of the same launches
         self.fused_launches += 1

@@ -10,7 +10,7 @@ Here the whole step is ONE node whose inputs are the parameters:
   forward   runs the step's forward (`Hulc2._training_step_impl`) under `torch.enable_grad()` and keeps the inner loss,
   backward  runs the inner backward with the incoming gradient as its root — under a GradScaler that is the loss scale, a device scalar the
             first backward kernel multiplies by (a power of two: exact through every kernel) — while the keeper's gradient sinks are live
-            (trainer.ArenaTrainer(shadows_only=True, step_node=True)): the backward kernels write the weight gradients straight into one
+            (arena.WeightKeeper(model, step_node=True)): the backward kernels write the weight gradients straight into one
             gradient arena (one grouped launch, the first writer of a slice overwrites it), and the node hands the arena views to autograd
             as the parameters' gradients.  AccumulateGrad takes them without a copy; DDP's reducer hooks, `GradScaler.unscale_`,
             gradient clipping and any torch optimizer see ordinary `.grad` tensors.
@@ -98,7 +98,7 @@ class _GraphStepFn(torch.autograd.Function):
 
 
 class StepNode:
-    """the step node of one Hulc2 module under its shadows-only keeper (`Hulc2._step_node`)"""
+    """the step node of one Hulc2 module under its weight keeper (`Hulc2._step_node`)"""
 
     STASHED = 3                       # captured batch layouts kept beside the current one (least recently used goes first)
     EAGER_STEPS = 2                   # eager-node steps of a configuration before it is captured (the second one runs in sink-overwrite mode)

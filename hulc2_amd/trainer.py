@@ -17,9 +17,9 @@ backward -> DDP bucketed all-reduce -> Adam step).  Lightning is a third-party l
 from typing import Dict, List, Optional
 
 import contextlib
+import copy
 import ctypes
 import os
-import weakref
 
 import torch
 import torch.distributed as dist
@@ -27,28 +27,7 @@ import torch.distributed as dist
 from . import gradsink
 from . import kernels as kn
 from . import shadow
-
-# parameter arenas by the address of their storage (weak: an arena lives as long as its trainer / the model's keeper)
-_ARENAS: "weakref.WeakValueDictionary[int, ArenaTrainer]" = weakref.WeakValueDictionary()
-
-
-def arena_of(params) -> "Optional[ArenaTrainer]":
-    """the ArenaTrainer whose fp32 arena holds exactly these parameters (same objects, every one a view of the arena), else None"""
-    params = list(params)
-    if not params or params[0].device.type != "cuda":
-        return None
-    tr = _ARENAS.get(params[0].untyped_storage().data_ptr())
-    if tr is None or len(params) != len(tr.params):
-        return None
-    mine = {id(p) for p in tr.params}
-    base = tr.flat_p.data_ptr()
-    for p in params:
-        if id(p) not in mine:
-            return None
-    for p, off in zip(tr.params, tr.offsets):
-        if p.data_ptr() != base + off * 4 or p.dtype != torch.float32:
-            return None
-    return tr
+from .arena import MAX_KERNEL_RANGES, WeightKeeper, plan_arena, span_ranges
 
 
 class GradComm:
@@ -329,394 +308,100 @@ class GradBuckets:
         self.reset()
 
 
-class _LoadHook:
-    """load_state_dict post-hook of a model with a trainer: re-derive the kernel-side copies (ArenaTrainer._after_model_load)"""
+class ArenaTrainer(WeightKeeper):
+    """The native loop on the weight keeper's arenas: the gradient arena, the arena optimizer (moments, three update rules, the lr schedule,
+    the state dicts), the gradient exchange (GradComm / GradBuckets) and step() / capture() / replay()."""
 
-    def __init__(self, trainer):
-        self.ref = weakref.ref(trainer)
-
-    def __call__(self, module, incompatible_keys):
-        tr = self.ref()
-        if tr is not None and tr.model is module:
-            tr._after_model_load(module, incompatible_keys)
-
-    def __deepcopy__(self, memo):
-        return self
-
-
-class ArenaTrainer:
     def __init__(self, model: torch.nn.Module, lr: float = 2e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                  bucket_mb: int = 32, group=None, overlap: bool = True, comm_algo: Optional[str] = None, grad_payload: Optional[str] = None,
-                 force_comm: bool = False, shadows_only: bool = False, step_node: bool = False, optimizer: str = "adam",
-                 momentum: float = 0.0, dampening: float = 0.0, nesterov: bool = False, skip_params=()):
+                 force_comm: bool = False, optimizer: str = "adam", momentum: float = 0.0, dampening: float = 0.0, nesterov: bool = False,
+                 skip_params=()):
         """optimizer: the update rule of optimizer_step() — "adam" (torch.optim.Adam, L2 weight decay), "adamw" (torch.optim.AdamW, decoupled
         decay) or "sgd" (torch.optim.SGD with momentum / dampening / nesterov, L2 weight decay): conf/model/optimizer/{adam,adamw,sgd}.yaml;
         hulc2_amd.optim.trainer_kwargs_from_config maps such a config to these arguments.
         skip_params (adamw / sgd): parameters that never receive a gradient.  Their arena ranges (neighbours merged, at most 8) are left
         untouched by the step, as torch leaves a parameter without a gradient — weight decay would shrink them otherwise.
         force_comm: run the multi-rank control flow (split graphs, comm stream, collectives) even with a single rank in the process
-        group — how the RCCL path is exercised on a one-GPU box.
-        shadows_only (round 4): keep the KERNEL-SIDE COPIES of the parameters only — the parameters move into the fp32 arena, every derived
-        copy (bf16 shadow, transposed tiles, packed fragments, remainders, conv repacks) is allocated and registered, refresh_if_stale()
-        re-derives all of them with five launches when an external optimizer has stepped (any parameter's version counter moved) — and leave gradients, optimizer state and
-        communication to the caller (Lightning + torch.optim.Adam + torch DDP: hulc2/training.py:79-82).  Without it that loop re-derives every
-        copy per parameter and layout through torch ops (~200 small launches per step).
-        step_node (round 5, with shadows_only): the keeper also owns a GRADIENT arena and registers every parameter's slice as a gradient sink
-        that is live only inside the model's step node (hulc2_amd/stepnode.py: the whole forward + backward of a training step as ONE autograd
-        node, eager or as two replayed hipGraphs) — the backward kernels write weight gradients straight into the arena (grouped launch,
-        first writer overwrites), the node hands the arena views to autograd as the parameters' gradients.  No Adam moments, no communication."""
-        self.model = model
-        self.shadows_only = bool(shadows_only)
-        self.step_node = bool(step_node) and self.shadows_only
-        prev = model.__dict__.get("_hulc_arena_trainer")
-        prev = prev() if prev is not None else None
-        if prev is not None and prev.model is not model:       # (a deep copy of a model carries the original's weak reference along)
-            prev = None
-        if prev is not None:                               # an earlier trainer of this model: its load hook would keep re-homing weights into a
-            prev.close()                                   # dead arena (and keep that arena alive) — ADVICE r02
-        self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
+        group — how the RCCL path is exercised on a one-GPU box."""
         if optimizer not in ("adam", "adamw", "sgd"):
             raise ValueError(f"ArenaTrainer: optimizer {optimizer!r} is not one of 'adam', 'adamw', 'sgd'")
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")          # (torch.optim.SGD's own refusal)
+        self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
         self.optimizer, self.momentum, self.dampening, self.nesterov = optimizer, float(momentum), float(dampening), bool(nesterov)
         self.base_lr = lr                                  # what a schedule's factor multiplies (torch: the group's initial_lr)
-        self.params = [p for p in model.parameters() if p.requires_grad]
-        dev = self.params[0].device
-        # arena order = registration order, except that modules may ask for groups of parameters to sit back to back
-        # (fused_param_groups: the decoder's four heads become one (184, H) matrix view).  Fused views receive their gradient
-        # through a sink only, so they exist only when sinks do (not with per-parameter all-reduce hooks).
+        self.step_node = False                             # (the step node is the keeper's, under an external optimizer)
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.multi = self.world > 1 or (force_comm and dist.is_initialized())
-        use_sinks = dev.type == "cuda" and ((not self.multi or not overlap) and not self.shadows_only or self.step_node)
-        groups = []
-        for mod in model.modules():                     # views installed by an earlier trainer die with its arena
-            if getattr(mod, "fused_param_groups", None) is not None:
-                mod._fused = None
-        if use_sinks:
-            for mod in model.modules():
-                fn = getattr(mod, "fused_param_groups", None)
-                if fn is not None:
-                    groups += [(mod, g) for g in fn() if all(p.requires_grad for p in g["params"])]
-        member = {id(p): gi for gi, (_, g) in enumerate(groups) for p in g["params"]}
-        order, placed, self.group_spans = [], set(), {}
-        for p in self.params:
-            gi = member.get(id(p))
-            if gi is None:
-                order.append((p, None))
-            elif gi not in placed:
-                placed.add(gi)
-                order += [(q, gi) for q in groups[gi][1]["params"]]
-        self.params = [p for p, _ in order]
-        self.offsets, total = [], 0
-        for i, (p, gi) in enumerate(order):
-            self.offsets.append(total)
-            last_of_group = gi is not None and (i + 1 == len(order) or order[i + 1][1] != gi)
-            if gi is None:
-                total += (p.numel() + 7) // 8 * 8        # 16-byte alignment in both the fp32 and the bf16 arena
-            else:
-                if gi not in self.group_spans:
-                    self.group_spans[gi] = total
-                total += p.numel()                        # members tightly packed ...
-                if last_of_group:
-                    total = (total + groups[gi][1]["pad"] + 7) // 8 * 8   # ... then the group's zero padding
-        self._groups = groups
-        self.total = total
-        self.flat_p = torch.zeros(total, dtype=torch.float32, device=dev)
-        _ARENAS[self.flat_p.untyped_storage().data_ptr()] = self    # (hulc2_amd.optim.Adam finds the arena behind a parameter list here)
-        n_state = 0 if self.shadows_only else total            # (gradients and Adam moments belong to the caller's optimizer then)
-        self.flat_g = torch.zeros(total if self.step_node else n_state, dtype=torch.float32, device=dev)
-        self.grads_zeroed_at = None            # flat_g._version at which hulc2_amd.optim.Adam.zero_grad(set_to_none=False) left the arena all zeros
+        # fused views receive their gradient through a sink only, so they exist only when sinks do (not with per-parameter all-reduce hooks)
+        use_sinks = next(p for p in model.parameters() if p.requires_grad).is_cuda and (not self.multi or not overlap)
+        plan = plan_arena(model, use_sinks)
+        self.skip_ranges = self._skip_ranges(plan, skip_params)
+        self._install(model, plan, grad_arena=True)
+        dev, total = self.dev, self.total
+        for p, off in zip(self.params, self.offsets):
+            p.grad = self.flat_g[off:off + p.numel()].view(p.shape)
         # SGD: exp_avg serves as the momentum buffer (none with momentum == 0), there is no second state arena
         sgd = self.optimizer == "sgd"
-        self.exp_avg = torch.zeros(0 if sgd and self.momentum == 0 else n_state, dtype=torch.float32, device=dev)
-        self.exp_avg_sq = torch.zeros(0 if sgd else n_state, dtype=torch.float32, device=dev)
-        self.skip_ranges = self._skip_ranges(skip_params)
-        self.flat_bf16 = torch.zeros(total, dtype=torch.bfloat16, device=dev) if dev.type == "cuda" else None
-        with torch.no_grad():
-            for p, off in zip(self.params, self.offsets):
-                n = p.numel()
-                self.flat_p[off:off + n].copy_(p.reshape(-1))
-                p.data = self.flat_p[off:off + n].view(p.shape)
-                if not self.shadows_only:
-                    p.grad = self.flat_g[off:off + n].view(p.shape)
-                if self.flat_bf16 is not None and p.dim() == 2:
-                    shadow.register_arena_view(p, self.flat_bf16[off:off + n].view(p.shape))
-        # fused group views: parameter view for the kernels, gradient view as its sink, bf16 shadow like any 2-D weight
-        self.fused = []
-        for gi, (mod, g) in enumerate(groups):
-            off, shape = self.group_spans[gi], tuple(g["shape"])
-            n = 1
-            for d in shape:
-                n *= d
-            pv, gv = self.flat_p[off:off + n].view(shape), self.flat_g[off:off + n].view(shape)
-            if mod._fused is None:
-                mod._fused = {}
-            mod._fused[g["attr"]] = pv
-            self.fused.append((pv, gv, off, shape))
-            if len(shape) == 2:
-                shadow.register_arena_view(pv, self.flat_bf16[off:off + n].view(shape))
-        if self.flat_bf16 is not None:
-            kn.cast_f32_to_bf16(self.flat_p, self.flat_bf16, total)
-        # transposed bf16 shadows of the nn.Linear weights (data-gradient GEMMs read W^T k-major); RNN and conv weights are
-        # consumed in place by their own kernels and stay out of the table
-        self.flat_bf16_t = self.tiles_t = None
-        if self.flat_bf16 is not None:
-            names = {id(p): n for n, p in model.named_parameters()}
-            mats = []                                     # (tensor the kernels see, arena offset): single weights and fused groups
-            for p, off in zip(self.params, self.offsets):
-                nm = names.get(id(p), "")
-                if p.dim() != 2 or "rnn.weight_hh" in nm or "rnn.weight_ih_l1" in nm or min(p.shape) < 8 or id(p) in member:
-                    continue
-                mats.append((p, off))
-            mats += [(pv, off) for pv, _, off, shape in self.fused if len(shape) == 2]
-            tiles = []
-            for t, off in mats:
-                r, c = t.shape
-                tiles += [(off, r, c, i, j) for i in range((r + 63) // 64) for j in range((c + 63) // 64)]
-            if tiles:
-                self.flat_bf16_t = torch.zeros(total, dtype=torch.bfloat16, device=dev)
-                self.tiles_t = torch.tensor(tiles, dtype=torch.int64, device=dev)
-                for t, off in mats:
-                    shadow.register_arena_view_t(t, self.flat_bf16_t[off:off + t.numel()].view(t.shape[1], t.shape[0]))
-                kn.transpose_bf16_tiles(self.flat_bf16, self.flat_bf16_t, self.tiles_t)
-        # fragment-packed feed-forward weights of the transformer block launch (modules list them in frag_operands()): one gather launch per
-        # step from the bf16 arena and its transposed shadow, 8-byte chunks
-        self.frag_shadow = self.frag_idx = None
-        if self.flat_bf16 is not None and self.flat_bf16_t is not None:
-            off_of = {id(p): off for p, off in zip(self.params, self.offsets)}
-            chunks, views, dst = [], [], 0
-            for m in model.modules():
-                if not hasattr(m, "frag_operands"):
-                    continue
-                for p, n in m.frag_operands():
-                    off = off_of.get(id(p))
-                    if off is None or off % 4 or id(p) in member:
-                        continue
-                    ff = p.shape[0] if n in (0, 3) else p.shape[1]
-                    perm = kn.ffn_frag_perm(n, ff).astype("int64").reshape(-1, 4)
-                    assert (perm[:, 0] % 4 == 0).all() and (perm[:, 1:] - perm[:, :1] == [1, 2, 3]).all(), "fragment permutations move runs of 4"
-                    c = (perm[:, 0] + off) // 4
-                    chunks.append(c | (1 << 31) if n in (2, 3) else c)
-                    views.append((p, "ffn_p%d" % n, dst, p.numel()))
-                    dst += p.numel()
-            if chunks:
-                import numpy as np
-                self.frag_shadow = torch.zeros(dst, dtype=torch.bfloat16, device=dev)
-                self.frag_idx = torch.from_numpy(np.concatenate(chunks).astype(np.uint32).view(np.int32)).to(dev)
-                for p, name, d0, n_el in views:
-                    shadow.register_layout_view(p, name, self.frag_shadow[d0:d0 + n_el])
-                kn.gather_chunks(self.flat_bf16, self.flat_bf16_t, self.frag_shadow, self.frag_idx)
-        # rounding remainders w - bf16(w) of the weights a split-operand forward reads (modules list them in lo_operands(): natural layout
-        # "lo", packed "ffn_p0_lo" / "ffn_p1_lo").  Round 4: a second shadow ARENA (same offsets as the bf16 shadow; 94 MB of the 288 GB) that
-        # the Adam kernel fills inside <= 8 element ranges while the new weights are in its registers — the separate residual launch
-        # (66-73 us per step) is only used when weights are written from outside (refresh_shadows)
-        self.flat_lo = self.lo_seg = self.lo_frag = self.lo_frag_idx = None
-        self.lo_ranges = []
-        if self.flat_bf16 is not None:
-            off_of = {id(p): off for p, off in zip(self.params, self.offsets)}
-            segs, nat, packed = [], {}, []
-            for m in model.modules():
-                if not hasattr(m, "lo_operands"):
-                    continue
-                for p, layout in m.lo_operands():
-                    off = off_of.get(id(p))
-                    if off is None or off % 4 or id(p) in member:
-                        continue
-                    if id(p) not in nat:
-                        nat[id(p)] = (p, off)
-                        segs.append((off, p.numel(), off))
-                    if layout not in ("lo", "oihw_flat_lo"):
-                        packed.append((p, layout))
-            if segs:
-                import numpy as np
-                self.flat_lo = torch.zeros(total, dtype=torch.bfloat16, device=dev)
-                self.lo_seg = torch.tensor(segs, dtype=torch.int64, device=dev)
-                ranges = sorted([a, a + (n + 3) // 4 * 4] for a, n, _ in segs)      # (offsets are multiples of 8: the padding is the slice's own)
-                merged = []
-                for a, b in ranges:
-                    if merged and a <= merged[-1][1]:
-                        merged[-1][1] = max(merged[-1][1], b)
-                    else:
-                        merged.append([a, b])
-                while len(merged) > 8:                       # the kernel takes 8: close the smallest gaps (remainders of the weights between
-                    gi = min(range(len(merged) - 1), key=lambda i: merged[i + 1][0] - merged[i][1])   # them are written too: harmless)
-                    merged[gi][1] = merged[gi + 1][1]
-                    del merged[gi + 1]
-                self.lo_ranges = [(a, min(b, total)) for a, b in merged]
-                for p, d0 in nat.values():
-                    shadow.register_layout_view(p, "lo", self.flat_lo[d0:d0 + p.numel()].view(p.shape))
-                    if p.dim() == 4:                        # conv weight: its OIHW-flat remainder is the same memory
-                        shadow.register_layout_view(p, "oihw_flat_lo", self.flat_lo[d0:d0 + p.numel()].view(p.shape[0], -1))
-                chunks, views, fdst = [], [], 0
-                for p, layout in packed:
-                    n = int(layout[5])
-                    ff = p.shape[0] if n in (0, 3) else p.shape[1]
-                    perm = kn.ffn_frag_perm(n, ff).astype("int64").reshape(-1, 4)
-                    chunks.append((perm[:, 0] + nat[id(p)][1]) // 4)
-                    views.append((p, layout, fdst, p.numel()))
-                    fdst += p.numel()
-                if chunks:
-                    self.lo_frag = torch.zeros(fdst, dtype=torch.bfloat16, device=dev)
-                    self.lo_frag_idx = torch.from_numpy(np.concatenate(chunks).astype(np.uint32).view(np.int32)).to(dev)
-                    for p, name, d0, n_el in views:
-                        shadow.register_layout_view(p, name, self.lo_frag[d0:d0 + n_el])
-                self._refresh_lo()
-        # conv weights in their kernel layouts (OIHW flat for conv1, OHWI forward, IHWO data gradient): one repack launch per step
-        self.conv_shadow = self.conv_table = None
-        if self.flat_bf16 is not None:
-            rows, views, dst = [], [], 0
-            flat_lin = {id(w): chw for m in model.modules() if hasattr(m, "flatten_linears") for w, chw in m.flatten_linears()}
-            for p, off in zip(self.params, self.offsets):
-                chw = flat_lin.get(id(p))
-                if p.dim() == 2 and chw is not None:          # Linear behind nn.Flatten of a (C, H, W) map (gripper encoder): NHWC column order
-                    co, (ci, kh, kw) = p.shape[0], chw
-                    modes = [("hwc", 1, (co, kh * kw * ci)), ("hwc_t", 3, (kh * kw * ci, co))]
-                elif p.dim() != 4:
-                    continue
-                else:
-                    co, ci, kh, kw = p.shape
-                    modes = [("oihw_flat", 0, (co, ci * kh * kw))] if ci < 8 else [("ohwi", 1, (co, kh * kw * ci)), ("ihwo", 2, (ci, kh, kw, co))]
-                for name, mode, shape in modes:
-                    rows.append((off, dst, co, ci, kh, kw, mode))
-                    views.append((p, name, dst, shape))
-                    dst += (p.numel() + 7) // 8 * 8
-            if rows:
-                self.conv_shadow = torch.zeros(dst, dtype=torch.bfloat16, device=dev)
-                self.conv_table = torch.tensor(rows, dtype=torch.int64, device=dev)
-                for p, name, d0, shape in views:
-                    shadow.register_layout_view(p, name, self.conv_shadow[d0:d0 + p.numel()].view(shape))
-                kn.repack_conv_weights(self.flat_p, self.conv_shadow, self.conv_table)
-        self.comm = self.buckets = None
-        if not self.shadows_only:
-            self.comm = GradComm(self.flat_g, group, comm_algo, grad_payload, force=force_comm)
-            self.buckets = GradBuckets(self.params, self.offsets, self.flat_g, bucket_mb << 20, group, overlap, comm=self.comm)
-            # bucket all-reduces overlapped with backward share the GPU with the compute stream: barrier kernels are then off
-            kn.set_concurrent_streams(dev.type == "cuda" and self.multi and overlap)
-        self._autograd_written, self._zero_planned, self._acc_hooks, self._sink_keys = set(), None, [], []
-        self._replan_pending = False
-        if use_sinks:                                     # no per-parameter all-reduce hooks depend on AccumulateGrad
-            owner = self if self.shadows_only else None       # (the keeper's sinks are live inside its model's step node only)
-            for p, off in zip(self.params, self.offsets):
-                self._sink_keys.append(gradsink.register(p, self.flat_g[off:off + p.numel()].view(p.shape), owner))
-                if not self.shadows_only:                     # (the step node takes autograd-made gradients with autograd.grad: nothing accumulates into the arena)
-                    self._acc_hooks.append(p.register_post_accumulate_grad_hook(self._saw_autograd_grad))
-            for pv, gv, _, _ in self.fused:
-                self._sink_keys.append(gradsink.register(pv, gv, owner))
+        self.exp_avg = torch.zeros(0 if sgd and self.momentum == 0 else total, dtype=torch.float32, device=dev)
+        self.exp_avg_sq = torch.zeros(0 if sgd else total, dtype=torch.float32, device=dev)
+        self.comm = GradComm(self.flat_g, group, comm_algo, grad_payload, force=force_comm)
+        self.buckets = GradBuckets(self.params, self.offsets, self.flat_g, bucket_mb << 20, group, overlap, comm=self.comm)
+        # bucket all-reduces overlapped with backward share the GPU with the compute stream: barrier kernels are then off
+        kn.set_concurrent_streams(dev.type == "cuda" and self.multi and overlap)
+        self._acc_hooks = []
+        if use_sinks:                                      # no per-parameter all-reduce hooks depend on AccumulateGrad
+            self._register_sinks(None)
+            self._acc_hooks = [p.register_post_accumulate_grad_hook(self._saw_autograd_grad) for p in self.params]
         self.step_count = 0
-        self.dev = dev
-        if dev.type == "cuda" and not self.shadows_only:
+        if dev.type == "cuda":
             kn.step_state(dev)[1] = 0               # the device-resident Adam step count starts with this trainer (the RNG word keeps walking)
         self.graph_fb = self.graph_enc = self.graph_opt = None
         self.static_loss = None
         self._comm_events = []
-        # (not a bound method: copy.deepcopy(model) copies the module's hook table, and a bound method would drag the trainer — arenas and all —
-        # into the copy; the copy's hook finds that the trainer belongs to another module and does nothing)
-        self._load_hook = model.register_load_state_dict_post_hook(_LoadHook(self))
-        model.__dict__["_hulc_arena_trainer"] = weakref.ref(self)
-        # Split point for overlapping the gradient all-reduce with the tail of backward in graph mode: the camera encoders
-        # are registered first (arena head, 0.75 M parameters) but their backward (the conv stack) is the LAST ~2 ms of a step,
-        # while everything else (98 % of the gradient bytes) is complete once backward reaches the encoder output.
+        self._split_encoder(model)
+
+    def _split_encoder(self, model) -> None:
+        """Split point for overlapping the gradient all-reduce with the tail of backward in graph mode: the camera encoders are registered
+        first (arena head, 0.75 M parameters) but their backward (the conv stack) is the LAST ~2 ms of a step, while everything else (98 % of
+        the gradient bytes) is complete once backward reaches the encoder output."""
         names = {id(p): n for n, p in model.named_parameters()}
         enc = [names.get(id(p), "").startswith("perceptual_encoder.") for p in self.params]
         idx = [i for i, e in enumerate(enc) if e]
         self.enc_lo = self.enc_hi = 0                      # arena slice [enc_lo, enc_hi) = the encoder gradients (one contiguous run)
         self.enc_params, self.rest_params = [], list(self.params)
         if idx and len(idx) < len(self.params) and idx[-1] - idx[0] + 1 == len(idx) and hasattr(model, "perceptual_encoder"):
-            self.enc_lo = self.offsets[idx[0]]
-            self.enc_hi = self.offsets[idx[-1] + 1] if idx[-1] + 1 < len(self.params) else total
+            (self.enc_lo, self.enc_hi), = self.span_ranges(idx)
             self.enc_params = [self.params[i] for i in idx]
             self.rest_params = [p for i, p in enumerate(self.params) if not enc[i]]
-            if not self.shadows_only:                             # (the split backward belongs to this trainer's own step)
-                model.perceptual_encoder.register_forward_hook(self._keep_encoder_output)
+            model.perceptual_encoder.register_forward_hook(self._keep_encoder_output)
         self._emb = None
 
-    def _skip_ranges(self, skip_params) -> list:
-        """arena ranges of the parameters the optimizer pass leaves alone: a parameter's span up to its successor's offset (the alignment
-        padding behind it is zero and stays zero), arena neighbours merged"""
+    def _skip_ranges(self, plan, skip_params) -> list:
+        """arena ranges of the parameters the optimizer pass leaves alone (arena.span_ranges), checked against what the kernels take"""
         skip = {id(p) for p in skip_params}
         if not skip:
             return []
         if self.optimizer == "adam":
             raise ValueError("ArenaTrainer: skip_params needs optimizer='adamw' or 'sgd' (the Adam pass has no skip ranges)")
-        unknown = skip - {id(p) for p in self.params}
+        unknown = skip - {id(p) for p in plan.params}
         if unknown:
             raise ValueError(f"ArenaTrainer: {len(unknown)} of skip_params are not trainable parameters of the model")
-        ranges = []
-        for i, p in enumerate(self.params):
-            if id(p) not in skip:
-                continue
-            a, b = self.offsets[i], self.offsets[i + 1] if i + 1 < len(self.params) else self.total
-            if ranges and ranges[-1][1] == a:
-                ranges[-1][1] = b
-            else:
-                ranges.append([a, b])
-        if len(ranges) > 8:
-            raise ValueError(f"ArenaTrainer: skip_params make {len(ranges)} arena ranges, the optimizer kernels take at most 8")
+        ranges = span_ranges(plan.offsets, plan.total, [i for i, p in enumerate(plan.params) if id(p) in skip])
+        if len(ranges) > MAX_KERNEL_RANGES:
+            raise ValueError(f"ArenaTrainer: skip_params make {len(ranges)} arena ranges, the optimizer kernels take at most {MAX_KERNEL_RANGES}")
         if any(a % 4 for a, _ in ranges):
             raise ValueError("ArenaTrainer: a skipped parameter sits at an arena offset that is no multiple of 4 (member of a fused group)")
-        return [(a, b) for a, b in ranges]
+        return ranges
 
     def __deepcopy__(self, memo):
-        """the shadows-only keeper is not copied with its model (copy.deepcopy(model) reaches it through the model's __dict__): the copy
-        starts without one and builds its own on its first training step.  A full trainer copies like any object."""
-        if self.shadows_only:
-            return None
-        import copy
+        """a trainer copies like any object (only a model's own keeper stays behind when the model is copied)"""
         new = self.__class__.__new__(self.__class__)
         memo[id(self)] = new
-        for k, v in self.__dict__.items():
-            setattr(new, k, copy.deepcopy(v, memo))
+        new.__dict__.update(copy.deepcopy(self.__dict__, memo))
         return new
 
-    def refresh_if_stale(self) -> bool:
-        """shadows_only mode: an external optimizer steps the parameters in place (views of the arena) and bumps their version counters; one
-        look at three of them decides whether the derived copies are re-made (five launches for the whole model)"""
-        ps = self.params
-        sig = sum(p._version for p in ps)                      # (every in-place write to any parameter — optimizer, load, a test's nudge — moves it)
-        if sig == getattr(self, "_fresh_sig", None):
-            return False
-        for p, off in zip(ps, self.offsets):                  # (an optimizer that REPLACED .data would have left the arena)
-            if p.data_ptr() != self.flat_p.data_ptr() + off * 4:
-                self._after_model_load(None, None)
-                break
-        else:
-            self.refresh_shadows()
-        self._fresh_sig = sig
-        return True
-
-    def _refresh_lo(self) -> None:
-        """the remainders from scratch (weights written from outside; the optimizer step keeps them fresh inside the Adam kernel)"""
-        if self.lo_seg is not None:
-            kn.residual_bf16(self.flat_p, self.flat_bf16, self.flat_lo, self.lo_seg)
-            if self.lo_frag_idx is not None:
-                kn.gather_chunks(self.flat_lo, None, self.lo_frag, self.lo_frag_idx)
-
-    # ---- weights written from outside (checkpoint restore) and optimizer state ----------------------------------------------------
-    def refresh_shadows(self) -> None:
-        """Re-derive every kernel-side copy of the parameters from the fp32 arena: the bf16 shadow, its transposed tiles and the conv
-        repacks.  The Adam kernel keeps them fresh step by step; anything else that writes the parameters (model.load_state_dict —
-        Lightning restores weights AFTER the optimizer exists, hulc2/training.py:41-53,82 —, an external p.data.copy_) must be followed by
-        this call, else the next forward/backward runs on the old weights.  Installed as a load_state_dict post-hook on the model."""
-        if self.flat_bf16 is not None:
-            kn.cast_f32_to_bf16(self.flat_p, self.flat_bf16, self.total)
-            if self.tiles_t is not None:
-                kn.transpose_bf16_tiles(self.flat_bf16, self.flat_bf16_t, self.tiles_t)
-            if self.frag_idx is not None:
-                kn.gather_chunks(self.flat_bf16, self.flat_bf16_t, self.frag_shadow, self.frag_idx)
-            self._refresh_lo()
-            if self.conv_table is not None:
-                kn.repack_conv_weights(self.flat_p, self.conv_shadow, self.conv_table)
-        shadow.bump_epoch()
-
-    def _after_model_load(self, module, incompatible_keys) -> None:
-        for p, off in zip(self.params, self.offsets):         # a load that REPLACED .data (assign=True) would detach the arena: re-home it
-            if p.data_ptr() != self.flat_p.data_ptr() + off * 4:
-                with torch.no_grad():
-                    self.flat_p[off:off + p.numel()].copy_(p.reshape(-1))
-                    p.data = self.flat_p[off:off + p.numel()].view(p.shape)
-        self.refresh_shadows()
-
+    # ---- optimizer state ---------------------------------------------------------------------------------------------------------------------
     def state_dict(self) -> Dict:
         """optimizer state in the reference's terms (a Lightning checkpoint carries torch.optim.Adam's exp_avg / exp_avg_sq / step per
         parameter, hulc2.py:185-198): per-parameter tensors keyed by the model's parameter names, so the arena layout can change between
@@ -780,96 +465,93 @@ class ArenaTrainer:
         self.refresh_shadows()
 
     # ---- interchange with the reference's checkpoints: `optimizer_states[0]` of a Lightning checkpoint IS torch.optim.Adam.state_dict() ----------
+    def _torch_state_names(self) -> tuple:
+        """the per-parameter state tensors of the torch optimizer of this trainer's kind, in the order (exp_avg, exp_avg_sq) of the arenas"""
+        if self.optimizer == "sgd":
+            return ("momentum_buffer",) if self.exp_avg.numel() else ()
+        return ("exp_avg", "exp_avg_sq")
+
     def to_torch_optimizer_state_dict(self) -> Dict:
-        """This trainer's state as the `state_dict()` of the torch optimizer of its kind holds it (torch 2.10): torch.optim.Adam (see
-        to_torch_adam_state_dict), torch.optim.AdamW — Adam's layout with `decoupled_weight_decay: True` — or torch.optim.SGD, whose state is
-        `momentum_buffer` alone (no entry without momentum).  skip_params have no entry: torch never made state for them."""
-        if self.optimizer == "adam":
-            return self.to_torch_adam_state_dict()
+        """This trainer's state as the `state_dict()` of the torch optimizer of its kind holds it (torch 2.10; reference: hulc2.py:185-198,
+        conf/model/optimizer/*.yaml): `state` keyed by the INDEX of the parameter in `model.parameters()` order, `param_groups[0]["params"]`
+        = all indices.  torch.optim.Adam / AdamW keep `step` / `exp_avg` / `exp_avg_sq` per parameter and differ in `decoupled_weight_decay`;
+        torch.optim.SGD's state is `momentum_buffer` alone (no entry without momentum).  Frozen / never-updated parameters and skip_params
+        have no entry: torch never made state for them.  A reference Lightning run resumes from it with `optimizer.load_state_dict(...)`."""
         order = list(self.model.parameters())
         index = {id(p): off for p, off in zip(self.params, self.offsets)}
         skipped = lambda off: any(a <= off < b for a, b in self.skip_ranges)
-        sgd = self.optimizer == "sgd"
+        sgd, names = self.optimizer == "sgd", self._torch_state_names()
         state = {}
-        if self.step_count > 0 and not (sgd and self.momentum == 0):
+        if self.step_count > 0 and names:
             for i, p in enumerate(order):
                 off = index.get(id(p))
                 if off is None or skipped(off):
                     continue
-                n = p.numel()
-                if sgd:
-                    state[i] = {"momentum_buffer": self.exp_avg[off:off + n].view(p.shape).clone()}
-                else:
-                    state[i] = {"step": torch.tensor(float(self.step_count)),
-                                "exp_avg": self.exp_avg[off:off + n].view(p.shape).clone(),
-                                "exp_avg_sq": self.exp_avg_sq[off:off + n].view(p.shape).clone()}
+                state[i] = {} if sgd else {"step": torch.tensor(float(self.step_count))}
+                for name, arena in zip(names, (self.exp_avg, self.exp_avg_sq)):
+                    state[i][name] = arena[off:off + p.numel()].view(p.shape).clone()
         lr = self.lr
-        if self._lr_lambda is not None:
+        if self._lr_lambda is not None:                           # what a torch scheduler leaves behind k steps: base * lambda(k) and initial_lr
             lr = float(self.base_lr) * self._lr_lambda(self._opt_steps)
         if sgd:
             group = {"lr": lr, "momentum": self.momentum, "dampening": self.dampening, "weight_decay": self.wd, "nesterov": self.nesterov,
                      "maximize": False, "foreach": None, "differentiable": False, "fused": None}
         else:
             group = {"lr": lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd, "amsgrad": False, "maximize": False,
-                     "foreach": None, "capturable": False, "differentiable": False, "fused": None, "decoupled_weight_decay": True}
+                     "foreach": None, "capturable": False, "differentiable": False, "fused": None,
+                     "decoupled_weight_decay": self.optimizer == "adamw"}
         group["params"] = list(range(len(order)))
         if self._lr_lambda is not None:
             group["initial_lr"] = float(self.base_lr)
         return {"state": state, "param_groups": [group]}
 
     def from_torch_optimizer_state_dict(self, sd: Dict) -> None:
-        """Resume from the `state_dict()` of the torch optimizer of this trainer's kind: the inverse of to_torch_optimizer_state_dict.
-        An AdamW trainer refuses a group without decoupled decay (that is torch.optim.Adam's rule: optimizer="adam"), and the other way round.
-        torch.optim.SGD keeps no step count: a state WITH momentum buffers resumes behind the first step, one without starts at it."""
-        g0 = sd["param_groups"][0]
-        if self.optimizer == "adam":
-            if g0.get("decoupled_weight_decay"):
-                raise ValueError("the optimizer state decays decoupled (torch.optim.AdamW): build the trainer with optimizer='adamw'")
-            return self.from_torch_adam_state_dict(sd)
-        sgd = self.optimizer == "sgd"
-        if sgd != ("momentum" in g0) or (not sgd and not g0.get("decoupled_weight_decay")):
+        """Resume from the `state_dict()` of the torch optimizer of this trainer's kind (a reference checkpoint's `ckpt["optimizer_states"][0]`):
+        the inverse of to_torch_optimizer_state_dict.  An AdamW trainer refuses a group without decoupled decay (that is torch.optim.Adam's
+        rule: optimizer="adam"), and the other way round.  The fused kernels keep ONE step count, so the per-parameter steps must agree (they
+        do for an optimizer that stepped all its parameters together).  torch.optim.SGD keeps no step count: a state WITH momentum buffers
+        resumes behind the first step, one without starts at it.  Adam's form may come in several param_groups (their ids are flattened, the
+        hyper-parameters are group 0's)."""
+        groups = sd["param_groups"]
+        g0 = groups[0]
+        sgd, adam = self.optimizer == "sgd", self.optimizer == "adam"
+        if adam and g0.get("decoupled_weight_decay"):
+            raise ValueError("the optimizer state decays decoupled (torch.optim.AdamW): build the trainer with optimizer='adamw'")
+        if not adam and (sgd != ("momentum" in g0) or (not sgd and not g0.get("decoupled_weight_decay"))):
             raise ValueError(f"the optimizer state is not torch's for optimizer={self.optimizer!r} (group keys {sorted(k for k in g0 if k != 'params')})")
         if g0.get("amsgrad") or g0.get("maximize"):
-            raise NotImplementedError("amsgrad / maximize are not built")
-        if len(sd["param_groups"]) != 1:
+            raise NotImplementedError("amsgrad / maximize are not built (conf/model/optimizer/*.yaml use neither)")
+        if not adam and len(groups) != 1:
             raise NotImplementedError("several param groups are not built: the arena optimizer keeps one set of hyper-parameters")
         order = list(self.model.parameters())
-        ids = list(g0["params"])
+        ids = [i for g in groups for i in g["params"]]
         if len(ids) != len(order):
             raise KeyError(f"optimizer state for {len(ids)} parameters, model.parameters() has {len(order)}")
         if sgd and (float(g0["momentum"]) != 0) != (self.exp_avg.numel() != 0):
             raise ValueError("the optimizer state and this trainer disagree on whether SGD keeps a momentum buffer")
         index = {id(p): off for p, off in zip(self.params, self.offsets)}
-        steps = set()
+        names, steps = self._torch_state_names(), set()
         with torch.no_grad():
             for pos, key in enumerate(ids):
                 p, rec = order[pos], sd["state"].get(key)
                 off = index.get(id(p))
                 if off is None:
                     continue
-                n = p.numel()
-                if sgd:
-                    buf = None if rec is None else rec.get("momentum_buffer")
-                    if self.exp_avg.numel():
-                        if buf is None:
-                            self.exp_avg[off:off + n].zero_()
-                        else:
-                            self.exp_avg[off:off + n].copy_(buf.reshape(-1))
-                            steps.add(1)
-                    continue
-                if rec is None:
-                    self.exp_avg[off:off + n].zero_()
-                    self.exp_avg_sq[off:off + n].zero_()
-                    continue
-                if tuple(rec["exp_avg"].shape) != tuple(p.shape):
-                    raise KeyError(f"optimizer state {key}: shape {tuple(rec['exp_avg'].shape)} vs parameter {tuple(p.shape)}")
-                self.exp_avg[off:off + n].copy_(rec["exp_avg"].reshape(-1))
-                self.exp_avg_sq[off:off + n].copy_(rec["exp_avg_sq"].reshape(-1))
-                steps.add(int(float(rec["step"])))
+                if rec is not None and names and rec.get(names[0]) is None:
+                    rec = None                                    # (no record: torch creates state lazily, a parameter that never saw a gradient)
+                for name, arena in zip(names, (self.exp_avg, self.exp_avg_sq)):
+                    if rec is None:
+                        arena[off:off + p.numel()].zero_()
+                        continue
+                    if tuple(rec[name].shape) != tuple(p.shape):
+                        raise KeyError(f"optimizer state {key}: shape {tuple(rec[name].shape)} vs parameter {tuple(p.shape)}")
+                    arena[off:off + p.numel()].copy_(rec[name].reshape(-1))
+                if rec is not None and names:
+                    steps.add(1 if sgd else int(float(rec["step"])))
         if len(steps) > 1:
             raise ValueError(f"per-parameter steps differ ({sorted(steps)}): the arena optimizer keeps one step count")
         self.step_count = steps.pop() if steps else 0
-        self._opt_steps = self.step_count
+        self._opt_steps = self.step_count                         # (a scheduler stepped once per optimizer step stands at the same count)
         if "initial_lr" in g0:
             self.base_lr = float(g0["initial_lr"])
         if sgd:
@@ -882,76 +564,16 @@ class ArenaTrainer:
         self.refresh_shadows()
 
     def to_torch_adam_state_dict(self) -> Dict:
-        """This trainer's state as `torch.optim.Adam(model.parameters(), lr).state_dict()` would hold it (reference: hulc2.py:185-198,
-        conf/model/optimizer/adam.yaml): `state` keyed by the INDEX of the parameter in `model.parameters()` order with a per-parameter `step`
-        tensor, `param_groups[0]["params"]` = all indices.  Frozen / never-updated parameters have no entry, like in torch.  A reference
-        Lightning run resumes from it with `optimizer.load_state_dict(...)`."""
+        """to_torch_optimizer_state_dict() of an Adam trainer: what `torch.optim.Adam(model.parameters(), lr).state_dict()` would hold"""
         if self.optimizer != "adam":
             raise ValueError(f"to_torch_adam_state_dict: this trainer's optimizer is {self.optimizer!r}; use to_torch_optimizer_state_dict()")
-        order = list(self.model.parameters())
-        index = {id(p): off for p, off in zip(self.params, self.offsets)}
-        state = {}
-        if self.step_count > 0:
-            for i, p in enumerate(order):
-                off = index.get(id(p))
-                if off is None:
-                    continue
-                n = p.numel()
-                state[i] = {"step": torch.tensor(float(self.step_count)),
-                            "exp_avg": self.exp_avg[off:off + n].view(p.shape).clone(),
-                            "exp_avg_sq": self.exp_avg_sq[off:off + n].view(p.shape).clone()}
-        lr = self.lr
-        if self._lr_lambda is not None:                           # what a torch scheduler leaves behind k steps: base * lambda(k) and initial_lr
-            lr = float(self.base_lr) * self._lr_lambda(self._opt_steps)
-        group = {"lr": lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd, "amsgrad": False, "maximize": False,
-                 "foreach": None, "capturable": False, "differentiable": False, "fused": None, "decoupled_weight_decay": False,
-                 "params": list(range(len(order)))}
-        if self._lr_lambda is not None:
-            group["initial_lr"] = float(self.base_lr)
-        return {"state": state, "param_groups": [group]}
+        return self.to_torch_optimizer_state_dict()
 
     def from_torch_adam_state_dict(self, sd: Dict) -> None:
-        """Resume from a reference checkpoint's optimizer state (`ckpt["optimizer_states"][0]`): the inverse of to_torch_adam_state_dict.
-        The fused kernel keeps ONE step count, so the per-parameter steps must agree (they do for a torch.optim.Adam that stepped all its
-        parameters together — every parameter of this model receives a gradient every step)."""
+        """from_torch_optimizer_state_dict() of an Adam trainer: resume from a reference checkpoint's `ckpt["optimizer_states"][0]`"""
         if self.optimizer != "adam":
             raise ValueError(f"from_torch_adam_state_dict: this trainer's optimizer is {self.optimizer!r}; use from_torch_optimizer_state_dict()")
-        order = list(self.model.parameters())
-        groups = sd["param_groups"]
-        ids = [i for g in groups for i in g["params"]]
-        if len(ids) != len(order):
-            raise KeyError(f"optimizer state for {len(ids)} parameters, model.parameters() has {len(order)}")
-        index = {id(p): off for p, off in zip(self.params, self.offsets)}
-        steps = set()
-        with torch.no_grad():
-            for pos, key in enumerate(ids):
-                p, rec = order[pos], sd["state"].get(key)
-                off = index.get(id(p))
-                if off is None:
-                    continue
-                n = p.numel()
-                if rec is None:                                  # torch creates state lazily: a parameter that never saw a gradient
-                    self.exp_avg[off:off + n].zero_()
-                    self.exp_avg_sq[off:off + n].zero_()
-                    continue
-                if tuple(rec["exp_avg"].shape) != tuple(p.shape):
-                    raise KeyError(f"optimizer state {key}: shape {tuple(rec['exp_avg'].shape)} vs parameter {tuple(p.shape)}")
-                self.exp_avg[off:off + n].copy_(rec["exp_avg"].reshape(-1))
-                self.exp_avg_sq[off:off + n].copy_(rec["exp_avg_sq"].reshape(-1))
-                steps.add(int(float(rec["step"])))
-        if len(steps) > 1:
-            raise ValueError(f"per-parameter Adam steps differ ({sorted(steps)}): the arena optimizer keeps one step count")
-        self.step_count = steps.pop() if steps else 0
-        self._opt_steps = self.step_count                         # (a scheduler stepped once per optimizer step stands at the same count)
-        g0 = groups[0]
-        if "initial_lr" in g0:
-            self.base_lr = float(g0["initial_lr"])
-        if g0.get("amsgrad") or g0.get("maximize"):
-            raise NotImplementedError("amsgrad / maximize are not built (conf/model/optimizer/adam.yaml uses neither)")
-        self._set_hparams(g0["lr"], g0["betas"], g0["eps"], g0.get("weight_decay", 0.0))
-        if self.dev.type == "cuda":
-            kn.step_state(self.dev)[1] = self.step_count
-        self.refresh_shadows()
+        self.from_torch_optimizer_state_dict(sd)
 
     def _set_hparams(self, lr, betas, eps, wd, momentum=None, dampening=None, nesterov=None) -> None:
         """lr / betas / eps / weight decay are scalar kernel arguments: a captured optimizer graph has the OLD ones baked in, so a change
@@ -1002,19 +624,14 @@ class ArenaTrainer:
             self.set_lr(float(self.base_lr) * self._lr_lambda(self._opt_steps))
 
     def close(self) -> None:
-        """Detach this trainer from the model: the load_state_dict post-hook (which keeps the trainer, hence its four arenas, alive through the
-        model) is removed and the gradient sinks are dropped.  Parameters keep living in the arena until another trainer re-homes them."""
-        h, self._load_hook = getattr(self, "_load_hook", None), None
-        if h is not None:
-            h.remove()
+        """Detach this trainer from the model (WeightKeeper.close: load hook, gradient sinks) and remove its per-parameter hooks."""
+        super().close()
         for h in getattr(self, "_acc_hooks", ()):
             h.remove()
         self._acc_hooks = []
         b = getattr(self, "buckets", None)
         if b is not None:
             b.close()
-        gradsink.unregister(getattr(self, "_sink_keys", ()))       # this trainer's sinks only (another live trainer keeps its own)
-        self._sink_keys = []
 
     def _saw_autograd_grad(self, p) -> None:
         """post-accumulate hook: this parameter's gradient arrives through autograd's `grad +=` (not a kernel-side sink), so its arena slice must
@@ -1056,80 +673,14 @@ class ArenaTrainer:
         torch.autograd.backward(emb, grad_tensors=g, inputs=self.enc_params)
         kn.wgrad_flush(self.dev)
 
-    def _plan_partial_zero(self) -> None:
-        """After a fully zeroed step: the arena slices NOT written through a gradient sink are the only ones the next steps need zeroed
-        (autograd's `param.grad += g` lands there); sinks written by the backward kernels are overwritten by their first writer
-        (hulc2_amd/gradsink.py).  Neighbouring must-zero slices are merged across small written ones — zeroing a slice that is overwritten
-        later is harmless, one fill launch per slice is not."""
-        spans = []                                                 # arena ranges of fused groups whose single sink was written
-        for pv, gv, off, shape in self.fused:
-            if gradsink.written(pv):
-                spans.append((off, off + gv.numel()))
-        inside = lambda a, b: any(lo <= a and b <= hi for lo, hi in spans)
-        # ... and of those only the ones autograd really accumulates into (seen by the post-accumulate hooks during this first, fully zeroed
-        # step): a parameter nobody writes (an unused module of the reference's constructor, e.g. plan_recognition.layernorm) stays zero
-        need = [(off, off + p.numel()) for p, off in zip(self.params, self.offsets)
-                if not (gradsink.written(p) or inside(off, off + p.numel())) and id(p) in self._autograd_written]
-        self._zero_planned = {id(p) for p in self.params if id(p) in self._autograd_written}
-        merged = []
-        for a, b in sorted(need):
-            if merged and a - merged[-1][1] <= (1 << 18):          # gaps up to 1 MB of fp32 are cheaper to zero than another launch
-                merged[-1][1] = max(merged[-1][1], b)
-            else:
-                merged.append([a, b])
-        self._zero_ranges = [(a, b) for a, b in merged]
-        self._planned_written = gradsink.written_ids()
-        self._sink_slices = {id(p): (off, off + p.numel()) for p, off in zip(self.params, self.offsets)}
-        self._sink_slices.update({id(pv): (off, off + gv.numel()) for pv, gv, off, _ in self.fused})
-
-    _zero_ranges = None
-
-    def _zero_arena(self) -> None:
-        """what a backward pass needs of the gradient arena before it starts: everything zeroed (first pass: sinks accumulate) or only the slices
-        autograd accumulates into (later passes: the first sink writer of a slice overwrites it)"""
-        if self._zero_ranges is None or os.environ.get("HULC_FULL_ZERO_GRAD"):
-            self.flat_g.zero_()
-            gradsink.begin_step(False)
-        else:
-            for a, b in self._zero_ranges:
-                self.flat_g[a:b].zero_()
-            gradsink.begin_step(True)
-
     def zero_grad(self):
-        if self.shadows_only:
-            raise RuntimeError("ArenaTrainer(shadows_only=True) keeps the kernel-side weight copies only: gradients and the optimizer are the caller's")
         self.grads_zeroed_at = None                        # (optim.Adam.zero_grad's mark: this pass writes the arena with kernels of its own)
         self._zero_arena()
         for p, off in zip(self.params, self.offsets):      # autograd may have replaced .grad; re-point at the arena
             if p.grad is None or p.grad.data_ptr() != self.flat_g.data_ptr() + off * 4:
                 p.grad = self.flat_g[off:off + p.numel()].view(p.shape)
 
-    def _settle_sinks(self) -> None:
-        """bookkeeping behind a finished backward pass: the first (fully zeroed) pass makes the zeroing plan; later passes clean up after it"""
-        if self._zero_ranges is None and gradsink._sinks and not os.environ.get("HULC_FULL_ZERO_GRAD"):
-            self._plan_partial_zero()                              # the backward that just finished ran on a fully zeroed arena
-        elif self._zero_ranges is not None:
-            # a sink the plan expects to be overwritten was not written by this backward (a branch of the model did not run): its slice
-            # still holds the previous step's gradient — the true gradient is zero
-            now = gradsink.written_ids()
-            for k in self._planned_written - now:
-                a, b = self._sink_slices[k]
-                self.flat_g[a:b].zero_()
-            # a sink written for the first time AFTER the plan was made (untouched in the planning step, so neither zeroed per step nor
-            # expected to be overwritten): from now on it is "expected" — a later step that does not write it gets the clean-up above
-            # instead of Adam applying the stale slice (ADVICE r03, second case)
-            new = {k for k in now if k in self._sink_slices} - self._planned_written
-            if new:
-                self._planned_written = self._planned_written | new
-            if self._replan_pending:
-                # a parameter autograd accumulates into showed up after the plan: its slice was zero when this backward started (unplanned
-                # slices are only ever written through sinks, and those are cleaned above), so THIS step's sum is right; the next step
-                # runs on a fully zeroed arena and the plan is re-made behind it
-                self._zero_ranges, self._replan_pending = None, False
-
     def optimizer_step(self):
-        if self.shadows_only:
-            raise RuntimeError("ArenaTrainer(shadows_only=True) keeps the kernel-side weight copies only: gradients and the optimizer are the caller's")
         self._settle_sinks()
         self.step_count += 1
         common = dict(grad_scale=1.0 / self.world,
@@ -1145,12 +696,7 @@ class ArenaTrainer:
         else:
             kn.sgd_step(self.flat_p, self.flat_g, self.exp_avg if self.exp_avg.numel() else None, self.flat_bf16, self.total, self.lr,
                         self.momentum, self.dampening, self.nesterov, self.wd, self.step_count, skip_ranges=self.skip_ranges, **common)
-        # the derived copies: two launches behind Adam (were five: transposed tiles, fragment gather, residual, remainder gather, conv repack)
-        if self.tiles_t is not None or self.conv_table is not None:
-            kn.derive_copies(self.flat_bf16, self.flat_bf16_t, self.tiles_t, self.flat_p, self.conv_shadow, self.conv_table)
-        if self.frag_idx is not None or self.lo_frag_idx is not None:
-            kn.gather_chunks2(self.flat_bf16, self.flat_bf16_t, self.frag_shadow, self.frag_idx, self.flat_lo, self.lo_frag, self.lo_frag_idx)
-        shadow.bump_epoch()
+        self.derive_after_step()                                   # (the other derived copies: two launches behind the optimizer's)
 
     def _forward_backward(self, batch, batch_idx: int) -> torch.Tensor:
         shadow.bump_epoch()                    # every repack/shadow is re-made inside this step (and inside a capture)

@@ -18,6 +18,7 @@ from hulc2_amd import kernels as kn, synthetic as syn  # noqa: E402
 from hulc2_amd.compat import instantiate  # noqa: E402
 from hulc2_amd.config import default_model_config  # noqa: E402
 from hulc2_amd.lib import HulcKernelError  # noqa: E402
+from hulc2_amd.arena import WeightKeeper  # noqa: E402
 from hulc2_amd.trainer import ArenaTrainer  # noqa: E402
 
 
@@ -226,9 +227,9 @@ def test_training_step_under_lightning_amp_gives_the_same_bits(dev):
     assert all(v.dtype in (torch.float32, torch.int64, torch.int32) for v in out.values())
 
 
-def test_external_optimizer_loop_keeps_weight_copies_fresh_with_a_shadows_only_trainer(dev):
+def test_external_optimizer_loop_keeps_weight_copies_fresh_with_a_weight_keeper(dev):
     """Round 4: under an external optimizer (Lightning + torch.optim.Adam, hulc2/training.py:79-82) the first training-mode step installs
-    ArenaTrainer(shadows_only=True) — parameters re-homed into one arena, all kernel-side weight copies re-derived by a handful of launches
+    a WeightKeeper — parameters re-homed into one arena, all kernel-side weight copies re-derived by a handful of launches
     when the optimizer has stepped.  The loop's losses must be the bits of the lazy per-parameter path (HULC_NO_AUTO_SHADOWS=1), a nudge of
     ONE parameter must be seen, and copy.deepcopy(model) must not drag the keeper along."""
     import copy
@@ -259,7 +260,7 @@ def test_external_optimizer_loop_keeps_weight_copies_fresh_with_a_shadows_only_t
     assert "_hulc_shadow_keeper" not in m_lazy.__dict__
     m, batch, got = run(True)
     keeper = m.__dict__.get("_hulc_shadow_keeper")
-    assert keeper is not None and keeper.shadows_only and keeper.step_node and keeper.flat_g.numel() == keeper.total   # (round 5: the step node's gradient arena)
+    assert keeper is not None and type(keeper) is WeightKeeper and keeper.step_node and keeper.flat_g.numel() == keeper.total   # (round 5: the step node's gradient arena)
     assert got == want, (got, want)
     assert all(p.data_ptr() == keeper.flat_p.data_ptr() + 4 * off for p, off in zip(keeper.params, keeper.offsets))
     # one parameter nudged in place: the next step must run on the new value
@@ -278,5 +279,28 @@ def test_external_optimizer_loop_keeps_weight_copies_fresh_with_a_shadows_only_t
     # a full trainer takes over from the keeper
     from hulc2_amd.trainer import ArenaTrainer
     tr = ArenaTrainer(m)
-    assert not tr.shadows_only
+    assert isinstance(tr, ArenaTrainer)
     float(tr.step(batch, 0))
+
+
+def test_weight_keeper_and_trainer_lay_out_and_derive_alike(dev):
+    """WeightKeeper(step_node=True) and a single-rank ArenaTrainer run ONE plan (hulc2_amd/arena.py): on identically initialised models the
+    offsets, the remainder ranges and every device table are the same, byte for byte, and so is every derived arena after a
+    refresh_shadows().  The keeper has no optimizer state and no communication at all."""
+    keeper = WeightKeeper(_model(dev, 9), step_node=True)
+    tr = ArenaTrainer(_model(dev, 9))
+    assert type(keeper) is WeightKeeper and isinstance(tr, WeightKeeper)
+    assert not any(hasattr(keeper, a) for a in ("exp_avg", "exp_avg_sq", "comm", "buckets"))
+    assert keeper.offsets == tr.offsets and keeper.total == tr.total and keeper.lo_ranges == tr.lo_ranges and len(tr.lo_ranges) > 0
+    for name in ("tiles_t", "frag_idx", "lo_seg", "lo_frag_idx", "conv_table"):
+        a, b = getattr(keeper, name), getattr(tr, name)
+        assert a is not None and a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b), name
+    keeper.refresh_shadows()
+    tr.refresh_shadows()
+    torch.cuda.synchronize()
+    assert torch.equal(keeper.flat_p, tr.flat_p)
+    for name in ("flat_bf16", "flat_bf16_t", "frag_shadow", "flat_lo", "lo_frag", "conv_shadow"):
+        a, b = getattr(keeper, name), getattr(tr, name)
+        assert a is not None and a.shape == b.shape and torch.equal(a.view(torch.int16), b.view(torch.int16)), name      # (bits, not values)
+    keeper.close()
+    tr.close()

@@ -1,5 +1,5 @@
-"""Optimizer tail: Adam + the derived weight copies, old launch sequence (round 3: Adam, transposed tiles, fragment gather, residual, remainder
-gather, conv repack) against the fused one (round 4: Adam writes the remainders; derive_copies; gather_chunks2).  hipGraph replay of 10 repeats."""
+"""Optimizer tail: Adam + the derived weight copies, from scratch (WeightKeeper.refresh_shadows: cast, transposed tiles, fragment gather, residual,
+remainder gather, conv repack) against the fused tail (Adam writes the remainders; WeightKeeper.derive_after_step: two launches).  hipGraph replay of 10 repeats."""
 import sys
 
 import torch
@@ -22,18 +22,13 @@ st = kn.step_state(dev)
 
 def old():
     kn.adam_step(tr.flat_p, tr.flat_g, tr.exp_avg, tr.exp_avg_sq, tr.flat_bf16, tr.total, 2e-4, 0.9, 0.999, 1e-8, 0.0, 1, step_state_dev=st)
-    kn.transpose_bf16_tiles(tr.flat_bf16, tr.flat_bf16_t, tr.tiles_t)
-    kn.gather_chunks(tr.flat_bf16, tr.flat_bf16_t, tr.frag_shadow, tr.frag_idx)
-    kn.residual_bf16(tr.flat_p, tr.flat_bf16, tr.flat_lo, tr.lo_seg)
-    kn.gather_chunks(tr.flat_lo, None, tr.lo_frag, tr.lo_frag_idx)
-    kn.repack_conv_weights(tr.flat_p, tr.conv_shadow, tr.conv_table)
+    tr.refresh_shadows()                             # every copy from scratch (the cast included: Adam has written the bf16 shadow already)
 
 
 def new():
     kn.adam_step(tr.flat_p, tr.flat_g, tr.exp_avg, tr.exp_avg_sq, tr.flat_bf16, tr.total, 2e-4, 0.9, 0.999, 1e-8, 0.0, 1, step_state_dev=st,
                  lo=tr.flat_lo, lo_ranges=tr.lo_ranges)
-    kn.derive_copies(tr.flat_bf16, tr.flat_bf16_t, tr.tiles_t, tr.flat_p, tr.conv_shadow, tr.conv_table)
-    kn.gather_chunks2(tr.flat_bf16, tr.flat_bf16_t, tr.frag_shadow, tr.frag_idx, tr.flat_lo, tr.lo_frag, tr.lo_frag_idx)
+    tr.derive_after_step()
 
 
 def adam_only():
@@ -66,5 +61,5 @@ def timeit(fn, rep=10):
 
 print(f"params {tr.total / 1e6:.2f} M, lo ranges {tr.lo_ranges}")
 print(f"adam alone                     {timeit(adam_only):7.1f} us")
-print(f"round-3 sequence (6 launches)  {timeit(old):7.1f} us")
-print(f"round-4 sequence (3 launches)  {timeit(new):7.1f} us")
+print(f"from scratch (7 launches)      {timeit(old):7.1f} us")
+print(f"fused tail (3 launches)        {timeit(new):7.1f} us")
