@@ -17,6 +17,7 @@
 // summation order) or one thread per token; fp32 VALU throughout, libm-accurate exp/log.
 #include "hulc_common.h"
 #include "hulc_abi_internal.h"
+#include <stdio.h>
 
 namespace {
 
@@ -207,8 +208,12 @@ __global__ __launch_bounds__(256) void cat_kl_group_kernel(const float* __restri
     if (lane == 0) kl_group[g] = kl;
 }
 // one workgroup per segment (a modality of the batch): out[seg] = beta * mean over the segment's rows
-__global__ __launch_bounds__(1024) void cat_kl_sum_kernel(const float* __restrict__ kl_group, int NG_seg, int B_seg, float beta, float* __restrict__ out) {
+// beta_dev (optional, here and in the two backward kernels below): the KL weight read from device memory, one uniform 4-byte load per
+// thread before beta is used; the arithmetic after it is the scalar argument's, so *beta_dev == beta gives the same bits
+__global__ __launch_bounds__(1024) void cat_kl_sum_kernel(const float* __restrict__ kl_group, int NG_seg, int B_seg, float beta,
+                                                          const float* __restrict__ beta_dev, float* __restrict__ out) {
     __shared__ float sh[16];
+    if (beta_dev) beta = *beta_dev;
     const float* kg = kl_group + (long)blockIdx.x * NG_seg;
     float acc = 0.f;
     for (int g = threadIdx.x; g < NG_seg; g += blockDim.x) acc += kg[g];
@@ -217,11 +222,13 @@ __global__ __launch_bounds__(1024) void cat_kl_sum_kernel(const float* __restric
 }
 
 __global__ __launch_bounds__(256) void cat_kl_bwd_kernel(const float* __restrict__ pp, const float* __restrict__ pr,
-                                                         const float* __restrict__ kl_group, int B, int G, float beta, float mix,
-                                                         const float* __restrict__ gout, int nseg, float* __restrict__ dpp, float* __restrict__ dpr) {
+                                                         const float* __restrict__ kl_group, int B, int G, float beta,
+                                                         const float* __restrict__ beta_dev, float mix, const float* __restrict__ gout,
+                                                         int nseg, float* __restrict__ dpp, float* __restrict__ dpr) {
     const int lane = threadIdx.x & 31;
     const int g = blockIdx.x * (blockDim.x >> 5) + (threadIdx.x >> 5);
     if (g >= B * G) return;
+    if (beta_dev) beta = *beta_dev;
     const int Bs = B / nseg;                                      // rows per segment; gout[seg] is that segment's upstream gradient
     gout += (g / G) / Bs;
     B = Bs;
@@ -336,11 +343,13 @@ __global__ __launch_bounds__(128) void gauss_plan_row_kernel(const float* __rest
 __global__ __launch_bounds__(256) void gauss_plan_bwd_kernel(const float* __restrict__ pp, const float* __restrict__ pr,
                                                              const float* __restrict__ eps_in, unsigned long long seed,
                                                              const unsigned long long* __restrict__ seed_dev, int B, int P, float min_std,
-                                                             float beta, float mix, int nseg, const float* __restrict__ dplan,
-                                                             const float* __restrict__ gout, float* __restrict__ dpp, float* __restrict__ dpr) {
+                                                             float beta, const float* __restrict__ beta_dev, float mix, int nseg,
+                                                             const float* __restrict__ dplan, const float* __restrict__ gout,
+                                                             float* __restrict__ dpp, float* __restrict__ dpr) {
     const int NP = (P + 1) >> 1;
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)B * NP) return;
+    if (beta_dev) beta = *beta_dev;                    // (null whenever gout is: the sample-only backward does not use beta)
     const int b = (int)(i / NP), k = (int)(i % NP);
     if (seed_dev) seed ^= seed_dev[0];
     float z[2] = {0.f, 0.f};
@@ -631,21 +640,52 @@ extern "C" int hulc_mix_loss_bwd(const hulc_mix_desc* d, const float* y, const f
     return hulc_check_launch("hulc_mix_loss_bwd");
 }
 
-extern "C" int hulc_cat_kl_fwd(const float* pp, const float* pr, int B, int G, int CLS, float beta, int nseg, float* out, float* kl_group, void* stream) {
-    if (!pp || !pr || !out || !kl_group) return hulc_fail(-1, "hulc_cat_kl_fwd: null pointer");
-    if (CLS != 32) return hulc_fail(-2, "hulc_cat_kl_fwd: class_size must be 32 (one 32-lane sub-wave per category)");
-    if (nseg < 1 || B % nseg) return hulc_fail(-2, "hulc_cat_kl_fwd: the batch must split evenly into nseg segments");
+// every hulc_cat_kl_* / hulc_gauss_plan_* entry point ends in one of these four; beta_dev == nullptr is the scalar-beta path
+static int fail_named(int code, const char* name, const char* what) {       // "<entry point>: <what>" for checks shared by two entry points
+    char msg[256];
+    snprintf(msg, sizeof(msg), "%s: %s", name, what);
+    return hulc_fail(code, msg);
+}
+static int beta_dev_check(const float* beta_dev, const char* null_msg, const char* align_msg) {
+    if (!beta_dev) return hulc_fail(-1, null_msg);
+    if ((uintptr_t)beta_dev % 4) return hulc_fail(-4, align_msg);
+    return 0;
+}
+static int cat_kl_fwd_impl(const char* name, const float* pp, const float* pr, int B, int G, int CLS, float beta, const float* beta_dev, int nseg,
+                           float* out, float* kl_group, void* stream) {
+    if (!pp || !pr || !out || !kl_group) return fail_named(-1, name, "null pointer");
+    if (CLS != 32) return fail_named(-2, name, "class_size must be 32 (one 32-lane sub-wave per category)");
+    if (nseg < 1 || B % nseg) return fail_named(-2, name, "the batch must split evenly into nseg segments");
     cat_kl_group_kernel<<<(B * G + 7) / 8, 256, 0, (hipStream_t)stream>>>(pp, pr, B * G, kl_group);
-    cat_kl_sum_kernel<<<nseg, 1024, 0, (hipStream_t)stream>>>(kl_group, B / nseg * G, B / nseg, beta, out);
-    return hulc_check_launch("hulc_cat_kl_fwd");
+    cat_kl_sum_kernel<<<nseg, 1024, 0, (hipStream_t)stream>>>(kl_group, B / nseg * G, B / nseg, beta, beta_dev, out);
+    return hulc_check_launch(name);
+}
+static int cat_kl_bwd_impl(const char* name, const float* pp, const float* pr, const float* kl_group, int B, int G, int CLS, float beta,
+                           const float* beta_dev, float mix, const float* gout, int nseg, float* dpp, float* dpr, void* stream) {
+    if (!pp || !pr || !kl_group || !gout || !dpp || !dpr) return fail_named(-1, name, "null pointer");
+    if (CLS != 32) return fail_named(-2, name, "class_size must be 32");
+    if (nseg < 1 || B % nseg) return fail_named(-2, name, "the batch must split evenly into nseg segments");
+    cat_kl_bwd_kernel<<<(B * G + 7) / 8, 256, 0, (hipStream_t)stream>>>(pp, pr, kl_group, B, G, beta, beta_dev, mix, gout, nseg, dpp, dpr);
+    return hulc_check_launch(name);
+}
+extern "C" int hulc_cat_kl_fwd(const float* pp, const float* pr, int B, int G, int CLS, float beta, int nseg, float* out, float* kl_group, void* stream) {
+    return cat_kl_fwd_impl("hulc_cat_kl_fwd", pp, pr, B, G, CLS, beta, nullptr, nseg, out, kl_group, stream);
 }
 extern "C" int hulc_cat_kl_bwd(const float* pp, const float* pr, const float* kl_group, int B, int G, int CLS, float beta, float mix,
                                const float* gout, int nseg, float* dpp, float* dpr, void* stream) {
-    if (!pp || !pr || !kl_group || !gout || !dpp || !dpr) return hulc_fail(-1, "hulc_cat_kl_bwd: null pointer");
-    if (CLS != 32) return hulc_fail(-2, "hulc_cat_kl_bwd: class_size must be 32");
-    if (nseg < 1 || B % nseg) return hulc_fail(-2, "hulc_cat_kl_bwd: the batch must split evenly into nseg segments");
-    cat_kl_bwd_kernel<<<(B * G + 7) / 8, 256, 0, (hipStream_t)stream>>>(pp, pr, kl_group, B, G, beta, mix, gout, nseg, dpp, dpr);
-    return hulc_check_launch("hulc_cat_kl_bwd");
+    return cat_kl_bwd_impl("hulc_cat_kl_bwd", pp, pr, kl_group, B, G, CLS, beta, nullptr, mix, gout, nseg, dpp, dpr, stream);
+}
+extern "C" int hulc_cat_kl_fwd_sched(const float* pp, const float* pr, int B, int G, int CLS, float beta, int nseg, float* out, float* kl_group,
+                                     const float* beta_dev, void* stream) {
+    int rc = beta_dev_check(beta_dev, "hulc_cat_kl_fwd_sched: null beta_dev", "hulc_cat_kl_fwd_sched: beta_dev must be 4-byte aligned");
+    if (rc) return rc;
+    return cat_kl_fwd_impl("hulc_cat_kl_fwd_sched", pp, pr, B, G, CLS, beta, beta_dev, nseg, out, kl_group, stream);
+}
+extern "C" int hulc_cat_kl_bwd_sched(const float* pp, const float* pr, const float* kl_group, int B, int G, int CLS, float beta, float mix,
+                                     const float* gout, int nseg, float* dpp, float* dpr, const float* beta_dev, void* stream) {
+    int rc = beta_dev_check(beta_dev, "hulc_cat_kl_bwd_sched: null beta_dev", "hulc_cat_kl_bwd_sched: beta_dev must be 4-byte aligned");
+    if (rc) return rc;
+    return cat_kl_bwd_impl("hulc_cat_kl_bwd_sched", pp, pr, kl_group, B, G, CLS, beta, beta_dev, mix, gout, nseg, dpp, dpr, stream);
 }
 extern "C" int hulc_plan_sample_fwd(const float* logits, const long* idx_in, unsigned long long seed, const unsigned long long* seed_dev,
                                     int NG, int CLS, long* idx_out, float* plan, void* stream) {
@@ -661,28 +701,62 @@ extern "C" int hulc_plan_sample_bwd(const float* logits, const float* dplan, int
     return hulc_check_launch("hulc_plan_sample_bwd");
 }
 
+static int gauss_plan_fwd_impl(const char* name, const float* pp, const float* pr, const float* eps_in, unsigned long long seed,
+                               const unsigned long long* seed_dev, int B, int P, float min_std, float beta, const float* beta_dev, int nseg,
+                               float* plan, float* eps_out, float* out, float* kl_row, void* stream) {
+    if (!plan && !eps_out && !out) return fail_named(-1, name, "nothing to compute (plan, eps_out and out are all null)");
+    if (!pr || (out && (!pp || !kl_row))) return fail_named(-1, name, "null pointer");
+    if (B < 1 || P < 1) return fail_named(-2, name, "needs B >= 1 and plan_features >= 1");
+    if (out && (nseg < 1 || B % nseg)) return fail_named(-2, name, "the batch must split evenly into nseg segments");
+    gauss_plan_row_kernel<<<B, 128, 0, (hipStream_t)stream>>>(pp, pr, eps_in, seed, seed_dev, P, min_std, plan, eps_out, out ? kl_row : nullptr);
+    if (out) cat_kl_sum_kernel<<<nseg, 1024, 0, (hipStream_t)stream>>>(kl_row, B / nseg, B / nseg, beta, beta_dev, out);
+    return hulc_check_launch(name);
+}
+static int gauss_plan_bwd_impl(const char* name, const float* pp, const float* pr, const float* eps_in, unsigned long long seed,
+                               const unsigned long long* seed_dev, int B, int P, float min_std, float beta, const float* beta_dev, float mix,
+                               int nseg, const float* dplan, const float* gout, float* dpp, float* dpr, void* stream) {
+    if (!dplan && !gout) return fail_named(-1, name, "nothing to compute (dplan and gout are both null)");
+    if (!pr || !dpr || (gout && (!pp || !dpp))) return fail_named(-1, name, "null pointer");
+    if (B < 1 || P < 1) return fail_named(-2, name, "needs B >= 1 and plan_features >= 1");
+    if (gout && (nseg < 1 || B % nseg)) return fail_named(-2, name, "the batch must split evenly into nseg segments");
+    const long n = (long)B * ((P + 1) / 2);
+    gauss_plan_bwd_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(pp, pr, eps_in, seed, seed_dev, B, P, min_std, beta,
+                                                                                        gout ? beta_dev : nullptr, mix, gout ? nseg : 1, dplan,
+                                                                                        gout, dpp, dpr);
+    return hulc_check_launch(name);
+}
 extern "C" int hulc_gauss_plan_fwd(const float* pp, const float* pr, const float* eps_in, unsigned long long seed,
                                    const unsigned long long* seed_dev, int B, int P, float min_std, float beta, int nseg, float* plan,
                                    float* eps_out, float* out, float* kl_row, void* stream) {
-    if (!plan && !eps_out && !out) return hulc_fail(-1, "hulc_gauss_plan_fwd: nothing to compute (plan, eps_out and out are all null)");
-    if (!pr || (out && (!pp || !kl_row))) return hulc_fail(-1, "hulc_gauss_plan_fwd: null pointer");
-    if (B < 1 || P < 1) return hulc_fail(-2, "hulc_gauss_plan_fwd: needs B >= 1 and plan_features >= 1");
-    if (out && (nseg < 1 || B % nseg)) return hulc_fail(-2, "hulc_gauss_plan_fwd: the batch must split evenly into nseg segments");
-    gauss_plan_row_kernel<<<B, 128, 0, (hipStream_t)stream>>>(pp, pr, eps_in, seed, seed_dev, P, min_std, plan, eps_out, out ? kl_row : nullptr);
-    if (out) cat_kl_sum_kernel<<<nseg, 1024, 0, (hipStream_t)stream>>>(kl_row, B / nseg, B / nseg, beta, out);
-    return hulc_check_launch("hulc_gauss_plan_fwd");
+    return gauss_plan_fwd_impl("hulc_gauss_plan_fwd", pp, pr, eps_in, seed, seed_dev, B, P, min_std, beta, nullptr, nseg, plan, eps_out, out,
+                               kl_row, stream);
 }
 extern "C" int hulc_gauss_plan_bwd(const float* pp, const float* pr, const float* eps_in, unsigned long long seed,
                                    const unsigned long long* seed_dev, int B, int P, float min_std, float beta, float mix, int nseg,
                                    const float* dplan, const float* gout, float* dpp, float* dpr, void* stream) {
-    if (!dplan && !gout) return hulc_fail(-1, "hulc_gauss_plan_bwd: nothing to compute (dplan and gout are both null)");
-    if (!pr || !dpr || (gout && (!pp || !dpp))) return hulc_fail(-1, "hulc_gauss_plan_bwd: null pointer");
-    if (B < 1 || P < 1) return hulc_fail(-2, "hulc_gauss_plan_bwd: needs B >= 1 and plan_features >= 1");
-    if (gout && (nseg < 1 || B % nseg)) return hulc_fail(-2, "hulc_gauss_plan_bwd: the batch must split evenly into nseg segments");
-    const long n = (long)B * ((P + 1) / 2);
-    gauss_plan_bwd_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(pp, pr, eps_in, seed, seed_dev, B, P, min_std, beta, mix,
-                                                                                        gout ? nseg : 1, dplan, gout, dpp, dpr);
-    return hulc_check_launch("hulc_gauss_plan_bwd");
+    return gauss_plan_bwd_impl("hulc_gauss_plan_bwd", pp, pr, eps_in, seed, seed_dev, B, P, min_std, beta, nullptr, mix, nseg, dplan, gout, dpp,
+                               dpr, stream);
+}
+// beta_dev is required only where beta is read: with the KL part (out / gout given)
+extern "C" int hulc_gauss_plan_fwd_sched(const float* pp, const float* pr, const float* eps_in, unsigned long long seed,
+                                         const unsigned long long* seed_dev, int B, int P, float min_std, float beta, int nseg, float* plan,
+                                         float* eps_out, float* out, float* kl_row, const float* beta_dev, void* stream) {
+    if (out) {
+        int rc = beta_dev_check(beta_dev, "hulc_gauss_plan_fwd_sched: null beta_dev", "hulc_gauss_plan_fwd_sched: beta_dev must be 4-byte aligned");
+        if (rc) return rc;
+    }
+    return gauss_plan_fwd_impl("hulc_gauss_plan_fwd_sched", pp, pr, eps_in, seed, seed_dev, B, P, min_std, beta, out ? beta_dev : nullptr, nseg,
+                               plan, eps_out, out, kl_row, stream);
+}
+extern "C" int hulc_gauss_plan_bwd_sched(const float* pp, const float* pr, const float* eps_in, unsigned long long seed,
+                                         const unsigned long long* seed_dev, int B, int P, float min_std, float beta, float mix, int nseg,
+                                         const float* dplan, const float* gout, float* dpp, float* dpr, const float* beta_dev, void* stream) {
+    if (gout) {
+        int rc = beta_dev_check(beta_dev, "hulc_gauss_plan_bwd_sched: null beta_dev", "hulc_gauss_plan_bwd_sched: beta_dev must be 4-byte aligned");
+        if (rc) return rc;
+    }
+    return gauss_plan_bwd_impl("hulc_gauss_plan_bwd_sched", pp, pr, eps_in, seed, seed_dev, B, P, min_std, beta, beta_dev, mix, nseg, dplan, gout,
+                               dpp, dpr, stream);
 }
 
 static size_t clip_smem(int M) { return ((size_t)4 * M * (CLIP_D + 1) + (size_t)M * (M + 1) + 5 * (size_t)M) * sizeof(float); }

@@ -44,6 +44,16 @@ def _c(t: torch.Tensor) -> torch.Tensor:
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _kl_beta(beta):
+    """the KL weight of a KL node -> (by-value float, device scalar or None).  A one-element fp32 tensor (Hulc2.set_kl_beta's device word) goes
+    to the *_sched kernels, which read it when they RUN: the node keeps the tensor itself, never its value, so a captured forward + backward
+    follows what the host writes into it between replays.  Contract: a value written between a forward and its backward is undefined —
+    set_kl_beta is called between steps."""
+    if isinstance(beta, torch.Tensor):
+        return 0.0, beta
+    return float(beta), None
+
+
 def _act_dtype() -> torch.dtype:
     """Storage type of the conv-stack activations and their gradients: the MFMA kernels round operands to the
     compute type while staging anyway, so in bf16 mode keeping them bf16 in HBM halves the traffic at identical
@@ -729,10 +739,12 @@ def layer_norm_cat(xs, norms, dim: int):
 class PlanSampleKLFn(torch.autograd.Function):
     """The posterior's two consumers in one node: straight-through plan sample (hulc2.py:235-237) + balanced KL against the prior
     (hulc2.py:444-466) -> (plan, idx, kl (nseg,)).  Backward adds the sample's gradient onto the KL's in the sampling kernel (`accumulate`):
-    no gradient fan-in add on the (rows, 1024) logits."""
+    no gradient fan-in add on the (rows, 1024) logits.  beta: a float, or a one-element fp32 device tensor read by the kernels (see _kl_beta:
+    written between steps only, never between this node's forward and its backward)."""
 
     @staticmethod
-    def forward(ctx, pp, pr, idx_in, G: int, CLS: int, seed: int, beta: float, mix: float, nseg: int):
+    def forward(ctx, pp, pr, idx_in, G: int, CLS: int, seed: int, beta, mix: float, nseg: int):
+        beta, beta_dev = _kl_beta(beta)
         pp, pr = _c(pp), _c(pr)
         B = pr.shape[0]
         plan = _f32(B, G * CLS, like=pr)
@@ -740,9 +752,9 @@ class PlanSampleKLFn(torch.autograd.Function):
         kn.plan_sample_fwd(pr, _c(idx_in) if idx_in is not None else None, seed, B * G, CLS, idx, plan)
         out = _f32(nseg, like=pp)
         klg = _f32(B * G, like=pp)
-        kn.cat_kl_fwd(pp, pr, B, G, CLS, beta, out, klg, nseg)
+        kn.cat_kl_fwd(pp, pr, B, G, CLS, beta, out, klg, nseg, beta_dev=beta_dev)
         ctx.save_for_backward(pp, pr, klg)
-        ctx.meta = (B, G, CLS, beta, mix, nseg)
+        ctx.meta = (B, G, CLS, beta, beta_dev, mix, nseg)
         ctx.mark_non_differentiable(idx)
         ctx.set_materialize_grads(False)
         return plan, idx, out
@@ -750,11 +762,11 @@ class PlanSampleKLFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dplan, _didx=None, gkl=None):
         pp, pr, klg = ctx.saved_tensors
-        B, G, CLS, beta, mix, nseg = ctx.meta
+        B, G, CLS, beta, beta_dev, mix, nseg = ctx.meta
         dpp = dpr = None
         if gkl is not None:
             dpp, dpr = torch.empty_like(pp), torch.empty_like(pr)
-            kn.cat_kl_bwd(pp, pr, klg, B, G, CLS, beta, mix, _c(gkl.reshape(nseg)), dpp, dpr, nseg)
+            kn.cat_kl_bwd(pp, pr, klg, B, G, CLS, beta, mix, _c(gkl.reshape(nseg)), dpp, dpr, nseg, beta_dev=beta_dev)
         if dplan is not None:
             if dpr is None:
                 dpr = torch.empty_like(pr)
@@ -769,32 +781,34 @@ class GaussPlanKLFn(torch.autograd.Function):
     """PlanSampleKLFn for the continuous plan (conf/model/distribution/continuous.yaml): pp_raw / pr_raw are the heads' raw (B, 2P) outputs
     [mean | r], std = softplus(r) + 1e-4 (distributions.py:55-59) -> (plan (B, P), kl (nseg,)).  Forward: the row kernel + the segment sum;
     backward: ONE launch, the sample's gradient summed onto the KL's inside it.  The noise is never kept: the backward regenerates it from
-    (seed, device step word), or reads the injected eps_in."""
+    (seed, device step word), or reads the injected eps_in.  beta: a float, or a one-element fp32 device tensor read by the kernels (see
+    _kl_beta: written between steps only, never between this node's forward and its backward)."""
 
     @staticmethod
-    def forward(ctx, pp, pr, eps_in, seed: int, beta: float, mix: float, nseg: int):
+    def forward(ctx, pp, pr, eps_in, seed: int, beta, mix: float, nseg: int):
+        beta, beta_dev = _kl_beta(beta)
         pp, pr = _c(pp), _c(pr)
         B, P = pr.shape[0], pr.shape[1] // 2
         eps_in = _c(eps_in) if eps_in is not None else None
         plan = _f32(B, P, like=pr)
         out = _f32(nseg, like=pp)
         klr = _f32(B, like=pp)
-        kn.gauss_plan_fwd(pp, pr, eps_in, seed, B, P, beta, nseg, plan, None, out, klr)
+        kn.gauss_plan_fwd(pp, pr, eps_in, seed, B, P, beta, nseg, plan, None, out, klr, beta_dev=beta_dev)
         ctx.save_for_backward(pp, pr, eps_in)
-        ctx.meta = (B, P, seed, beta, mix, nseg)
+        ctx.meta = (B, P, seed, beta, beta_dev, mix, nseg)
         ctx.set_materialize_grads(False)
         return plan, out
 
     @staticmethod
     def backward(ctx, dplan, gkl=None):
         pp, pr, eps_in = ctx.saved_tensors
-        B, P, seed, beta, mix, nseg = ctx.meta
+        B, P, seed, beta, beta_dev, mix, nseg = ctx.meta
         if dplan is None and gkl is None:
             return None, None, None, None, None, None, None
         dpr = torch.empty_like(pr)
         dpp = torch.empty_like(pp) if gkl is not None else None
         kn.gauss_plan_bwd(pp, pr, eps_in, seed, B, P, beta, mix, nseg, _c(dplan) if dplan is not None else None,
-                          _c(gkl.reshape(nseg)) if gkl is not None else None, dpp, dpr)
+                          _c(gkl.reshape(nseg)) if gkl is not None else None, dpp, dpr, beta_dev=beta_dev if gkl is not None else None)
         return dpp, dpr, None, None, None, None, None
 
 
@@ -824,25 +838,28 @@ class GaussPlanSampleFn(torch.autograd.Function):
 
 @_scoped
 class GaussKLFn(torch.autograd.Function):
-    """CatKLFn for the continuous plan: balanced KL of hulc2.py:444-466 on the raw (B, 2P) head outputs of prior (pp) and posterior (pr)"""
+    """CatKLFn for the continuous plan: balanced KL of hulc2.py:444-466 on the raw (B, 2P) head outputs of prior (pp) and posterior (pr).
+    beta: a float, or a one-element fp32 device tensor read by the kernels (see _kl_beta: written between steps only, never between this
+    node's forward and its backward)."""
 
     @staticmethod
-    def forward(ctx, pp, pr, beta: float, mix: float, nseg: int = 1):
+    def forward(ctx, pp, pr, beta, mix: float, nseg: int = 1):
+        beta, beta_dev = _kl_beta(beta)
         pp, pr = _c(pp), _c(pr)
         B, P = pr.shape[0], pr.shape[1] // 2
         out = _f32(nseg, like=pp)
         klr = _f32(B, like=pp)
-        kn.gauss_plan_fwd(pp, pr, None, 0, B, P, beta, nseg, None, None, out, klr)
+        kn.gauss_plan_fwd(pp, pr, None, 0, B, P, beta, nseg, None, None, out, klr, beta_dev=beta_dev)
         ctx.save_for_backward(pp, pr)
-        ctx.meta = (B, P, beta, mix, nseg)
+        ctx.meta = (B, P, beta, beta_dev, mix, nseg)
         return out[0] if nseg == 1 else out
 
     @staticmethod
     def backward(ctx, g):
         pp, pr = ctx.saved_tensors
-        B, P, beta, mix, nseg = ctx.meta
+        B, P, beta, beta_dev, mix, nseg = ctx.meta
         dpp, dpr = torch.empty_like(pp), torch.empty_like(pr)
-        kn.gauss_plan_bwd(pp, pr, None, 0, B, P, beta, mix, nseg, None, _c(g.reshape(nseg)), dpp, dpr)
+        kn.gauss_plan_bwd(pp, pr, None, 0, B, P, beta, mix, nseg, None, _c(g.reshape(nseg)), dpp, dpr, beta_dev=beta_dev)
         return dpp, dpr, None, None, None
 
 
@@ -1504,26 +1521,28 @@ class MixLossFn(torch.autograd.Function):
 
 @_scoped
 class CatKLFn(torch.autograd.Function):
-    """KL balancing of hulc2.py:444-466 on (B, G*32) logits of prior (pp) and posterior (pr)."""
+    """KL balancing of hulc2.py:444-466 on (B, G*32) logits of prior (pp) and posterior (pr).  beta: a float, or a one-element fp32 device
+    tensor read by the kernels (see _kl_beta: written between steps only, never between this node's forward and its backward)."""
 
     @staticmethod
-    def forward(ctx, pp, pr, G: int, CLS: int, beta: float, mix: float, nseg: int = 1):
+    def forward(ctx, pp, pr, G: int, CLS: int, beta, mix: float, nseg: int = 1):
         """nseg > 1: the rows are nseg equal segments (modalities batched together) -> (nseg,) losses, each its own mean"""
+        beta, beta_dev = _kl_beta(beta)
         pp, pr = _c(pp), _c(pr)
         B = pp.shape[0]
         out = _f32(nseg, like=pp)
         klg = _f32(B * G, like=pp)
-        kn.cat_kl_fwd(pp, pr, B, G, CLS, beta, out, klg, nseg)
+        kn.cat_kl_fwd(pp, pr, B, G, CLS, beta, out, klg, nseg, beta_dev=beta_dev)
         ctx.save_for_backward(pp, pr, klg)
-        ctx.meta = (B, G, CLS, beta, mix, nseg)
+        ctx.meta = (B, G, CLS, beta, beta_dev, mix, nseg)
         return out[0] if nseg == 1 else out
 
     @staticmethod
     def backward(ctx, g):
         pp, pr, klg = ctx.saved_tensors
-        B, G, CLS, beta, mix, nseg = ctx.meta
+        B, G, CLS, beta, beta_dev, mix, nseg = ctx.meta
         dpp, dpr = torch.empty_like(pp), torch.empty_like(pr)
-        kn.cat_kl_bwd(pp, pr, klg, B, G, CLS, beta, mix, _c(g.reshape(nseg)), dpp, dpr, nseg)
+        kn.cat_kl_bwd(pp, pr, klg, B, G, CLS, beta, mix, _c(g.reshape(nseg)), dpp, dpr, nseg, beta_dev=beta_dev)
         return dpp, dpr, None, None, None, None, None
 
 

@@ -1273,12 +1273,26 @@ def mix_loss_bwd(y, act, gout, dy, ld_dy, T, A, n_mix, num_classes, ld, log_scal
     _call("hulc_mix_loss_bwd", _c.byref(d), y, act, gout, dy, ld_dy)
 
 
-def cat_kl_fwd(pp, pr, B, G, CLS, beta, out, kl_group, nseg=1):
-    _call("hulc_cat_kl_fwd", pp, pr, B, G, CLS, beta, nseg, out, kl_group)
+def _beta_dev_ok(name, beta_dev, device):
+    """beta_dev: one-element fp32 tensor on the operands' device holding the KL weight (the hulc_*_sched entry points); the scalar `beta` is
+    then ignored and a captured launch follows whatever the host writes into beta_dev between replays"""
+    if not isinstance(beta_dev, torch.Tensor) or beta_dev.dtype != torch.float32 or beta_dev.numel() != 1 or beta_dev.device != device:
+        raise _L.HulcKernelError(f"{name}: beta_dev is a one-element fp32 tensor on the operands' device")
 
 
-def cat_kl_bwd(pp, pr, kl_group, B, G, CLS, beta, mix, gout, dpp, dpr, nseg=1):
-    _call("hulc_cat_kl_bwd", pp, pr, kl_group, B, G, CLS, beta, mix, gout, nseg, dpp, dpr)
+def cat_kl_fwd(pp, pr, B, G, CLS, beta, out, kl_group, nseg=1, beta_dev=None):
+    """beta_dev: see _beta_dev_ok (hulc_cat_kl_fwd_sched)"""
+    if beta_dev is None:
+        return _call("hulc_cat_kl_fwd", pp, pr, B, G, CLS, beta, nseg, out, kl_group)
+    _beta_dev_ok("cat_kl_fwd", beta_dev, _first_device(pp, pr, out))
+    _call("hulc_cat_kl_fwd_sched", pp, pr, B, G, CLS, beta, nseg, out, kl_group, beta_dev)
+
+
+def cat_kl_bwd(pp, pr, kl_group, B, G, CLS, beta, mix, gout, dpp, dpr, nseg=1, beta_dev=None):
+    if beta_dev is None:
+        return _call("hulc_cat_kl_bwd", pp, pr, kl_group, B, G, CLS, beta, mix, gout, nseg, dpp, dpr)
+    _beta_dev_ok("cat_kl_bwd", beta_dev, _first_device(pp, pr, dpp))
+    _call("hulc_cat_kl_bwd_sched", pp, pr, kl_group, B, G, CLS, beta, mix, gout, nseg, dpp, dpr, beta_dev)
 
 
 def plan_sample_fwd(logits, idx_in, seed, NG, CLS, idx_out, plan):
@@ -1302,17 +1316,26 @@ def _first_device(*ts):
     raise _L.HulcKernelError("no tensor operand")
 
 
-def gauss_plan_fwd(pp, pr, eps_in, seed, B, P, beta, nseg, plan, eps_out, out, kl_row, min_std=GAUSS_MIN_STD):
+def gauss_plan_fwd(pp, pr, eps_in, seed, B, P, beta, nseg, plan, eps_out, out, kl_row, min_std=GAUSS_MIN_STD, beta_dev=None):
     """continuous latent plan: sample (plan / eps_out) from the head `pr` and / or balanced KL (out, kl_row) against `pp`; parts are switched
-    off by None.  Without eps_in the noise follows the device step word: a replayed graph draws fresh noise."""
-    word = step_state(_first_device(pr, pp, plan, eps_out, out)) if eps_in is None else None
-    _call("hulc_gauss_plan_fwd", pp, pr, eps_in, seed, word, B, P, min_std, beta, nseg, plan, eps_out, out, kl_row)
+    off by None.  Without eps_in the noise follows the device step word: a replayed graph draws fresh noise.
+    beta_dev: see _beta_dev_ok (hulc_gauss_plan_fwd_sched)"""
+    dev = _first_device(pr, pp, plan, eps_out, out)
+    word = step_state(dev) if eps_in is None else None
+    if beta_dev is None:
+        return _call("hulc_gauss_plan_fwd", pp, pr, eps_in, seed, word, B, P, min_std, beta, nseg, plan, eps_out, out, kl_row)
+    _beta_dev_ok("gauss_plan_fwd", beta_dev, dev)
+    _call("hulc_gauss_plan_fwd_sched", pp, pr, eps_in, seed, word, B, P, min_std, beta, nseg, plan, eps_out, out, kl_row, beta_dev)
 
 
-def gauss_plan_bwd(pp, pr, eps_in, seed, B, P, beta, mix, nseg, dplan, gout, dpp, dpr, min_std=GAUSS_MIN_STD):
+def gauss_plan_bwd(pp, pr, eps_in, seed, B, P, beta, mix, nseg, dplan, gout, dpp, dpr, min_std=GAUSS_MIN_STD, beta_dev=None):
     """one launch: dpr = KL part (gout) + sample part (dplan), dpp = KL part; the noise is regenerated from (seed, step word) or read from eps_in"""
-    word = step_state(_first_device(pr, pp, dplan, gout, dpr)) if eps_in is None else None
-    _call("hulc_gauss_plan_bwd", pp, pr, eps_in, seed, word, B, P, min_std, beta, mix, nseg, dplan, gout, dpp, dpr)
+    dev = _first_device(pr, pp, dplan, gout, dpr)
+    word = step_state(dev) if eps_in is None else None
+    if beta_dev is None:
+        return _call("hulc_gauss_plan_bwd", pp, pr, eps_in, seed, word, B, P, min_std, beta, mix, nseg, dplan, gout, dpp, dpr)
+    _beta_dev_ok("gauss_plan_bwd", beta_dev, dev)
+    _call("hulc_gauss_plan_bwd_sched", pp, pr, eps_in, seed, word, B, P, min_std, beta, mix, nseg, dplan, gout, dpp, dpr, beta_dev)
 
 
 def clip_loss_fwd(im, tx, use, logit_scale, M, D, out, row0=0):

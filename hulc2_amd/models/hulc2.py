@@ -331,7 +331,7 @@ class Hulc2(LightningModule):
             cont = self.dist.dist == "continuous"
             inj = [db.get("plan_eps" if cont else "plan_idx") for _, db in mods]
             inj_all = torch.cat(inj, dim=0) if all(i is not None for i in inj) else None
-            plan_all, _, kls = self.dist.rsample_plan_and_kl(pp_all, pr_all, 0xA11CE, None if cont else inj_all, self.kl_beta,
+            plan_all, _, kls = self.dist.rsample_plan_and_kl(pp_all, pr_all, 0xA11CE, None if cont else inj_all, self._kl_beta_arg(),
                                                              self.kl_balancing_mix, len(mods), eps=inj_all if cont else None)
             kl_stacked = kls
             act_losses = self.action_decoder.loss_stacked(plan_all, emb_dec_t if fan else emb_all, goal_all,
@@ -405,10 +405,61 @@ class Hulc2(LightningModule):
 
     def compute_kl_loss(self, pp_state: State, pr_state: State) -> torch.Tensor:
         """hulc2.py:444-466."""
-        return self.dist.kl_balanced(pp_state, pr_state, self.kl_beta, self.kl_balancing_mix)
+        return self.dist.kl_balanced(pp_state, pr_state, self._kl_beta_arg(), self.kl_balancing_mix)
+
+    _kl_beta_dev = None            # one fp32 element on the parameters' device once set_kl_beta() was called on a GPU model (device-beta mode)
 
     def set_kl_beta(self, kl_beta):
+        """hulc2.py `set_kl_beta` (driven every epoch by hulc2/utils/kl_callbacks.py).  `self.kl_beta` stays the Python float.  On a GPU model
+        the value (rounded to fp32 as the kernel argument would be) is also written into a one-element device tensor with one stream-ordered
+        fill on the current stream — no host synchronisation — and from the first call on the KL kernels read THAT word instead of taking beta
+        by value: a captured step follows the annealing without a recapture.  The tensor is a plain attribute (no buffer, no parameter: the
+        checkpoint keys are unchanged).  Call it between steps: a value written between a forward and its backward is undefined."""
+        dev = self._param_device()
+        if dev is not None and dev.type == "cuda":
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("Hulc2.set_kl_beta was called while a stream capture is in progress: the fill would become a node of the "
+                                   "graph and every replay would write this value back — set the KL weight between captures / replays")
+            self._kl_beta_fill(dev, kl_beta)
         self.kl_beta = kl_beta
+
+    def _param_device(self):
+        p = next(self.parameters(), None)
+        return p.device if p is not None else None
+
+    _kl_beta_word = None           # the fp32 value last written into _kl_beta_dev (host copy: comparing costs no synchronisation)
+
+    def _kl_beta_fill(self, dev, kl_beta):
+        import ctypes
+        if self._kl_beta_dev is None or self._kl_beta_dev.device != dev:
+            self._kl_beta_dev = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._kl_beta_word = ctypes.c_float(float(kl_beta)).value
+        self._kl_beta_dev.fill_(self._kl_beta_word)
+
+    def _kl_beta_arg(self):
+        """what the distribution's KL entry points get: the float (by value, as before any set_kl_beta call and on a CPU model) or, in
+        device-beta mode, the device word.  The word is written again here when it no longer holds fp32(self.kl_beta) — set_kl_beta ran while
+        the model was on the CPU and the model came back — and made anew when the model has moved to another device."""
+        if self._kl_beta_dev is None:
+            return self.kl_beta
+        dev = self._param_device()
+        if dev is None or dev.type != "cuda":
+            return self.kl_beta
+        import ctypes
+        if self._kl_beta_dev.device != dev or self._kl_beta_word != ctypes.c_float(float(self.kl_beta)).value:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("Hulc2: the device word of kl_beta is out of date inside a stream capture; call set_kl_beta on the GPU model "
+                                   "before capturing")
+            self._kl_beta_fill(dev, self.kl_beta)
+        return self._kl_beta_dev
+
+    @property
+    def kl_beta_on_device(self) -> bool:
+        """device-beta mode: set_kl_beta() has been called on a GPU model and the model is on a GPU now — the KL kernels read the device word"""
+        if self._kl_beta_dev is None:
+            return False
+        dev = self._param_device()
+        return dev is not None and dev.type == "cuda"
 
     def clip_auxiliary_loss(self, seq_vis_feat, encoded_lang, use_for_aux_loss, row0: int = 0):
         """hulc2.py:472-508; rows with use_for_aux_loss == False are excluded inside the kernel.  row0 > 0: the features are the stacked rows of

@@ -179,8 +179,12 @@ class StepNode:
     # ---- dispatch -----------------------------------------------------------------------------------------------------------------
     def _signature(self, leaves) -> tuple:
         m = self._model()
+        # the KL weight: baked into the captured launches while it is a by-value kernel argument — part of the signature; in device-beta mode
+        # (Hulc2.set_kl_beta was called) the launches read the model's device word, and one constant marker stands for every value: the first
+        # set_kl_beta costs at most one recapture, later ones none
+        kl_beta = "device" if getattr(m, "kl_beta_on_device", False) else float(m.kl_beta)
         return (tuple((path, tuple(t.shape), t.dtype, t.device) for path, t in leaves), kn.base_mode(), kn.get_compute(),
-                os.environ.get("HULC_FP32_SITES"), kn.concurrent_streams(), kn.fork_branches(), float(m.kl_beta), float(m.kl_balancing_mix),
+                os.environ.get("HULC_FP32_SITES"), kn.concurrent_streams(), kn.fork_branches(), kl_beta, float(m.kl_balancing_mix),
                 float(m.clip_auxiliary_loss_beta), bool(m.use_clip_auxiliary_loss))
 
     def usable(self) -> bool:

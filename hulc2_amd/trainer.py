@@ -623,6 +623,32 @@ class ArenaTrainer(WeightKeeper):
         if self._lr_lambda is not None:
             self.set_lr(float(self.base_lr) * self._lr_lambda(self._opt_steps))
 
+    # ---- KL annealing: the KL weight as a device scalar the captured KL launches read (Hulc2.set_kl_beta) --------------------------------
+    _kl_captured = None            # the by-value KL weight baked into the captured graphs; None: no graphs, or they read the model's device word
+    _kl_schedule = None            # the attached annealing rule (set_kl_schedule)
+
+    def set_kl_beta(self, beta: float) -> None:
+        """The KL weight of the following steps (reference: hulc2/utils/kl_callbacks.py -> pl_module.set_kl_beta every epoch).  Forwards to the
+        model, which on a GPU writes a device scalar the KL kernels read — a stream-ordered one-element fill, no host synchronisation, and
+        captured graphs follow it.  The call that switches the model to that mode drops graphs captured with the weight as a kernel
+        argument (as set_lr does for the learning rate); later calls never drop one."""
+        self.model.set_kl_beta(beta)
+        if self._kl_captured is not None and getattr(self.model, "kl_beta_on_device", False):
+            self._kl_captured = None
+            self.graph_fb = self.graph_enc = self.graph_opt = None
+
+    def set_kl_schedule(self, fn) -> None:
+        """fn(epoch) -> KL weight (hulc2_amd.kl_schedule.linear / sigmoid / constant, or any callable); begin_epoch applies it.  The rule is
+        not state (as the lr schedule's function is not): a resumed run attaches the same one."""
+        self._kl_schedule = fn
+
+    def begin_epoch(self, epoch: int) -> None:
+        """what the reference's on_train_epoch_start callbacks do for a Lightning loop: set the KL weight of this epoch"""
+        if self._kl_schedule is not None:
+            beta = self._kl_schedule(int(epoch))
+            if beta is not None:                                  # (kl_schedule.constant(): the weight is never set, as in the reference)
+                self.set_kl_beta(beta)
+
     def close(self) -> None:
         """Detach this trainer from the model (WeightKeeper.close: load hook, gradient sinks) and remove its per-parameter hooks."""
         super().close()
@@ -809,10 +835,17 @@ class ArenaTrainer(WeightKeeper):
             with torch.cuda.graph(self.graph_opt, pool=self.graph_fb.pool(), stream=side, **mode):
                 self.optimizer_step()
         torch.cuda.synchronize()
+        # a KL weight taken by value is baked into graph_fb: replay() refuses to run it under another one
+        kl = getattr(self.model, "kl_beta", None)
+        self._kl_captured = None if (kl is None or getattr(self.model, "kl_beta_on_device", False)) else float(kl)
 
     def replay(self) -> torch.Tensor:
         if self.graph_fb is None:
             raise RuntimeError("ArenaTrainer.replay: no captured graphs (never captured, or dropped after a barrier-kernel fault): call capture(batch)")
+        if self._kl_captured is not None and float(self.model.kl_beta) != self._kl_captured:
+            raise RuntimeError(f"ArenaTrainer.replay: the graphs were captured with kl_beta = {self._kl_captured!r} as a kernel argument and cannot "
+                               f"see model.kl_beta = {float(self.model.kl_beta)!r}: set the weight through ArenaTrainer.set_kl_beta (the captured "
+                               "launches then read a device scalar) and call capture() again")
         with self.gpu_section():
             self.graph_fb.replay()
         if self.graph_enc is not None:

@@ -100,6 +100,12 @@ class Distribution:
 
     # ---- fused hot-path entry points -----------------------------------------------------------
     @staticmethod
+    def _beta(kl_beta):
+        """kl_beta as the KL nodes take it: a one-element fp32 tensor (Hulc2.set_kl_beta's device word, read by the kernels) passes through
+        as it is, anything else becomes a Python float"""
+        return kl_beta if isinstance(kl_beta, torch.Tensor) else float(kl_beta)
+
+    @staticmethod
     def _raw(state: ContState) -> torch.Tensor:
         """the head output [mean | r] behind a continuous state (the fused kernels apply softplus themselves)"""
         raw = getattr(state, "raw", None)
@@ -119,23 +125,23 @@ class Distribution:
             return HF.GaussPlanSampleFn.apply(self._raw(state), eps, int(seed)), None
         return HF.PlanSampleFn.apply(state.logit, idx, self.category_size, self.class_size, int(seed))
 
-    def kl_balanced(self, pp_state: State, pr_state: State, kl_beta: float, mix: float) -> torch.Tensor:
+    def kl_balanced(self, pp_state: State, pr_state: State, kl_beta, mix: float) -> torch.Tensor:
         """Hulc2.compute_kl_loss (hulc2.py:444-466) in one kernel pair."""
         if self.dist == "continuous":
-            return HF.GaussKLFn.apply(self._raw(pp_state), self._raw(pr_state), float(kl_beta), float(mix))
-        return HF.CatKLFn.apply(pp_state.logit, pr_state.logit, self.category_size, self.class_size, float(kl_beta), float(mix))
+            return HF.GaussKLFn.apply(self._raw(pp_state), self._raw(pr_state), self._beta(kl_beta), float(mix))
+        return HF.CatKLFn.apply(pp_state.logit, pr_state.logit, self.category_size, self.class_size, self._beta(kl_beta), float(mix))
 
-    def kl_balanced_segments(self, pp_state: State, pr_state: State, kl_beta: float, mix: float, nseg: int) -> torch.Tensor:
+    def kl_balanced_segments(self, pp_state: State, pr_state: State, kl_beta, mix: float, nseg: int) -> torch.Tensor:
         """the same loss for nseg modalities stacked on the batch axis: (nseg,) values, each the mean over its own rows"""
         if self.dist == "continuous":
-            out = HF.GaussKLFn.apply(self._raw(pp_state), self._raw(pr_state), float(kl_beta), float(mix), int(nseg))
+            out = HF.GaussKLFn.apply(self._raw(pp_state), self._raw(pr_state), self._beta(kl_beta), float(mix), int(nseg))
             return out.reshape(1) if nseg == 1 else out
-        return HF.CatKLFn.apply(pp_state.logit, pr_state.logit, self.category_size, self.class_size, float(kl_beta), float(mix), int(nseg))
+        return HF.CatKLFn.apply(pp_state.logit, pr_state.logit, self.category_size, self.class_size, self._beta(kl_beta), float(mix), int(nseg))
 
-    def rsample_plan_and_kl(self, pp_state: State, pr_state: State, seed: int, idx, kl_beta: float, mix: float, nseg: int = 1, eps=None):
+    def rsample_plan_and_kl(self, pp_state: State, pr_state: State, seed: int, idx, kl_beta, mix: float, nseg: int = 1, eps=None):
         """rsample_plan + kl_balanced_segments as one autograd node -> (plan, idx, kl (nseg,))"""
         if self.dist == "continuous":
-            plan, kl = HF.GaussPlanKLFn.apply(self._raw(pp_state), self._raw(pr_state), eps, int(seed), float(kl_beta), float(mix), int(nseg))
+            plan, kl = HF.GaussPlanKLFn.apply(self._raw(pp_state), self._raw(pr_state), eps, int(seed), self._beta(kl_beta), float(mix), int(nseg))
             return plan, None, kl
-        return HF.PlanSampleKLFn.apply(pp_state.logit, pr_state.logit, idx, self.category_size, self.class_size, int(seed), float(kl_beta),
+        return HF.PlanSampleKLFn.apply(pp_state.logit, pr_state.logit, idx, self.category_size, self.class_size, int(seed), self._beta(kl_beta),
                                        float(mix), int(nseg))

@@ -252,6 +252,25 @@ int hulc_gauss_plan_fwd(const float* pp, const float* pr, const float* eps_in, u
 int hulc_gauss_plan_bwd(const float* pp, const float* pr, const float* eps_in, unsigned long long seed, const unsigned long long* seed_dev,
                         int B, int P, float min_std, float beta, float mix, int nseg, const float* dplan, const float* gout, float* dpp,
                         float* dpr, void* stream);
+/* (added under ABI 7 — new symbols only; every earlier prototype and hulc_abi_version() are unchanged.)  The four KL entry points above with
+ * the KL WEIGHT read from device memory: beta_dev (4-byte aligned device float) replaces the scalar `beta`, which is then ignored.  Every
+ * thread of the kernels that use beta (the segment sum and the two backward kernels — the same kernels as the scalar entry points, beta_dev
+ * is a nullable parameter of theirs) reads it once with a plain load before its first use; the arithmetic after the load is the scalar
+ * path's (beta * sum / rows, gout[seg] * beta / rows), so *beta_dev == beta gives bit-identical results.  A captured launch therefore follows
+ * the KL annealing the host writes into beta_dev between replays (reference: hulc2/utils/kl_callbacks.py:5-60 -> Hulc2.set_kl_beta every
+ * epoch).  A value written between a forward and its backward is undefined.  beta_dev is required (-1 when null, -4 when misaligned; nothing
+ * is launched) wherever beta is read: always for hulc_cat_kl_*_sched, with out / gout given for hulc_gauss_plan_*_sched (the sample-only
+ * calls take none).  All other arguments as in the scalar twins. */
+int hulc_cat_kl_fwd_sched(const float* pp, const float* pr, int B, int G, int CLS, float beta, int nseg, float* out, float* kl_group,
+                          const float* beta_dev, void* stream);
+int hulc_cat_kl_bwd_sched(const float* pp, const float* pr, const float* kl_group, int B, int G, int CLS, float beta, float mix,
+                          const float* gout, int nseg, float* dpp, float* dpr, const float* beta_dev, void* stream);
+int hulc_gauss_plan_fwd_sched(const float* pp, const float* pr, const float* eps_in, unsigned long long seed,
+                              const unsigned long long* seed_dev, int B, int P, float min_std, float beta, int nseg, float* plan,
+                              float* eps_out, float* out, float* kl_row, const float* beta_dev, void* stream);
+int hulc_gauss_plan_bwd_sched(const float* pp, const float* pr, const float* eps_in, unsigned long long seed,
+                              const unsigned long long* seed_dev, int B, int P, float min_std, float beta, float mix, int nseg,
+                              const float* dplan, const float* gout, float* dpp, float* dpr, const float* beta_dev, void* stream);
 /* CLIP-style symmetric contrastive loss on projected features im/tx [M][32] restricted to rows with
  * use[m] != 0 (hulc2.py:472-508); dscale = d loss / d logit_scale.  out[2] = {loss, number of rows with use != 0 (1 when none): the weight
  * `batch_size["aux_lang"]` the step logs the loss with, hulc2.py:391-394 — a device value, no host synchronisation}. */
