@@ -9,7 +9,7 @@ import torch
 
 from . import lib as _L
 
-F32, BF16, F16 = 0, 1, 2
+F32, BF16, F16 = (_L.DEFINES["HULC_" + n] for n in ("F32", "BF16", "F16"))      # the header's dtype codes
 _COMPUTE = {"bf16": BF16, "fp32": F32, "f32": F32}
 _compute_mode = BF16
 

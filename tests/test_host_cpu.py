@@ -266,6 +266,129 @@ def test_integration_doc_binding_lists_every_gemm_field():
     assert "raise `NotImplementedError`" not in doc or "validation" not in doc.split("raise `NotImplementedError`")[0][-200:]
 
 
+def test_struct_parser_accepts_the_header_forms_and_refuses_the_rest():
+    """lib.parse_structs on literal snippets: every accepted form once, against _fields_ written out by hand; one refusal per form the
+    header does not use; a `;` inside a comment of a struct body"""
+    from hulc2_amd import lib
+    i, l, f, u, p = ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_ulonglong, ctypes.c_void_p
+    got = lib.parse_structs("""
+        #define HULC_N 3   /* a length; with a semicolon */
+        typedef struct hulc_in_item {
+            const void* a; float* b;     /* two statements; one line */
+            const float *c, *d;
+            int M, N, K; long ld;
+            float s;   // a line comment; with a semicolon
+            unsigned long long seed;
+            const unsigned long long* seed_dev;
+            int* e; void *g, **h;
+        } hulc_in_item;
+        typedef struct { int n; hulc_in_item items[HULC_N]; hulc_in_item two[2]; float *y, z; } hulc_out_desc;
+        int hulc_f(const hulc_out_desc* d);
+    """)
+    assert list(got) == ["InItem", "OutDesc"]
+    InItem, OutDesc = got.values()
+    assert issubclass(InItem, ctypes.Structure) and issubclass(OutDesc, ctypes.Structure)
+    assert InItem.__name__ == "InItem" and OutDesc.__name__ == "OutDesc"
+    assert InItem._fields_ == [("a", p), ("b", p), ("c", p), ("d", p), ("M", i), ("N", i), ("K", i), ("ld", l), ("s", f), ("seed", u),
+                               ("seed_dev", p), ("e", p), ("g", p), ("h", p)]
+    names, types = zip(*OutDesc._fields_)
+    assert names == ("n", "items", "two", "y", "z") and types[0] is i and types[3] is p and types[4] is f
+    assert types[1]._type_ is InItem and types[1]._length_ == 3 and types[2]._type_ is InItem and types[2]._length_ == 2
+    assert lib.parse_structs("typedef struct hulc_rnn_wave_desc { int S; /* steps; not rows */ long ld; } hulc_rnn_wave_desc;")[
+        "RnnWaveDesc"]._fields_ == [("S", i), ("ld", l)]
+    item = "typedef struct { int a; } hulc_item; "
+    for refused in ("typedef struct { double a; } hulc_x;",
+                    "typedef struct { char a; } hulc_x;",
+                    item + "typedef struct { hulc_item one; } hulc_x;",                       # a struct by value
+                    "typedef struct { hulc_item v[2]; } hulc_x; " + item,                     # used before it is declared
+                    "typedef struct { int a : 3; } hulc_x;",
+                    item + "typedef struct { hulc_item v[2][2]; } hulc_x;",
+                    "typedef struct { int v[4]; } hulc_x;",
+                    item + "typedef struct { hulc_item v[HULC_LEN]; } hulc_x;",               # a length that is not #defined
+                    "#define HULC_LEN (2)\n" + item + "typedef struct { hulc_item v[HULC_LEN]; } hulc_x;",   # ... or not as a decimal
+                    "typedef union { int a; float b; } hulc_x;",
+                    "typedef struct { union { int a; float b; } u; } hulc_x;"):
+        with pytest.raises(lib.HulcKernelError):
+            lib.parse_structs(refused)
+
+
+# the ten descriptor structs in header order: (C name, name in hulc2_amd.lib, sizeof from a `cc -std=c99` build on x86-64 Linux; clang agrees)
+_STRUCT_SIZES = [("hulc_gemm_desc", "GemmDesc", 208), ("hulc_conv_desc", "ConvDesc", 144), ("hulc_mix_desc", "MixDesc", 64),
+                 ("hulc_txl_attn_desc", "TxlAttnDesc", 224), ("hulc_txl_block_layer", "TxlBlockLayer", 360),
+                 ("hulc_txl_block_desc", "TxlBlockDesc", 1560), ("hulc_mlp_chain_layer", "MlpChainLayer", 80),
+                 ("hulc_mlp_chain_desc", "MlpChainDesc", 672), ("hulc_wgrad_item", "WgradItem", 88), ("hulc_rnn_wave_desc", "RnnWaveDesc", 240)]
+
+
+def _c_compiler():
+    """the first of cc, gcc, clang on the PATH, else the clang that ships beside the hipcc the library is built with"""
+    import shutil
+    from hulc2_amd import build
+    for name in ("cc", "gcc", "clang"):
+        if shutil.which(name):
+            return shutil.which(name)
+    hipcc = shutil.which(build.HIPCC)
+    clang = Path(hipcc).resolve().parent.parent / "lib" / "llvm" / "bin" / "clang" if hipcc else None
+    return str(clang) if clang and clang.exists() else None
+
+
+def test_ctypes_layout_matches_a_c_compiler(tmp_path):
+    """sizeof of every descriptor struct, offsetof and sizeof of every field, as a C99 compiler lays include/hulc2_amd.h out == what ctypes
+    gives the classes of hulc2_amd.lib; the field lists come from this file's _parse_struct.  No compiler is a failure, not a skip."""
+    import subprocess
+    from hulc2_amd import lib
+    header = (ROOT / "include" / "hulc2_amd.h").read_text()
+    assert [c for c, _, _ in _STRUCT_SIZES] == re.findall(r"^\}\s*(hulc_\w+)\s*;", header, re.M)
+    fields = {c: [n for n, _ in _parse_struct(header, c)] for c, _, _ in _STRUCT_SIZES}
+    prints = []
+    for c, names in fields.items():
+        prints.append(f'printf("{c} %zu\\n", sizeof({c}));')
+        prints += [f'printf("{c}.{n} %zu %zu\\n", offsetof({c}, {n}), sizeof((({c}*)0)->{n}));' for n in names]
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "hulc2_amd.h"\nint main(void) {\n' + "\n".join(prints) + "\nreturn 0;\n}\n")
+    cc = _c_compiler()
+    assert cc, "no C compiler: none of cc, gcc, clang on the PATH and no clang beside hulc2_amd.build.HIPCC"
+    r = subprocess.run([cc, "-std=c99", "-I", str(ROOT / "include"), "-x", "c", str(src), "-o", str(tmp_path / "layout")],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([str(tmp_path / "layout")], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr[-3000:]
+    c_says = {line.split()[0]: tuple(map(int, line.split()[1:])) for line in r.stdout.splitlines()}
+    assert len(c_says) == len(_STRUCT_SIZES) + sum(map(len, fields.values()))
+    for c, py, size in _STRUCT_SIZES:
+        cls = getattr(lib, py)
+        assert [n for n, _ in cls._fields_] == fields[c], c
+        assert ctypes.sizeof(cls) == c_says[c][0] == size, (c, ctypes.sizeof(cls), c_says[c], size)
+        for n in fields[c]:
+            assert (getattr(cls, n).offset, getattr(cls, n).size) == c_says[f"{c}.{n}"], (c, n, getattr(cls, n), c_says[f"{c}.{n}"])
+    for c, py, n, off in (("hulc_gemm_desc", "GemmDesc", "drop_seed", 152), ("hulc_conv_desc", "ConvDesc", "y_bf16", 136),
+                          ("hulc_txl_block_desc", "TxlBlockDesc", "layers", 120)):
+        assert getattr(getattr(lib, py), n).offset == c_says[f"{c}.{n}"][0] == off, (c, n)
+
+
+def test_constants_come_from_the_header():
+    from hulc2_amd import kernels, lib
+    header = (ROOT / "include" / "hulc2_amd.h").read_text()
+    defined = {k: int(v) for k, v in re.findall(r"^#define\s+(HULC_\w+)\s+(\d+)\s*$", header, re.M)}
+    assert lib.TXL_MAX_LAYERS == 4 == defined["HULC_TXL_MAX_LAYERS"]
+    assert (kernels.F32, kernels.BF16, kernels.F16) == (0, 1, 2) == (defined["HULC_F32"], defined["HULC_BF16"], defined["HULC_F16"])
+    assert all(type(v) is int for v in (lib.TXL_MAX_LAYERS, kernels.F32, kernels.BF16, kernels.F16))
+    assert lib.TxlBlockDesc.layers.size == 4 * ctypes.sizeof(lib.TxlBlockLayer) and lib.MlpChainDesc.layers.size == 8 * ctypes.sizeof(lib.MlpChainLayer)
+    assert dict(lib.TxlBlockDesc._fields_)["layers"]._length_ == 4 and dict(lib.MlpChainDesc._fields_)["layers"]._length_ == 8
+
+
+def test_descriptor_classes_exist_at_import_without_load():
+    """a fresh interpreter: after `import hulc2_amd.lib`, load() not called, the ten descriptor classes are plain module globals (no module
+    __getattr__: kernels.py instantiates one per launch)"""
+    import subprocess
+    code = ("import ctypes, sys; sys.path.insert(0, sys.argv[1]); import hulc2_amd.lib as lib\n"
+            "assert lib._lib is None and '__getattr__' not in vars(lib)\n"
+            "for n in sys.argv[2:]:\n"
+            "    assert isinstance(vars(lib)[n], type) and issubclass(vars(lib)[n], ctypes.Structure) and vars(lib)[n]._fields_, n\n"
+            "assert lib._lib is None\n")
+    r = subprocess.run([sys.executable, "-c", code, str(ROOT), *[py for _, py, _ in _STRUCT_SIZES]], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-3000:]
+
+
 def test_fused_heads_follow_the_configured_mixture_count():
     """the fused head layout is derived from out_features x n_mixtures, not assumed to be 6 x 10"""
     from hulc2_amd.models.decoders.logistic_decoder_rnn import LogisticDecoderRNN
