@@ -676,14 +676,19 @@ static void launch_relu_bits(const hulc_conv_desc* d, const void* y, hipStream_t
 }
 
 extern "C" int hulc_conv2d_fwd(const hulc_conv_desc* d, const void* x, const void* w, const float* bias, void* y, void* stream) {
+    hulc_conv_path_clear();
     int rc = validate(d, "fwd"); if (rc) return rc;
     if (!x || !w || !y) return hulc_fail(-1, "hulc_conv2d_fwd: null pointer");
     GatherP g; fill_gather(g, d);
-    bool bits_pending = false;
     if (d->relu_bits && (d->Cout % 32 || !d->relu)) return hulc_fail(-4, "hulc_conv2d_fwd: relu_bits needs relu and Cout % 32 == 0");
     if (d->y_bf16 && ((d->y_dtype != HULC_F32 && d->y_dtype != HULC_F16) || d->relu_bits || ((uintptr_t)d->y_bf16 % 16)))
         return hulc_fail(-4, "hulc_conv2d_fwd: y_bf16 goes with an fp32 / fp16 output, no sign planes, 16-byte aligned");
     if (d->y_dtype == HULC_F16 && !d->y_bf16) return hulc_fail(-4, "hulc_conv2d_fwd: an fp16 output is the twin of a bf16 map (y_bf16)");
+    const bool conv1_geom = d->compute == HULC_BF16 && d->x_nchw && (d->x_dtype == HULC_F32 || d->x_u8_nhwc) && d->Cin == 3 && d->Cout == 32 && d->KH == 8 &&
+                            d->KW == 8 && d->stride == 4;
+    // (no other kernel knows these fields: ignoring x2 would read N frames from a tensor that holds n_split of them)
+    if (!conv1_geom && d->x2) return hulc_fail(-6, "hulc_conv2d_fwd: a second frame tensor (x2) is taken by the conv1 band kernel only");
+    if (!conv1_geom && d->w_lo) return hulc_fail(-6, "hulc_conv2d_fwd: split operands (w_lo) are taken by the conv1 band kernel only");
     g.X = x; g.Wt = w; g.bias = bias; g.Y = y; g.mask = nullptr; g.mask_dtype = HULC_F32; g.mask_scale = 1.f; g.add = nullptr; g.add_dtype = HULC_F32;
     g.y_dtype = d->y_dtype; g.relu = d->relu;
     g.y_sn = (long)g.OH * g.OW * d->Cout; g.y_sy = (long)g.OW * d->Cout; g.y_sx = d->Cout;
@@ -694,23 +699,28 @@ extern "C" int hulc_conv2d_fwd(const hulc_conv_desc* d, const void* x, const voi
             cOH[c] = g.OH; cOW[c] = g.OW; cyo[c] = 0; cco[c] = 32 * c; cw0[c] = 32 * c;
             for (int t = 0; t < 16; ++t) ctap[c * 16 + t] = t < d->KH * d->KW ? g.w_tap_off[t] : 0;
         }
+        // the band kernel's epilogue writes the planes of a bf16 output; for any other launch that leaves them (an fp32 output, or a launch whose
+        // plane preconditions failed and that is repeated without them) the second pass over y follows
+        unsigned* planes = (d->relu && d->y_dtype == HULC_BF16) ? (unsigned*)d->relu_bits : nullptr;
+        void* y16 = d->y_dtype != HULC_BF16 ? d->y_bf16 : nullptr;
         rc = hulc_conv_band_dispatch(d->Cin, nset, d->KH, d->KW, d->stride, x, d->x_dtype, d->N, d->H, d->W, 0, 0, g.x_sn, g.x_sy, g.x_sx,
                                      y, d->y_dtype, g.y_sn, g.y_sy, g.y_sx, w, d->w_dtype, g.ldw, bias, nullptr, HULC_F32, d->relu, nset,
-                                     cOH, cOW, cyo, cco, cw0, ctap, nullptr, (d->relu && d->y_dtype == HULC_BF16) ? (unsigned*)d->relu_bits : nullptr, nullptr,
-                                     d->Cout, (d->y_dtype != HULC_BF16 ? d->y_bf16 : nullptr), (hipStream_t)stream);
-        if (rc == 1 && d->relu_bits)            // (the planes' preconditions failed, not the geometry: the same launch without them)
+                                     cOH, cOW, cyo, cco, cw0, ctap, nullptr, planes, nullptr, d->Cout, y16, (hipStream_t)stream);
+        if (rc == 1 && planes) {                // (the planes' preconditions failed, not the geometry: the same launch without them)
+            planes = nullptr;
             rc = hulc_conv_band_dispatch(d->Cin, nset, d->KH, d->KW, d->stride, x, d->x_dtype, d->N, d->H, d->W, 0, 0, g.x_sn, g.x_sy, g.x_sx,
                                          y, d->y_dtype, g.y_sn, g.y_sy, g.y_sx, w, d->w_dtype, g.ldw, bias, nullptr, HULC_F32, d->relu, nset,
-                                         cOH, cOW, cyo, cco, cw0, ctap, nullptr, nullptr, nullptr, 0, (d->y_dtype != HULC_BF16 ? d->y_bf16 : nullptr), (hipStream_t)stream), bits_pending = d->relu_bits != nullptr;
-        else bits_pending = false;
+                                         cOH, cOW, cyo, cco, cw0, ctap, nullptr, nullptr, nullptr, 0, y16, (hipStream_t)stream);
+        }
         if (rc < 0) return rc;
-        if (rc == 0) { if (bits_pending) launch_relu_bits(d, y, (hipStream_t)stream); return hulc_check_launch("hulc_conv2d_fwd(band)"); }
-        bits_pending = d->relu_bits != nullptr;
+        if (rc == 0) {
+            if (d->relu_bits && !planes) { launch_relu_bits(d, y, (hipStream_t)stream); hulc_conv_path_append(" +relu_bits_pass"); }
+            return hulc_check_launch("hulc_conv2d_fwd(band)");
+        }
     }
     if (d->y_dtype == HULC_F16)
         return hulc_fail(-6, "hulc_conv2d_fwd: the fp16 twin is stored by the direct-to-LDS band kernel only (bf16 compute, NHWC 23 x 23 x 64 -> 64, 3 x 3)");
-    if (d->compute == HULC_BF16 && d->x_nchw && (d->x_dtype == HULC_F32 || d->x_u8_nhwc) && d->Cin == 3 && d->Cout == 32 && d->KH == 8 && d->KW == 8 &&
-        d->stride == 4) {
+    if (conv1_geom) {
         unsigned* planes = (d->relu && d->y_dtype == HULC_BF16) ? (unsigned*)d->relu_bits : nullptr;
         rc = hulc_conv1_band_dispatch((const float*)x, w, d->w_dtype, g.ldw, bias, y, d->y_dtype, d->relu, d->N, d->H, d->W, d->x_u8_nhwc, d->aug_pad,
                                       d->aug_shift, d->frame_index, planes, d->w_lo, d->x2, d->n_split, d->x_slot, d->x2_slot, d->conv1_slots, (hipStream_t)stream);
@@ -718,7 +728,10 @@ extern "C" int hulc_conv2d_fwd(const hulc_conv_desc* d, const void* x, const voi
         if (rc != 0 && d->x2) return hulc_fail(-6, "hulc_conv2d_fwd: a second frame tensor (x2) is taken by the conv1 band kernel only");
         if (rc != 0 && (d->x_slot || d->x2_slot)) return hulc_fail(-6, "hulc_conv2d_fwd: frame slots are taken by the conv1 band kernel only");
         if (rc != 0 && d->w_lo) return hulc_fail(-6, "hulc_conv2d_fwd: split operands (w_lo) are taken by the conv1 band kernel only");
-        if (rc == 0) { if (d->relu_bits && !planes) launch_relu_bits(d, y, (hipStream_t)stream); return hulc_check_launch("hulc_conv2d_fwd(conv1 band)"); }
+        if (rc == 0) {
+            if (d->relu_bits && !planes) { launch_relu_bits(d, y, (hipStream_t)stream); hulc_conv_path_append(" +relu_bits_pass"); }
+            return hulc_check_launch("hulc_conv2d_fwd(conv1 band)");
+        }
     }
     if (d->x_u8_nhwc) return hulc_fail(-6, "hulc_conv2d_fwd: uint8 frames are consumed by the conv1 band kernel only (bf16 compute, 3 -> 32, 8x8 stride 4, W % 4 == 0)");
     if (d->x_slot || d->x2_slot) return hulc_fail(-6, "hulc_conv2d_fwd: frame slots are taken by the conv1 band kernel only");
@@ -728,6 +741,7 @@ extern "C" int hulc_conv2d_fwd(const hulc_conv_desc* d, const void* x, const voi
         rc = hulc_cast_f32_to_bf16((const float*)y, d->y_bf16, (long)d->N * g.OH * g.OW * d->Cout, stream);
         if (rc) return rc;
     }
+    hulc_conv_path_set("gather<%s>%s%s", d->compute == HULC_F32 ? "f32" : "bf16", d->relu_bits ? " +relu_bits_pass" : "", d->y_bf16 ? " +cast_pass" : "");
     return hulc_check_launch("hulc_conv2d_fwd");
 }
 
@@ -735,6 +749,7 @@ extern "C" int hulc_conv2d_fwd(const hulc_conv_desc* d, const void* x, const voi
 // folded in, bias = the folded shift, optional residual `add` (same shape / dtype as y) summed before the ReLU.
 extern "C" int hulc_conv2d_padded_fwd(const hulc_conv_desc* d, int pad, const void* x, const void* w, const float* bias, const void* add, void* y,
                                       void* stream) {
+    hulc_conv_path_clear();
     if (!d || !x || !w || !y) return hulc_fail(-1, "hulc_conv2d_padded_fwd: null pointer");
     if (d->x_nchw || d->x_u8_nhwc) return hulc_fail(-7, "hulc_conv2d_padded_fwd: NHWC activations only");
     if (d->N <= 0 || d->stride <= 0 || pad < 0 || d->H + 2 * pad < d->KH || d->W + 2 * pad < d->KW) return hulc_fail(-2, "hulc_conv2d_padded_fwd: bad geometry");
@@ -774,6 +789,7 @@ extern "C" int hulc_conv2d_padded_fwd(const hulc_conv_desc* d, int pad, const vo
         if (rc == 0) return hulc_check_launch("hulc_conv2d_padded_fwd(band)");
     }
     if (d->compute == HULC_F32) launch_gather<float>(g, (hipStream_t)stream); else launch_gather<bf16_t>(g, (hipStream_t)stream);
+    hulc_conv_path_set("gather<%s>", d->compute == HULC_F32 ? "f32" : "bf16");
     return hulc_check_launch("hulc_conv2d_padded_fwd");
 }
 
@@ -809,6 +825,7 @@ extern "C" int hulc_r3m_stem_fwd(const void* xp, const void* w, const float* bia
 // dX (NHWC [N][H][W][Cin]) from dY (NHWC [N][OH][OW][Cout]); wt = weights permuted to [Cin][KH][KW][Cout].
 // relu_src (optional, same shape as dX): dX *= (relu_src > 0)  — the ReLU that produced this conv's input.
 extern "C" int hulc_conv2d_bwd_data(const hulc_conv_desc* d, const void* dy, const void* wt, void* dx, const void* relu_src, void* stream) {
+    hulc_conv_path_clear();
     if (!d || !dy || !wt || !dx) return hulc_fail(-1, "hulc_conv2d_bwd_data: null pointer");
     if (d->x_nchw) return hulc_fail(-7, "hulc_conv2d_bwd_data: only NHWC activations have a data gradient on this path");
     if (log2_exact(d->Cout) < 3) return hulc_fail(-4, "conv bwd_data: Cout must be a power of two >= 8");
@@ -845,6 +862,7 @@ extern "C" int hulc_conv2d_bwd_data(const hulc_conv_desc* d, const void* dy, con
             if (brc == 0) return hulc_check_launch("hulc_conv2d_bwd_data(band)");
         }
     }
+    int launches = 0;
     for (int py = 0; py < s; ++py)
         for (int px = 0; px < s; ++px) {
             GatherP g;
@@ -877,7 +895,9 @@ extern "C" int hulc_conv2d_bwd_data(const hulc_conv_desc* d, const void* dy, con
                 if (d->y_dtype != HULC_F32 || d->w_dtype != HULC_F32) return hulc_fail(-6, "conv bwd_data: f32 compute requires f32 operands");
                 launch_gather<float>(g, (hipStream_t)stream);
             } else launch_gather<bf16_t>(g, (hipStream_t)stream);
+            ++launches;
         }
+    hulc_conv_path_set("gather<%s> launches=%d", d->compute == HULC_F32 ? "f32" : "bf16", launches);
     return hulc_check_launch("hulc_conv2d_bwd_data");
 }
 
@@ -904,6 +924,7 @@ extern "C" long hulc_conv2d_bwd_weight_workspace(const hulc_conv_desc* d) {
 // dW ([Cout][K] in the forward k order) and db ([Cout]) from x and dY; ws = workspace of
 // hulc_conv2d_bwd_weight_workspace() bytes.
 extern "C" int hulc_conv2d_bwd_weight(const hulc_conv_desc* d, const void* x, const void* dy, float* dw, float* db, void* ws, void* stream) {
+    hulc_conv_path_clear();
     int rc = validate(d, "bwd_weight"); if (rc) return rc;
     if (!x || !dy || !dw || !ws) return hulc_fail(-1, "hulc_conv2d_bwd_weight: null pointer");
     if (d->compute == HULC_BF16) {                           // LDS-band kernel (conv_wgrad_band.hip) for the geometries it covers
@@ -938,5 +959,6 @@ extern "C" int hulc_conv2d_bwd_weight(const hulc_conv_desc* d, const void* x, co
     const int perm_c = (d->dw_oihw && !d->x_nchw) ? d->Cin : 0;
     reduce_partials_kernel<<<(unsigned)((R + 63) / 64), 1024, 0, s>>>(p.partial_w, dw, (int)P, R, d->dw_accumulate, perm_c, d->KH * d->KW);
     if (db) reduce_partials_kernel<<<1, 1024, 0, s>>>(p.partial_b, db, (int)P, d->Cout, d->dw_accumulate, 0, 0);
+    hulc_conv_path_set("wgrad_gather f32=%d P=%ld", d->compute == HULC_F32 ? 1 : 0, P);
     return hulc_check_launch("hulc_conv2d_bwd_weight");
 }

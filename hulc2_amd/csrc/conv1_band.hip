@@ -361,6 +361,7 @@ int launch_conv1(C1P& p, int slots, hipStream_t s) {
     if (x3) conv1_band_kernel<XCH, false, true><<<grid, 512, (size_t)lds_of(R), s>>>(p);
     else if (p.u8) conv1_band_kernel<UX, true><<<grid, 512, (size_t)lds_of(R), s>>>(p);
     else conv1_band_kernel<XCH, false><<<grid, 512, (size_t)lds_of(R), s>>>(p);
+    hulc_conv_path_set("conv1_band u8=%d x3=%d R=%d grid=%d", p.u8 ? 1 : 0, x3, R, grid);
     return 0;
 }
 

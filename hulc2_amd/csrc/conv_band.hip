@@ -335,6 +335,10 @@ int launch_band_x(BandP& p, hipStream_t s) {
     if (lds < wbytes) lds = wbytes;
     const int per = (nunits + 255) / 256;                    // balanced persistent grid
     const int grid = (nunits + per - 1) / per;
+    auto report = [&]() {
+        hulc_conv_path_set("band_x<%d,%d,%d,%d,%d> xf32=%d bits=%d multi=%d R=%d F=%d units=%d grid=%d", C, NSET, TH, TW, S, (int)XF32, BITS, F > 1 ? 1 : 0,
+                           R, F, nunits, grid);
+    };
     if (F > 1) {
         auto kern = conv_band_kernel<C, NSET, TH, TW, S, MAXCH, true, XF32, BITS>;
         static bool attr_set = false;
@@ -343,6 +347,7 @@ int launch_band_x(BandP& p, hipStream_t s) {
             attr_set = true;
         }
         kern<<<grid, 512, lds, s>>>(p, nullptr);
+        report();
     } else {
         auto kern = conv_band_kernel<C, NSET, TH, TW, S, MAXCH, false, XF32, BITS>;
         static bool attr_set = false;
@@ -363,6 +368,7 @@ int launch_band_x(BandP& p, hipStream_t s) {
         } else
 #endif
         kern<<<grid, 512, lds, s>>>(p, nullptr);
+        report();
     }
     return 0;
 }
@@ -563,6 +569,7 @@ int launch_band_glds(BandP& p, hipStream_t s) {
     const int nunits = p.Nimg, per = (nunits + 255) / 256, grid = (nunits + per - 1) / per;
     auto kern = conv_band_glds_kernel<NSET, TH, TW, BITS, PAD>;
     kern<<<grid, 512, lds, s>>>(p);
+    hulc_conv_path_set("band_glds<%d,%d,%d> bits=%d pad=%d units=%d grid=%d", NSET, TH, TW, BITS, (int)PAD, nunits, grid);
     return 0;
 }
 

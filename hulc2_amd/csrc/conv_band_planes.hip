@@ -296,6 +296,7 @@ int launch_planes(BandP& p, hipStream_t s) {
     }
 #endif
     conv_band_planes_kernel<NSET, TH, TW, HIN, WIN, BITS, PAD><<<grid, 512, 0, s>>>(p);
+    hulc_conv_path_set("band_planes<%d,%d> bits=%d units=%d grid=%d", HIN, WIN, BITS, nunits, grid);
     return 0;
 }
 

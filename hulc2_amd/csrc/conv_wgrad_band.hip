@@ -872,6 +872,7 @@ int launch_conv1_wgrad(W1P& p, float* dw, float* db, void* ws, long ws_bytes, in
     const long Rw = 32L * K;
     const int nbw = (int)((Rw + 63) / 64);
     wband_reduce_kernel<<<nbw + (db ? 1 : 0), 1024, 0, s>>>(p.partial_w, dw, grid, Rw, accumulate, 0, 64, nbw, p.partial_b, db, 32);
+    hulc_conv_path_set("conv1_wgrad u8=%d R=%d grid=%d", p.u8 ? 1 : 0, R, grid);
     return 0;
 }
 
@@ -938,6 +939,7 @@ int launch_wband(WBandP& p, float* dw, float* db, void* ws, long ws_bytes, int d
     const int nbw = (int)((Rw + 63) / 64);
     wband_reduce_kernel<<<nbw + (db ? 1 : 0), 1024, 0, s>>>(p.partial_w, dw, grid, Rw, accumulate, (dw_oihw && !NCHW) ? C : 0, TH * TW, nbw, p.partial_b, db,
                                                           COUT);
+    hulc_conv_path_set("wband<%d,%d,%d,%d,%d> pure16=%d R=%d F=%d units=%d grid=%d", C, CT, TH, TW, S, (int)PURE16, R, F, nunits, grid);
     return 0;
 }
 
@@ -956,6 +958,9 @@ int hulc_conv_wgrad_band_dispatch(int nchw, int Cin, int Cout, int KH, int KW, i
     p.dy_sn = (long)p.OH * p.OW * Cout; p.dy_sy = (long)p.OW * Cout; p.dy_sx = Cout;
     int rc = 1;
     const bool pure16 = x_dtype == HULC_BF16 && dy_dtype == HULC_BF16;
+    // (the NHWC instances know neither field: ignoring x2 would read N frames from a tensor that holds n_split of them)
+    if ((x2 || x_slot || x2_slot) && !(nchw && Cin == 3 && Cout == 32 && KH == 8 && KW == 8 && S == 4))
+        return hulc_fail(-6, "conv weight gradient: x2 / frame slots are for conv1 only");
     if (!nchw && Cin == 64 && Cout == 64 && KH == 3 && KW == 3 && S == 1)
         rc = pure16 ? launch_wband<64, 2, 3, 3, 1, false, 5, 4, 1, true>(p, dw, db, ws, ws_bytes, dw_oihw, accumulate, s)
                     : launch_wband<64, 2, 3, 3, 1, false, 5, 4, 1>(p, dw, db, ws, ws_bytes, dw_oihw, accumulate, s);
@@ -984,7 +989,7 @@ int hulc_conv_wgrad_band_dispatch(int nchw, int Cin, int Cout, int KH, int KW, i
             rc = launch_conv1_wgrad(q, dw, db, ws, ws_bytes, accumulate, slots, s);
         }
     }
-    else return (x2 || x_slot) ? hulc_fail(-6, "conv weight gradient: x2 / frame slots are for conv1 only") : 1;
+    else return 1;
     if (rc == -1) return 1;
     if (rc < 0) return hulc_fail(-8, "conv wgrad band: could not raise the dynamic LDS limit");
     return 0;

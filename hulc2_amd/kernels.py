@@ -394,6 +394,23 @@ def _slot_fields(d, x, x2, H, W, Cin, Cout, KH, stride, x_nchw) -> None:
         _frame_slots_used.add(x2.data_ptr())
 
 
+def conv_last_path():
+    """(token, plan) of hulc_conv_last_path(): which kernel served this thread's last conv2d_fwd / conv2d_padded_fwd / conv2d_bwd_data /
+    conv2d_bwd_weight call — e.g. ("band_x<32,2,4,4,2>", {"xf32": 0, "bits": 1, "multi": 1, "R": 9, "F": 3, "units": 2, "grid": 2}); a follow-up
+    pass (`+relu_bits_pass`, `+cast_pass`) is a key with value 1.  ("", {}) after a refused call.  For tests and diagnostics: nothing acts on it."""
+    words = _L.load().hulc_conv_last_path().decode().split()
+    if not words:
+        return "", {}
+    plan = {}
+    for w in words[1:]:
+        if w.startswith("+"):
+            plan[w[1:]] = 1
+        else:
+            k, v = w.split("=")
+            plan[k] = int(v)
+    return words[0], plan
+
+
 def conv2d_fwd(x, w2d, bias, y, N, H, W, Cin, Cout, KH, KW, stride, x_nchw, relu=True, compute=None, aug_shift=None, aug_pad=0,
                frame_index=None, relu_bits=None, w_lo=None, x2=None, y_bf16=None, conv1_slots=None):
     """y (NHWC) = relu(conv(x, w) + b); w2d is [Cout][K] in the layout's k order (see hulc_conv_desc).  x may be uint8 NHWC frames

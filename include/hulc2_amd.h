@@ -31,6 +31,13 @@ extern "C" {
 #define HULC_F16 2
 
 const char* hulc_last_error(void);
+/* (added under ABI 7 — a new symbol only; every earlier prototype and hulc_abi_version() are unchanged.)  Which kernel served this thread's last
+ * hulc_conv2d_fwd / hulc_conv2d_padded_fwd / hulc_conv2d_bwd_data / hulc_conv2d_bwd_weight call and the plan its launcher computed: a kernel token,
+ * then key=value fields and `+pass` suffixes for follow-up launches, e.g. "band_x<32,2,4,4,2> xf32=0 bits=1 multi=1 R=9 F=3 units=2 grid=2",
+ * "band_glds<4,2,2> bits=2 pad=1 units=3 grid=3", "conv1_band u8=0 x3=0 R=10 grid=5", "gather<bf16> +relu_bits_pass", "wgrad_gather f32=0 P=3".
+ * Thread-local like hulc_last_error(); every one of those entry points clears it on entry and a refused call leaves "".  Output only (tests and
+ * diagnostics): nothing in the library reads it back. */
+const char* hulc_conv_last_path(void);
 int hulc_abi_version(void);
 /* (ABI 6) Cooperative launches — the ones whose workgroups wait for each other inside the kernel and therefore must all be resident at once:
  * hulc_mlp_chain / hulc_mlp_chain2, hulc_txl_block_fwd / _bwd with shared sequences, the recurrent sweeps — take one workgroup per CU.  Two of

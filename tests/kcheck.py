@@ -1,5 +1,5 @@
 """Shared pieces of the kernel-level tests (tests/test_reductions_gpu.py, tests/test_losses_gpu.py, tests/test_ffn_kernel_gpu.py,
-tests/test_rnn_kernel_gpu.py).
+tests/test_rnn_kernel_gpu.py, tests/test_conv_paths_gpu.py).
 
 Every case of those files follows one pattern:
   1. inputs are drawn on the CPU in float64 from a seeded generator and rounded to the kernel's storage type; the float64 reference is given
@@ -23,6 +23,7 @@ _SENTINEL = {torch.float32: (torch.int32, 0x7FC5A5A5),      # quiet NaNs with a 
              torch.bfloat16: (torch.int16, 0x7FC5),
              torch.float16: (torch.int16, 0x7E5A),
              torch.int64: (torch.int64, 0x5A5A5A5A5A5A5A5A),
+             torch.int32: (torch.int32, 0x5A5A5A5A),
              torch.uint8: (torch.uint8, 0xA5)}
 
 RATIOS = {}                      # kernel name -> largest (GPU error / max(e_ref, 2^-23)) seen, printed once per module

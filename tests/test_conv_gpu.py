@@ -1,5 +1,10 @@
-"""GPU parity of the conv kernels (forward / data gradient / weight gradient) against torch's
-conv2d autograd in float64 on the same (bf16-rounded, for bf16 compute) operands."""
+"""GPU parity of the conv entry points (forward / data gradient / weight gradient) against torch's conv2d autograd in float64 on the same
+(bf16-rounded, for bf16 compute) operands, at the six layers of the two camera encoders.
+
+Which kernel a test measures (asserted through kernels.conv_last_path()): test_conv_forward and test_conv_bwd_data pass fp32 weights (and an fp32
+mask), which every LDS-band kernel hands over, so BOTH of their `compute` parametrisations are tests of the gather kernels
+(conv_gather_bf16_kernel / conv_gather_kernel).  The band kernels are reached by test_conv_bwd_weight, the sign-plane tests, the y_bf16 tests and
+the many-units test below; each of their instances is compared with float64, bit for bit on a lattice, in tests/test_conv_paths_gpu.py."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -42,6 +47,7 @@ def test_conv_forward(dev, compute, name, N, H, W, Cin, Cout, K, stride, nchw):
     w2d = w.reshape(Cout, -1).contiguous() if nchw else w.permute(0, 2, 3, 1).reshape(Cout, -1).contiguous()
     y = torch.full((N, OH, OW, Cout), float("nan"), device=dev)
     kn.conv2d_fwd(xin, w2d, b, y, N, H, W, Cin, Cout, K, K, stride, nchw, relu=True, compute=kn._COMPUTE[compute])
+    assert kn.conv_last_path()[0] == ("gather<bf16>" if compute == "bf16" else "gather<f32>")        # (fp32 weights: no band kernel takes them)
     torch.cuda.synchronize()
     ref = torch.relu(F.conv2d(_round(x, compute), _round(w, compute), b.double(), stride=stride)).permute(0, 2, 3, 1)
     err = (y.double() - ref).abs().max().item()
@@ -62,6 +68,7 @@ def test_conv_bwd_data(dev, compute, name, N, H, W, Cin, Cout, K, stride, nchw):
     dx = torch.full((N, H, W, Cin), float("nan"), device=dev)
     kn.conv2d_bwd_data(dy.permute(0, 2, 3, 1).contiguous(), wt, dx, relu_src, N, H, W, Cin, Cout, K, K, stride,
                        compute=kn._COMPUTE[compute])
+    assert kn.conv_last_path() == ("gather<bf16>" if compute == "bf16" else "gather<f32>", {"launches": stride * stride})
     torch.cuda.synchronize()
     ref = torch.nn.grad.conv2d_input((N, Cin, H, W), _round(w, compute), _round(dy, compute), stride=stride)
     ref = ref.permute(0, 2, 3, 1) * (relu_src > 0)
@@ -127,6 +134,11 @@ def test_relu_sign_planes_written_by_the_forward(dev, name, N, H, W, Cin, Cout, 
     bits = torch.full((N * OH * OW * (Cout // 32),), 0x5A5A5A5A, dtype=torch.int32, device=dev)
     kn.conv2d_fwd(xin, w2d, b, y0, N, H, W, Cin, Cout, K, K, stride, nchw, relu=True, compute=kn.BF16)
     kn.conv2d_fwd(xin, w2d, b, y1, N, H, W, Cin, Cout, K, K, stride, nchw, relu=True, compute=kn.BF16, relu_bits=bits)
+    token, plan = kn.conv_last_path()
+    if name.startswith("odd"):
+        assert (token, plan) == ("gather<bf16>", {"relu_bits_pass": 1})
+    else:
+        assert token == ("conv1_band" if nchw else "band_x<32,2,4,4,2>") and "relu_bits_pass" not in plan and (nchw or plan["bits"] == 1)
     torch.cuda.synchronize()
     assert torch.equal(y0, y1)
     assert torch.equal(bits, _pack_bits(y1)), f"{name}: {(bits != _pack_bits(y1)).sum().item()} of {bits.numel()} words differ"
@@ -135,6 +147,9 @@ def test_relu_sign_planes_written_by_the_forward(dev, name, N, H, W, Cin, Cout, 
 
 @pytest.mark.parametrize("name,N,H,W,Cin,Cout,K,stride,nchw", [l for l in LAYERS if not l[-1]] + [("odd2", 2, 17, 21, 32, 64, 4, 2, False)])
 def test_data_gradient_masked_by_sign_planes_equals_masked_by_the_activation(dev, name, N, H, W, Cin, Cout, K, stride, nchw):
+    """two launches of our own against each other (each instance against float64: tests/test_conv_paths_gpu.py): masked by the activation tensor the
+    register-staged band kernel serves every layer; with the planes the static camera's maps go to the direct-to-LDS instances, the small maps
+    (grip2, grip3, odd2) stay in the same kernel family"""
     from hulc2_amd import kernels as kn
 
     x, w, b, g = _setup(dev, N, H, W, Cin, Cout, K, 22)
@@ -144,8 +159,12 @@ def test_data_gradient_masked_by_sign_planes_equals_masked_by_the_activation(dev
     wt = w.permute(1, 2, 3, 0).contiguous().to(torch.bfloat16)
     a = torch.full((N, H, W, Cin), float("nan"), device=dev, dtype=torch.bfloat16)
     b2 = torch.full_like(a, float("nan"))
+    band_x = "band_x<64,4,2,2,1>" if K == 4 else "band_x<64,2,3,3,1>"
     kn.conv2d_bwd_data(dy, wt, a, act, N, H, W, Cin, Cout, K, K, stride, compute=kn.BF16)
+    assert kn.conv_last_path()[0] == band_x
     kn.conv2d_bwd_data(dy, wt, b2, act, N, H, W, Cin, Cout, K, K, stride, compute=kn.BF16, relu_bits=_pack_bits(act))
+    token, plan = kn.conv_last_path()
+    assert token == {"static2": "band_glds<4,2,2>", "static3": "band_planes<21,21>"}.get(name, band_x) and plan["bits"] == 2
     torch.cuda.synchronize()
     assert torch.isfinite(a.float()).all() and torch.equal(a, b2), f"{name}: {(a != b2).sum().item()} elements differ"
     assert (a.float().abs() > 0).float().mean().item() > 0.2
@@ -200,6 +219,7 @@ def test_conv1_two_frame_tensors_in_one_launch(dev, name, Na, Nb, H, W):
     if Nb:
         kn.conv2d_fwd(xb, w2d, b, y1[Na:], Nb, H, W, 3, 32, 8, 8, 4, True, compute=kn.BF16, relu_bits=b1[Na * OH * OW:])
     kn.conv2d_fwd(xa, w2d, b, y2, N, H, W, 3, 32, 8, 8, 4, True, compute=kn.BF16, relu_bits=b2, x2=xb)
+    assert kn.conv_last_path()[0] == "conv1_band" and kn.conv_last_path()[1]["u8"] == 0
     torch.cuda.synchronize()
     assert torch.equal(y1.view(torch.int16), y2.view(torch.int16)) and torch.equal(b1, b2)
     dy = torch.randn(N, OH, OW, 32, generator=g).to(dev).to(torch.bfloat16)
@@ -209,6 +229,7 @@ def test_conv1_two_frame_tensors_in_one_launch(dev, name, Na, Nb, H, W):
     if Nb:
         kn.conv2d_bwd_weight(xb, dy[Na:].contiguous(), dw1, db1, Nb, H, W, 3, 32, 8, 8, 4, True, compute=kn.BF16, accumulate=True)
     kn.conv2d_bwd_weight(xa, dy, dw2, db2, N, H, W, 3, 32, 8, 8, 4, True, compute=kn.BF16, x2=xb)
+    assert kn.conv_last_path()[0] == "conv1_wgrad" and kn.conv_last_path()[1]["u8"] == 0
     torch.cuda.synchronize()
     assert float((dw1 - dw2).abs().max()) <= 1e-5 * float(dw1.abs().max()) and float((db1 - db2).abs().max()) <= 1e-5 * float(db1.abs().max())
     xall = torch.cat([xa, xb]).to(torch.bfloat16).double().requires_grad_(False)
@@ -241,6 +262,7 @@ def test_conv1_two_uint8_frame_tensors_in_one_launch(dev, name, Na, Nb, H, W, sh
     kn.conv2d_fwd(xa, w2d, b, y1[:Na], Na, H, W, 3, 32, 8, 8, 4, True, compute=kn.BF16, relu_bits=b1[:Na * OH * OW], aug_shift=sa, aug_pad=pad)
     kn.conv2d_fwd(xb, w2d, b, y1[Na:], Nb, H, W, 3, 32, 8, 8, 4, True, compute=kn.BF16, relu_bits=b1[Na * OH * OW:], aug_shift=sb, aug_pad=pad)
     kn.conv2d_fwd(xa, w2d, b, y2, N, H, W, 3, 32, 8, 8, 4, True, compute=kn.BF16, relu_bits=b2, x2=xb, aug_shift=sab, aug_pad=pad)
+    assert kn.conv_last_path()[0] == "conv1_band" and kn.conv_last_path()[1]["u8"] == 1
     torch.cuda.synchronize()
     assert torch.equal(y1.view(torch.int16), y2.view(torch.int16)) and torch.equal(b1, b2)
     dy = torch.randn(N, OH, OW, 32, generator=g).to(dev).to(torch.bfloat16)
@@ -249,6 +271,7 @@ def test_conv1_two_uint8_frame_tensors_in_one_launch(dev, name, Na, Nb, H, W, sh
     kn.conv2d_bwd_weight(xa, dy[:Na].contiguous(), dw1, db1, Na, H, W, 3, 32, 8, 8, 4, True, compute=kn.BF16, aug_shift=sa, aug_pad=pad)
     kn.conv2d_bwd_weight(xb, dy[Na:].contiguous(), dw1, db1, Nb, H, W, 3, 32, 8, 8, 4, True, compute=kn.BF16, accumulate=True, aug_shift=sb, aug_pad=pad)
     kn.conv2d_bwd_weight(xa, dy, dw2, db2, N, H, W, 3, 32, 8, 8, 4, True, compute=kn.BF16, x2=xb, aug_shift=sab, aug_pad=pad)
+    assert kn.conv_last_path()[0] == "conv1_wgrad" and kn.conv_last_path()[1]["u8"] == 1
     torch.cuda.synchronize()
     assert float((dw1 - dw2).abs().max()) <= 1e-5 * float(dw1.abs().max()) and float((db1 - db2).abs().max()) <= 1e-5 * float(db1.abs().max())
 
