@@ -27,14 +27,27 @@ template <bool NT> HULC_DEVICE void st4(float* a, float x, float y, float z, flo
     else *(float4*)a = make_float4(x, y, z, w);
 }
 
-template <int NT>
+// ---- gradient clipping (hulc_*_step_clip): the effective gradient of one element -----------------------------------------------------------
+// CLIP_NORM: (g * gscale) * coef, two ROUNDED products in torch's order (unscale_, then clip_grad_norm_'s multiply by the coefficient
+// hulc_grad_norm_clip left in device memory); CLIP_VALUE: g * gscale clamped to [-c, c] by comparisons, so a NaN stays a NaN
+// (clip_grad_value_).  pinned(): the product leaves as an opaque value — the header's __fmul_rn is a plain `*`, which -ffp-contract=fast
+// would contract into the `+ wd * p` that follows.  CLIP_OFF is never routed through here: those kernels keep the expressions they had.
+enum { CLIP_OFF = 0, CLIP_NORM = 1, CLIP_VALUE = 2 };
+HULC_DEVICE float pinned(float x) { asm("" : "+v"(x)); return x; }
+template <int CLIP> HULC_DEVICE float clipped(float g, float gscale, float coef, float c) {
+    float x = pinned(__fmul_rn(g, gscale));
+    if (CLIP == CLIP_NORM) return pinned(__fmul_rn(x, coef));
+    return pinned(x < -c ? -c : (x > c ? c : x));
+}
+
+template <int NT, int CLIP>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, uint16_t* __restrict__ shadow, long n, float lr, float b1,
                                                    float b2, float eps, float wd, float bc1, float bc2_sqrt, float gscale,
                                                    const unsigned long long* __restrict__ step_state, const int* __restrict__ skip_flag,
                                                    uint16_t* __restrict__ lo, LoRanges lr_, float omb1, float omb2, double b1d, double b2d,
                                                    const float* __restrict__ loss_scale, const float* __restrict__ found_inf,
-                                                   const float* __restrict__ lr_dev) {
+                                                   const float* __restrict__ lr_dev, const float* __restrict__ clip_coef, float clip_value) {
     // omb1 / omb2 = 1 - beta as torch forms them: in DOUBLE from the decimal the caller meant (0.999), then rounded to fp32 — 1.f - 0.999f is
     // 4.7e-5 (relative) away from that, and exp_avg_sq with it; the bias corrections likewise come from double powers (torch: Python floats)
     if (skip_flag && *skip_flag) return;    // an upstream kernel reported a fault (barrier timeout): keep the weights, the host raises
@@ -45,6 +58,8 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     // the learning rate as a device scalar (hulc_adam_step_sched): a captured launch follows a schedule the host writes between replays.  One
     // uniform 4-byte read per thread; the arithmetic below is the scalar argument's, so lr_dev == (float)lr gives the same bits
     if (lr_dev) lr = *lr_dev;
+    float coef = 1.f;
+    if (CLIP == CLIP_NORM) coef = *clip_coef;   // what hulc_grad_norm_clip wrote in front of this launch (one uniform 4-byte read per thread)
     if (step_state) {                       // bias corrections from the device-resident step count (graph replay)
         const double t = (double)step_state[1];
         bc1 = (float)(1.0 - pow(b1d, t));
@@ -58,7 +73,9 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
             float ma[4] = {mv.x, mv.y, mv.z, mv.w}, va[4] = {vv.x, vv.y, vv.z, vv.w};
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                float gg = ga[k] * gscale + wd * pa[k];
+                float gg;
+                if (CLIP == CLIP_OFF) gg = ga[k] * gscale + wd * pa[k];
+                else gg = clipped<CLIP>(ga[k], gscale, coef, clip_value) + wd * pa[k];
                 ma[k] = b1 * ma[k] + omb1 * gg;
                 va[k] = b2 * va[k] + omb2 * gg * gg;
                 const float denom = sqrtf(va[k]) / bc2_sqrt + eps;
@@ -85,7 +102,9 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
             }
         } else {
             for (long k = i; k < n; ++k) {
-                float gg = g[k] * gscale + wd * p[k];
+                float gg;
+                if (CLIP == CLIP_OFF) gg = g[k] * gscale + wd * p[k];
+                else gg = clipped<CLIP>(g[k], gscale, coef, clip_value) + wd * p[k];
                 float mm = b1 * m[k] + omb1 * gg, vv = b2 * v[k] + omb2 * gg * gg;
                 m[k] = mm; v[k] = vv;
                 float pn = p[k] - (lr / bc1) * (mm / (sqrtf(vv) / bc2_sqrt + eps));
@@ -116,6 +135,7 @@ struct RuleArgs {
     double b1d, b2d;
     float momentum, omd;                               // SGD: omd = 1 - dampening, formed in double from the decimal the caller meant
     int nesterov, first;                               // first: step == 1 (torch clones the gradient into the buffer, no dampening)
+    float coef, cval;                                  // gradient clipping (CLIP_NORM: *clip_coef, read at kernel start; CLIP_VALUE: the bound)
 };
 
 HULC_DEVICE bool in_ranges(const LoRanges& r, long k) {
@@ -126,17 +146,21 @@ HULC_DEVICE bool in_ranges(const LoRanges& r, long k) {
 }
 
 // one element: p, m (exp_avg / momentum buffer), v (exp_avg_sq) in registers; keep = 1 - lr * wd (AdamW), lrb = lr / bc1 (AdamW) or lr (SGD)
-template <int RULE, bool BUF>
+template <int RULE, bool BUF, int CLIP>
 HULC_DEVICE void rule_update(float& p, float g, float& m, float& v, const RuleArgs& a, float keep, float lrb) {
     if (RULE == RULE_ADAMW) {
         p *= keep;                                     // torch's single-tensor AdamW: param.mul_(1 - lr * weight_decay) FIRST
-        const float gg = g * a.gscale;                 // (the moments see the undecayed gradient)
+        float gg;                                      // (the moments see the undecayed gradient)
+        if (CLIP == CLIP_OFF) gg = g * a.gscale;
+        else gg = clipped<CLIP>(g, a.gscale, a.coef, a.cval);
         m = a.b1 * m + a.omb1 * gg;
         v = a.b2 * v + a.omb2 * gg * gg;
         const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
         p -= lrb * (m / denom);
     } else {
-        const float gg = g * a.gscale + a.wd * p;
+        float gg;
+        if (CLIP == CLIP_OFF) gg = g * a.gscale + a.wd * p;
+        else gg = clipped<CLIP>(g, a.gscale, a.coef, a.cval) + a.wd * p;
         float d = gg;
         if (BUF) {
             m = a.first ? gg : a.momentum * m + a.omd * gg;
@@ -146,7 +170,7 @@ HULC_DEVICE void rule_update(float& p, float g, float& m, float& v, const RuleAr
     }
 }
 
-template <int RULE, bool BUF>
+template <int RULE, bool BUF, int CLIP>
 HULC_DEVICE void rule_scalar(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                              uint16_t* __restrict__ shadow, uint16_t* __restrict__ lo, const LoRanges& lr_, const LoRanges& sk, long k0, long k1,
                              const RuleArgs& a, float keep, float lrb) {
@@ -155,7 +179,7 @@ HULC_DEVICE void rule_scalar(float* __restrict__ p, const float* __restrict__ g,
         float pn = p[k], mm = 0.f, vv = 0.f;
         if (BUF) mm = m[k];
         if (RULE == RULE_ADAMW) vv = v[k];
-        rule_update<RULE, BUF>(pn, g[k], mm, vv, a, keep, lrb);
+        rule_update<RULE, BUF, CLIP>(pn, g[k], mm, vv, a, keep, lrb);
         p[k] = pn;
         if (BUF) m[k] = mm;
         if (RULE == RULE_ADAMW) v[k] = vv;
@@ -168,16 +192,18 @@ HULC_DEVICE void rule_scalar(float* __restrict__ p, const float* __restrict__ g,
 }
 
 // BUF: the rule keeps a first state arena (AdamW: always; SGD: momentum != 0)
-template <int RULE, bool BUF>
+template <int RULE, bool BUF, int CLIP>
 __global__ __launch_bounds__(256) void rule_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                    uint16_t* __restrict__ shadow, long n, RuleArgs a,
                                                    const unsigned long long* __restrict__ step_state, const int* __restrict__ skip_flag,
                                                    uint16_t* __restrict__ lo, LoRanges lr_, LoRanges sk, const float* __restrict__ loss_scale,
-                                                   const float* __restrict__ found_inf, const float* __restrict__ lr_dev) {
+                                                   const float* __restrict__ found_inf, const float* __restrict__ lr_dev,
+                                                   const float* __restrict__ clip_coef) {
     if (skip_flag && *skip_flag) return;               // as adam_kernel: fault upstream / GradScaler found an inf: nothing is touched
     if (found_inf && *found_inf != 0.f) return;
     if (loss_scale) a.gscale *= (float)(1.0 / (double)*loss_scale);
     if (lr_dev) a.lr = *lr_dev;
+    if (CLIP == CLIP_NORM) a.coef = *clip_coef;
     if (step_state) {                                  // the device-resident step count decides the bias corrections / what "first" is
         if (RULE == RULE_ADAMW) {
             const double t = (double)step_state[1];
@@ -188,18 +214,18 @@ __global__ __launch_bounds__(256) void rule_kernel(float* __restrict__ p, const 
     const float keep = 1.f - a.lr * a.wd, lrb = RULE == RULE_ADAMW ? a.lr / a.bc1 : a.lr;
     const long stride = (long)gridDim.x * blockDim.x * 4;
     for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {
-        if (i + 3 >= n) { rule_scalar<RULE, BUF>(p, g, m, v, shadow, lo, lr_, sk, i, n, a, keep, lrb); continue; }
+        if (i + 3 >= n) { rule_scalar<RULE, BUF, CLIP>(p, g, m, v, shadow, lo, lr_, sk, i, n, a, keep, lrb); continue; }
         if (sk.n) {                                    // ranges start at multiples of 4: a chunk is inside one, outside all, or holds an END
             const bool head = in_ranges(sk, i), last = in_ranges(sk, i + 3);
             if (head && last) continue;
-            if (head) { rule_scalar<RULE, BUF>(p, g, m, v, shadow, lo, lr_, sk, i, i + 4, a, keep, lrb); continue; }
+            if (head) { rule_scalar<RULE, BUF, CLIP>(p, g, m, v, shadow, lo, lr_, sk, i, i + 4, a, keep, lrb); continue; }
         }
         const float4 pv = ld4<true>(p + i), gv = ld4<true>(g + i);
         float pa[4] = {pv.x, pv.y, pv.z, pv.w}, ga[4] = {gv.x, gv.y, gv.z, gv.w}, ma[4] = {0.f, 0.f, 0.f, 0.f}, va[4] = {0.f, 0.f, 0.f, 0.f};
         if (BUF) { const float4 t = ld4<true>(m + i); ma[0] = t.x; ma[1] = t.y; ma[2] = t.z; ma[3] = t.w; }
         if (RULE == RULE_ADAMW) { const float4 t = ld4<true>(v + i); va[0] = t.x; va[1] = t.y; va[2] = t.z; va[3] = t.w; }
 #pragma unroll
-        for (int k = 0; k < 4; ++k) rule_update<RULE, BUF>(pa[k], ga[k], ma[k], va[k], a, keep, lrb);
+        for (int k = 0; k < 4; ++k) rule_update<RULE, BUF, CLIP>(pa[k], ga[k], ma[k], va[k], a, keep, lrb);
         st4<true>(p + i, pa[0], pa[1], pa[2], pa[3]);
         if (BUF) st4<true>(m + i, ma[0], ma[1], ma[2], ma[3]);
         if (RULE == RULE_ADAMW) st4<true>(v + i, va[0], va[1], va[2], va[3]);
@@ -214,6 +240,68 @@ __global__ __launch_bounds__(256) void rule_kernel(float* __restrict__ p, const 
             }
         }
     }
+}
+
+// ---- global gradient norm + clip coefficient (hulc_grad_norm_clip) -------------------------------------------------------------------------
+// Two launches, no atomics, no tickets: the result depends on n alone, never on which workgroup finishes first.  Stage 1: a grid fixed by n
+// streams the arena in 16-byte loads, four per lane and trip (2048 workgroups x 256 lanes x 64 B = 128 KiB in flight per CU at most, several
+// times what keeps the HBM streaming), squares in DOUBLE (the square of an fp32 value is exact there), four accumulators per lane, lanes of a
+// wave by shuffles, the four waves through LDS, one double per workgroup into ws.  Stage 2: one workgroup adds the partials — lane t takes
+// t, t + 256, ... in index order, then the same tree — and lane 0 writes the norm and the coefficient.  Every element of ws that stage 2
+// reads was written by stage 1 of the same call: nothing to clear.
+#ifndef HULC_GRAD_NORM_NT
+#define HULC_GRAD_NORM_NT 0        // stage-1 load policy: 0 default, 1 non-temporal (NOTES.md "Gradient clipping": the A/B)
+#endif
+constexpr long GRAD_NORM_MAX_BLOCKS = 2048;
+inline long grad_norm_blocks(long n) {
+    long b = (n / 4 + 1023) / 1024;                    // a workgroup's trip: 256 lanes x 4 loads of 4 elements
+    return b < 1 ? 1 : (b > GRAD_NORM_MAX_BLOCKS ? GRAD_NORM_MAX_BLOCKS : b);
+}
+
+// sum over the 256 lanes of a workgroup, the same tree every time; valid in lane 0
+HULC_DEVICE double block_sum_256(double x) {
+    __shared__ double part[4];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = x;
+    __syncthreads();
+    return (part[0] + part[1]) + (part[2] + part[3]);
+}
+
+HULC_DEVICE void sq_acc(double (&acc)[4], const float4 v) {
+    acc[0] += (double)v.x * (double)v.x; acc[1] += (double)v.y * (double)v.y;
+    acc[2] += (double)v.z * (double)v.z; acc[3] += (double)v.w * (double)v.w;
+}
+
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, long n, double* __restrict__ partial) {
+    constexpr bool NT = HULC_GRAD_NORM_NT != 0;
+    const long nv = n >> 2, T = (long)gridDim.x * blockDim.x;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    for (; i + 3 * T < nv; i += 4 * T) {               // four independent 16-byte loads in flight per lane
+        const float4 a = ld4<NT>(g + 4 * i), b = ld4<NT>(g + 4 * (i + T)), c = ld4<NT>(g + 4 * (i + 2 * T)), d = ld4<NT>(g + 4 * (i + 3 * T));
+        sq_acc(acc, a); sq_acc(acc, b); sq_acc(acc, c); sq_acc(acc, d);
+    }
+    for (; i < nv; i += T) sq_acc(acc, ld4<NT>(g + 4 * i));
+    if (blockIdx.x == 0 && threadIdx.x == 0)           // the last n % 4 elements
+        for (long k = nv << 2; k < n; ++k) acc[0] += (double)g[k] * (double)g[k];
+    const double s = block_sum_256((acc[0] + acc[1]) + (acc[2] + acc[3]));
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __restrict__ partial, int count, float gscale,
+                                                               const float* __restrict__ loss_scale, float max_norm, float* __restrict__ out) {
+    double x = 0.0;
+    for (int k = threadIdx.x; k < count; k += 256) x += partial[k];
+    const double S = block_sum_256(x);
+    if (threadIdx.x != 0) return;
+    if (loss_scale) gscale *= (float)(1.0 / (double)*loss_scale);          // as adam_kernel / rule_kernel form the scale
+    const float norm = (float)(sqrt(S) * (double)gscale);
+    // torch.nn.utils.clip_grad_norm_: clamp(max_norm / (total_norm + 1e-6), max = 1.0), `float / Tensor` being reciprocal() * float: three
+    // fp32 roundings.  The comparison (not fminf) lets a NaN norm give a NaN coefficient, as torch.clamp does.
+    const float c = __fmul_rn(pinned(__frcp_rn(pinned(__fadd_rn(norm, 1e-6f)))), max_norm);
+    out[0] = norm;
+    out[1] = c > 1.f ? 1.f : c;
 }
 
 __global__ void step_count_advance_if_kernel(unsigned long long* state, const float* found_inf) {
@@ -439,12 +527,21 @@ static double meant_decimal(float b) {
     return std::fabs(r - d) <= 6e-8 * std::fabs(d) ? r : d;
 }
 
+// the clipping arguments of the hulc_*_step_clip entry points: a coefficient (norm clipping) or a bound (value clipping), never both
+static int check_clip(const float* clip_coef, float clip_value) {
+    if (!(clip_value >= 0.f) || std::isinf(clip_value)) return hulc_fail(-2, "optimizer step: clip_value must be finite and >= 0 (0 = off)");
+    if (clip_coef && clip_value != 0.f) return hulc_fail(-2, "optimizer step: clip_coef (norm clipping) and clip_value (value clipping) exclude each other");
+    if ((uintptr_t)clip_coef % 4) return hulc_fail(-4, "optimizer step: clip_coef must be 4-byte aligned");
+    return 0;
+}
+
 // every hulc_adam_step* entry point ends here; lr_dev == nullptr is the scalar-lr path
 static int adam_launch(float* p, const float* g, float* m, float* v, void* bf16_shadow, long n, float lr, float beta1, float beta2,
                        float eps, float weight_decay, int step, const unsigned long long* step_state, float grad_scale, const int* skip_flag,
                        void* lo_shadow, const long* lo_ranges, int n_ranges, const float* loss_scale, const float* found_inf, const float* lr_dev,
-                       void* stream) {
+                       void* stream, const float* clip_coef = nullptr, float clip_value = 0.f) {
     if (!p || !g || !m || !v) return hulc_fail(-1, "hulc_adam_step: null pointer");
+    if (int rc = check_clip(clip_coef, clip_value)) return rc;
     LoRanges lr_;
     lr_.n = 0;
     for (int q = 0; q < 8; ++q) lr_.b[q] = lr_.e[q] = 0;
@@ -469,9 +566,16 @@ static int adam_launch(float* p, const float* g, float* m, float* v, void* bf16_
     // adam_kernel<NT>, NT bits: 0 g loads, 1 p / m / v loads, 2 p / m / v stores, 3 shadow stores (non-temporal)
     constexpr long cap = 8192;
     long blocks = (n / 4 + 255) / 256; if (blocks > cap) blocks = cap; if (blocks < 1) blocks = 1;
-    adam_kernel<7><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(p, g, m, v, (uint16_t*)bf16_shadow, n, lr, beta1, beta2, eps, weight_decay,
-                                                                    bc1, bc2s, grad_scale, step_state, skip_flag, (uint16_t*)lo_shadow, lr_,
-                                                                    (float)(1.0 - b1d), (float)(1.0 - b2d), b1d, b2d, loss_scale, found_inf, lr_dev);
+    // one launch site for the three instantiations: without clipping the kernel is the one every hulc_adam_step* entry point has always run
+#define HULC_ADAM_LAUNCH(CLIP)                                                                                                                  \
+    adam_kernel<7, CLIP><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(p, g, m, v, (uint16_t*)bf16_shadow, n, lr, beta1, beta2, eps,       \
+                                                                          weight_decay, bc1, bc2s, grad_scale, step_state, skip_flag,          \
+                                                                          (uint16_t*)lo_shadow, lr_, (float)(1.0 - b1d), (float)(1.0 - b2d),  \
+                                                                          b1d, b2d, loss_scale, found_inf, lr_dev, clip_coef, clip_value)
+    if (clip_coef) HULC_ADAM_LAUNCH(CLIP_NORM);
+    else if (clip_value != 0.f) HULC_ADAM_LAUNCH(CLIP_VALUE);
+    else HULC_ADAM_LAUNCH(CLIP_OFF);
+#undef HULC_ADAM_LAUNCH
     return hulc_check_launch("hulc_adam_step");
 }
 
@@ -494,6 +598,32 @@ extern "C" int hulc_adam_step_sched(float* p, const float* g, float* m, float* v
                        n_ranges, loss_scale, found_inf, lr_dev, stream);
 }
 
+// see include/hulc2_amd.h
+extern "C" int hulc_adam_step_clip(float* p, const float* g, float* m, float* v, void* bf16_shadow, long n, float lr, float beta1, float beta2,
+                                   float eps, float weight_decay, int step, const unsigned long long* step_state, float grad_scale,
+                                   const int* skip_flag, void* lo_shadow, const long* lo_ranges, int n_ranges, const float* loss_scale,
+                                   const float* found_inf, const float* lr_dev, const float* clip_coef, float clip_value, void* stream) {
+    if ((uintptr_t)lr_dev % 4) return hulc_fail(-4, "hulc_adam_step_clip: lr_dev must be 4-byte aligned");
+    return adam_launch(p, g, m, v, bf16_shadow, n, lr, beta1, beta2, eps, weight_decay, step, step_state, grad_scale, skip_flag, lo_shadow, lo_ranges,
+                       n_ranges, loss_scale, found_inf, lr_dev, stream, clip_coef, clip_value);
+}
+
+// see include/hulc2_amd.h
+extern "C" long hulc_grad_norm_ws_bytes(long n) { return n < 0 ? 0 : grad_norm_blocks(n) * (long)sizeof(double); }
+
+extern "C" int hulc_grad_norm_clip(const float* g, long n, float grad_scale, const float* loss_scale, float max_norm, float* out, void* ws,
+                                   void* stream) {
+    if (!out || !ws || (n > 0 && !g)) return hulc_fail(-1, "hulc_grad_norm_clip: null pointer");
+    if (n < 0 || !(max_norm >= 0.f)) return hulc_fail(-2, "hulc_grad_norm_clip: n >= 0, max_norm >= 0");
+    if ((uintptr_t)g % 16) return hulc_fail(-4, "hulc_grad_norm_clip: the gradient arena must be 16-byte aligned");
+    if (((uintptr_t)ws % 8) || (((uintptr_t)out | (uintptr_t)loss_scale) % 4)) return hulc_fail(-4, "hulc_grad_norm_clip: ws 8-byte, out / loss_scale 4-byte aligned");
+    const long blocks = grad_norm_blocks(n);
+    grad_sumsq_kernel<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(g, n, (double*)ws);
+    if (int rc = hulc_check_launch("hulc_grad_norm_clip")) return rc;
+    grad_norm_finish_kernel<<<1, 256, 0, (hipStream_t)stream>>>((const double*)ws, (int)blocks, grad_scale, loss_scale, max_norm, out);
+    return hulc_check_launch("hulc_grad_norm_clip");
+}
+
 // ---- hulc_adamw_step / hulc_sgd_step: see include/hulc2_amd.h -----------------------------------------------------------------------------
 // up to 8 (begin, end) element ranges of a host array into a kernel argument; starts multiples of 4, inside [0, n]
 static int take_ranges(LoRanges& r, const long* ranges, int count, long n, const char* what) {
@@ -512,7 +642,10 @@ static int take_ranges(LoRanges& r, const long* ranges, int count, long n, const
 template <int RULE>
 static int rule_launch(const char* name, float* p, const float* g, float* m, float* v, void* bf16_shadow, long n, RuleArgs a, int step,
                        const unsigned long long* step_state, const int* skip_flag, void* lo_shadow, const long* lo_ranges, int n_ranges,
-                       const float* loss_scale, const float* found_inf, const float* lr_dev, const long* skip_ranges, int n_skip, void* stream) {
+                       const float* loss_scale, const float* found_inf, const float* lr_dev, const long* skip_ranges, int n_skip, void* stream,
+                       const float* clip_coef = nullptr, float clip_value = 0.f) {
+    if (int rc = check_clip(clip_coef, clip_value)) return rc;
+    a.coef = 1.f; a.cval = clip_value;
     if (!p || !g || (RULE == RULE_ADAMW && (!m || !v))) return hulc_fail(-1, RULE == RULE_ADAMW ? "hulc_adamw_step: null pointer" : "hulc_sgd_step: null pointer");
     if (n < 0) return hulc_fail(-2, "optimizer step: negative element count");
     LoRanges lr_, sk;
@@ -534,29 +667,44 @@ static int rule_launch(const char* name, float* p, const float* g, float* m, flo
     constexpr long cap = 8192;
     long blocks = (n / 4 + 255) / 256; if (blocks > cap) blocks = cap; if (blocks < 1) blocks = 1;
     uint16_t *sh = (uint16_t*)bf16_shadow, *lo = (uint16_t*)lo_shadow;
-    if (RULE == RULE_ADAMW || m)
-        rule_kernel<RULE, true><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(p, g, m, v, sh, n, a, step_state, skip_flag, lo, lr_, sk, loss_scale, found_inf, lr_dev);
-    else
-        rule_kernel<RULE, false><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(p, g, m, v, sh, n, a, step_state, skip_flag, lo, lr_, sk, loss_scale, found_inf, lr_dev);
+#define HULC_RULE_LAUNCH(BUF, CLIP)                                                                                                  \
+    rule_kernel<RULE, BUF, CLIP><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(p, g, m, v, sh, n, a, step_state, skip_flag, lo, lr_, sk, \
+                                                                                  loss_scale, found_inf, lr_dev, clip_coef)
+    const bool buf = RULE == RULE_ADAMW || m;
+    if (clip_coef) { if (buf) HULC_RULE_LAUNCH(true, CLIP_NORM); else HULC_RULE_LAUNCH(false, CLIP_NORM); }
+    else if (clip_value != 0.f) { if (buf) HULC_RULE_LAUNCH(true, CLIP_VALUE); else HULC_RULE_LAUNCH(false, CLIP_VALUE); }
+    else { if (buf) HULC_RULE_LAUNCH(true, CLIP_OFF); else HULC_RULE_LAUNCH(false, CLIP_OFF); }
+#undef HULC_RULE_LAUNCH
     return hulc_check_launch(name);
+}
+
+// see include/hulc2_amd.h; hulc_adamw_step is this with clipping off
+extern "C" int hulc_adamw_step_clip(float* p, const float* g, float* m, float* v, void* bf16_shadow, long n, float lr, float beta1, float beta2,
+                                    float eps, float weight_decay, int step, const unsigned long long* step_state, float grad_scale,
+                                    const int* skip_flag, void* lo_shadow, const long* lo_ranges, int n_ranges, const float* loss_scale,
+                                    const float* found_inf, const float* lr_dev, const long* skip_ranges, int n_skip, const float* clip_coef,
+                                    float clip_value, void* stream) {
+    RuleArgs a = {};
+    a.lr = lr; a.wd = weight_decay; a.gscale = grad_scale; a.b1 = beta1; a.b2 = beta2; a.eps = eps;
+    a.b1d = meant_decimal(beta1); a.b2d = meant_decimal(beta2);
+    a.omb1 = (float)(1.0 - a.b1d); a.omb2 = (float)(1.0 - a.b2d);
+    return rule_launch<RULE_ADAMW>("hulc_adamw_step", p, g, m, v, bf16_shadow, n, a, step, step_state, skip_flag, lo_shadow, lo_ranges, n_ranges,
+                                   loss_scale, found_inf, lr_dev, skip_ranges, n_skip, stream, clip_coef, clip_value);
 }
 
 extern "C" int hulc_adamw_step(float* p, const float* g, float* m, float* v, void* bf16_shadow, long n, float lr, float beta1, float beta2,
                                float eps, float weight_decay, int step, const unsigned long long* step_state, float grad_scale, const int* skip_flag,
                                void* lo_shadow, const long* lo_ranges, int n_ranges, const float* loss_scale, const float* found_inf,
                                const float* lr_dev, const long* skip_ranges, int n_skip, void* stream) {
-    RuleArgs a = {};
-    a.lr = lr; a.wd = weight_decay; a.gscale = grad_scale; a.b1 = beta1; a.b2 = beta2; a.eps = eps;
-    a.b1d = meant_decimal(beta1); a.b2d = meant_decimal(beta2);
-    a.omb1 = (float)(1.0 - a.b1d); a.omb2 = (float)(1.0 - a.b2d);
-    return rule_launch<RULE_ADAMW>("hulc_adamw_step", p, g, m, v, bf16_shadow, n, a, step, step_state, skip_flag, lo_shadow, lo_ranges, n_ranges,
-                                   loss_scale, found_inf, lr_dev, skip_ranges, n_skip, stream);
+    return hulc_adamw_step_clip(p, g, m, v, bf16_shadow, n, lr, beta1, beta2, eps, weight_decay, step, step_state, grad_scale, skip_flag, lo_shadow,
+                                lo_ranges, n_ranges, loss_scale, found_inf, lr_dev, skip_ranges, n_skip, nullptr, 0.f, stream);
 }
 
-extern "C" int hulc_sgd_step(float* p, const float* g, float* buf, void* bf16_shadow, long n, float lr, float momentum, float dampening,
-                             int nesterov, float weight_decay, int step, const unsigned long long* step_state, float grad_scale,
-                             const int* skip_flag, void* lo_shadow, const long* lo_ranges, int n_ranges, const float* loss_scale,
-                             const float* found_inf, const float* lr_dev, const long* skip_ranges, int n_skip, void* stream) {
+extern "C" int hulc_sgd_step_clip(float* p, const float* g, float* buf, void* bf16_shadow, long n, float lr, float momentum, float dampening,
+                                  int nesterov, float weight_decay, int step, const unsigned long long* step_state, float grad_scale,
+                                  const int* skip_flag, void* lo_shadow, const long* lo_ranges, int n_ranges, const float* loss_scale,
+                                  const float* found_inf, const float* lr_dev, const long* skip_ranges, int n_skip, const float* clip_coef,
+                                  float clip_value, void* stream) {
     // torch.optim.SGD's own refusals
     if (nesterov && (momentum <= 0.f || dampening != 0.f)) return hulc_fail(-2, "hulc_sgd_step: nesterov momentum requires a momentum and zero dampening");
     if (momentum != 0.f && !buf) return hulc_fail(-2, "hulc_sgd_step: momentum != 0 needs a momentum buffer");
@@ -565,7 +713,15 @@ extern "C" int hulc_sgd_step(float* p, const float* g, float* buf, void* bf16_sh
     a.omd = (float)(1.0 - meant_decimal(dampening));
     a.b1d = a.b2d = 0.0;
     return rule_launch<RULE_SGD>("hulc_sgd_step", p, g, momentum != 0.f ? buf : nullptr, nullptr, bf16_shadow, n, a, step, step_state, skip_flag,
-                                 lo_shadow, lo_ranges, n_ranges, loss_scale, found_inf, lr_dev, skip_ranges, n_skip, stream);
+                                 lo_shadow, lo_ranges, n_ranges, loss_scale, found_inf, lr_dev, skip_ranges, n_skip, stream, clip_coef, clip_value);
+}
+
+extern "C" int hulc_sgd_step(float* p, const float* g, float* buf, void* bf16_shadow, long n, float lr, float momentum, float dampening,
+                             int nesterov, float weight_decay, int step, const unsigned long long* step_state, float grad_scale,
+                             const int* skip_flag, void* lo_shadow, const long* lo_ranges, int n_ranges, const float* loss_scale,
+                             const float* found_inf, const float* lr_dev, const long* skip_ranges, int n_skip, void* stream) {
+    return hulc_sgd_step_clip(p, g, buf, bf16_shadow, n, lr, momentum, dampening, nesterov, weight_decay, step, step_state, grad_scale, skip_flag,
+                              lo_shadow, lo_ranges, n_ranges, loss_scale, found_inf, lr_dev, skip_ranges, n_skip, nullptr, 0.f, stream);
 }
 
 extern "C" int hulc_cast_f32_to_bf16(const float* src, void* dst, long n, void* stream) {

@@ -1455,17 +1455,24 @@ def window_rows(store, starts, sizes, B, S, out, zero_cols=(0, 0)):
 
 
 def adam_step(p, g, m, v, shadow, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, step_state_dev=None, lo=None, lo_ranges=(),
-              loss_scale_dev=None, found_inf_dev=None, lr_dev=None):
+              loss_scale_dev=None, found_inf_dev=None, lr_dev=None, clip_coef_dev=None, clip_value=0.0):
     """step_state_dev: device {rng, step} words (see step_state); when given, the step count is read on device.  The update is skipped
     on the device while the fault word is set (a barrier kernel timed out upstream) — check_faults() then raises on the host.
     lo (bf16 arena like shadow) + lo_ranges (<= 8 (begin, end) element ranges): the rounding remainders w - bf16(w) of the updated weights
     inside the ranges are written by the same pass (hulc_adam_step_lo).
     lr_dev: one-element fp32 tensor on the parameters' device holding the learning rate (hulc_adam_step_sched); `lr` is then ignored and a
-    captured launch follows whatever the host writes into lr_dev between replays."""
+    captured launch follows whatever the host writes into lr_dev between replays.
+    clip_coef_dev (one-element fp32 tensor: what grad_norm_clip left in out[1:2]) / clip_value (> 0): gradient clipping by norm / by value
+    inside the pass (hulc_adam_step_clip); with neither set the launch is exactly the one above."""
     # algorithmic bytes per element (bench.py's roofline): p, g, m, v read (16 B), p, m, v written (12 B), the bf16 shadow (2 B) and, inside
     # lo_ranges, the remainder (2 B)
     n_lo = sum(int(e) - int(b) for b, e in lo_ranges) if (lo is not None and lo_ranges) else 0
     nbytes = float(n) * (16 + 12 + (2 if shadow is not None else 0)) + 2.0 * n_lo
+    if clip_coef_dev is not None or clip_value:
+        _call("hulc_adam_step_clip", p, g, m, v, shadow, n, lr, beta1, beta2, eps, weight_decay, step, step_state_dev, grad_scale,
+              *_rule_tail("adam_step", p, lo, lo_ranges, loss_scale_dev, found_inf_dev, lr_dev, (), clip_coef_dev)[:7], clip_coef_dev,
+              float(clip_value), nbytes=nbytes)
+        return
     if lr_dev is not None or loss_scale_dev is not None or found_inf_dev is not None:
         # device scalars: torch.amp.GradScaler's (hulc_adam_step_amp, ABI 5) and the learning rate (hulc_adam_step_sched) — fp32 tensors of
         # one element on the arena's device
@@ -1492,11 +1499,11 @@ def adam_step(p, g, m, v, shadow, n, lr, beta1, beta2, eps, weight_decay, step, 
           step_state_dev, grad_scale, fault_word(p.device), lo, arr, len(lo_ranges), nbytes=nbytes)
 
 
-def _rule_tail(name, p, lo, lo_ranges, loss_scale_dev, found_inf_dev, lr_dev, skip_ranges):
+def _rule_tail(name, p, lo, lo_ranges, loss_scale_dev, found_inf_dev, lr_dev, skip_ranges, clip_coef_dev=None):
     """the arguments hulc_adamw_step / hulc_sgd_step share behind grad_scale: fault word, remainders, device scalars, skip ranges"""
-    for t in (lr_dev, loss_scale_dev, found_inf_dev):
+    for t in (lr_dev, loss_scale_dev, found_inf_dev, clip_coef_dev):
         if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != 1 or t.device != p.device):
-            raise _L.HulcKernelError(f"{name}: lr_dev / loss_scale / found_inf are one-element fp32 tensors on the parameters' device")
+            raise _L.HulcKernelError(f"{name}: lr_dev / loss_scale / found_inf / clip_coef are one-element fp32 tensors on the parameters' device")
     has_lo = lo is not None and bool(lo_ranges)
     flat = [int(x) for r in lo_ranges for x in r] if has_lo else [0, 0]
     arr = (_c.c_long * len(flat))(*flat)
@@ -1507,24 +1514,48 @@ def _rule_tail(name, p, lo, lo_ranges, loss_scale_dev, found_inf_dev, lr_dev, sk
 
 
 def adamw_step(p, g, m, v, shadow, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, step_state_dev=None, lo=None, lo_ranges=(),
-               loss_scale_dev=None, found_inf_dev=None, lr_dev=None, skip_ranges=()):
-    """torch.optim.AdamW (decoupled weight decay) over the arena (hulc_adamw_step); arguments as adam_step's.
+               loss_scale_dev=None, found_inf_dev=None, lr_dev=None, skip_ranges=(), clip_coef_dev=None, clip_value=0.0):
+    """torch.optim.AdamW (decoupled weight decay) over the arena (hulc_adamw_step; hulc_adamw_step_clip when clip_coef_dev or clip_value
+    is set); arguments as adam_step's.
     skip_ranges: <= 8 (begin, end) element ranges, starts multiples of 4, that the pass leaves untouched (parameters without a gradient)."""
     n_lo = sum(int(e) - int(b) for b, e in lo_ranges) if (lo is not None and lo_ranges) else 0
     nbytes = float(n) * (16 + 12 + (2 if shadow is not None else 0)) + 2.0 * n_lo       # as adam_step: 30 B per element (+ 2 inside lo_ranges)
-    _call("hulc_adamw_step", p, g, m, v, shadow, n, lr, beta1, beta2, eps, weight_decay, step, step_state_dev, grad_scale,
-          *_rule_tail("adamw_step", p, lo, lo_ranges, loss_scale_dev, found_inf_dev, lr_dev, skip_ranges), nbytes=nbytes)
+    tail = _rule_tail("adamw_step", p, lo, lo_ranges, loss_scale_dev, found_inf_dev, lr_dev, skip_ranges, clip_coef_dev)
+    clip = (clip_coef_dev, float(clip_value)) if (clip_coef_dev is not None or clip_value) else ()
+    _call("hulc_adamw_step_clip" if clip else "hulc_adamw_step", p, g, m, v, shadow, n, lr, beta1, beta2, eps, weight_decay, step, step_state_dev,
+          grad_scale, *tail, *clip, nbytes=nbytes)
 
 
 def sgd_step(p, g, buf, shadow, n, lr, momentum, dampening, nesterov, weight_decay, step, grad_scale=1.0, step_state_dev=None, lo=None,
-             lo_ranges=(), loss_scale_dev=None, found_inf_dev=None, lr_dev=None, skip_ranges=()):
+             lo_ranges=(), loss_scale_dev=None, found_inf_dev=None, lr_dev=None, skip_ranges=(), clip_coef_dev=None, clip_value=0.0):
     """torch.optim.SGD (momentum / dampening / nesterov / L2 weight decay) over the arena (hulc_sgd_step).  buf: the momentum buffers' arena,
     None with momentum == 0.  The first step (step == 1, on the device when step_state_dev is given) copies the gradient into the buffer."""
     # p, g read and p written (12 B), the momentum buffer read and written (8 B), the bf16 shadow (2 B): 22 B per element, 14 B without momentum
     n_lo = sum(int(e) - int(b) for b, e in lo_ranges) if (lo is not None and lo_ranges) else 0
     nbytes = float(n) * (12 + (8 if (buf is not None and momentum != 0) else 0) + (2 if shadow is not None else 0)) + 2.0 * n_lo
-    _call("hulc_sgd_step", p, g, buf, shadow, n, lr, momentum, dampening, int(bool(nesterov)), weight_decay, step, step_state_dev, grad_scale,
-          *_rule_tail("sgd_step", p, lo, lo_ranges, loss_scale_dev, found_inf_dev, lr_dev, skip_ranges), nbytes=nbytes)
+    tail = _rule_tail("sgd_step", p, lo, lo_ranges, loss_scale_dev, found_inf_dev, lr_dev, skip_ranges, clip_coef_dev)
+    clip = (clip_coef_dev, float(clip_value)) if (clip_coef_dev is not None or clip_value) else ()      # hulc_sgd_step_clip: clipping inside the pass
+    _call("hulc_sgd_step_clip" if clip else "hulc_sgd_step", p, g, buf, shadow, n, lr, momentum, dampening, int(bool(nesterov)), weight_decay, step,
+          step_state_dev, grad_scale, *tail, *clip, nbytes=nbytes)
+
+
+_grad_norm_ws = {}
+
+
+def grad_norm_clip(g, n, grad_scale, loss_scale_dev, max_norm, out):
+    """out[0] = the L2 norm of g[:n] * grad_scale (/ *loss_scale_dev when given), out[1] = torch.nn.utils.clip_grad_norm_'s multiplier for
+    max_norm (hulc_grad_norm_clip: two launches, deterministic, no host synchronisation).  out: two fp32 elements on g's device; its second
+    element is the `clip_coef_dev` of adam_step / adamw_step / sgd_step.  The workspace (one double per workgroup) is cached per device."""
+    for t, k in ((out, 2), (loss_scale_dev, 1)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != k or t.device != g.device or not t.is_contiguous()):
+            raise _L.HulcKernelError("grad_norm_clip: out is two fp32 elements, loss_scale one, contiguous on the gradients' device")
+    if g.dtype != torch.float32 or not g.is_contiguous() or g.numel() < n:
+        raise _L.HulcKernelError("grad_norm_clip: g is a contiguous fp32 tensor of at least n elements")
+    need = int(_L.load().hulc_grad_norm_ws_bytes(int(n)))
+    ws = _grad_norm_ws.get(g.device)
+    if ws is None or ws.numel() * 8 < need:           # (at most 16 KiB: the grid is capped; doubles, so the buffer is 8-byte aligned)
+        ws = _grad_norm_ws[g.device] = torch.empty(max(need // 8, 2048), dtype=torch.float64, device=g.device)
+    _call("hulc_grad_norm_clip", g, int(n), float(grad_scale), loss_scale_dev, float(max_norm), out, ws, nbytes=4.0 * n)
 
 
 def step_count_advance_if(state, found_inf_dev=None) -> None:

@@ -132,6 +132,36 @@ class Hulc2(LightningModule):
         sched = make_lr_scheduler(sc, opt)
         return {"optimizer": opt, "lr_scheduler": {"scheduler": sched, "interval": "step", "frequency": 1}}
 
+    def configure_gradient_clipping(self, optimizer, *args, gradient_clip_val=None, gradient_clip_algorithm=None, **kwargs):
+        """Lightning's hook behind `trainer.gradient_clip_val` / `gradient_clip_algorithm`, called before every optimizer step.  Signatures:
+        (optimizer, optimizer_idx, gradient_clip_val, gradient_clip_algorithm) in Lightning 1.x, without optimizer_idx in 2.x; the two
+        values come positionally or by keyword.  A drop-in optimizer (hulc2_amd.optim.Adam / AdamW / SGD) is handed the setting
+        (set_grad_clip) and clips inside its own step — one norm pass over the gradient arena and a multiplier in the step kernel, under a
+        GradScaler too — so nothing is clipped here and `.grad` stays as backward left it.  Any other optimizer gets the base class's
+        behaviour, self.clip_gradients(...), where the base class has it."""
+        from ..optim import _ArenaStep
+        rest = list(args)
+        kwargs.pop("optimizer_idx", None)
+        is_algo = lambda x: x is None or isinstance(x, str) or hasattr(x, "value")
+        if len(rest) == 3 or (len(rest) == 2 and not is_algo(rest[1])) or (len(rest) == 1 and type(rest[0]) is int):
+            rest.pop(0)                                      # Lightning 1.x: optimizer_idx (Lightning itself passes the two values by keyword)
+        if rest:
+            gradient_clip_val = rest.pop(0)
+        if rest:
+            gradient_clip_algorithm = rest.pop(0)
+        algo = getattr(gradient_clip_algorithm, "value", gradient_clip_algorithm)      # (Lightning's GradClipAlgorithmType enum or a string)
+        inner = getattr(optimizer, "optimizer", optimizer)   # (a LightningOptimizer wraps the torch one)
+        if isinstance(inner, _ArenaStep):
+            algo = "norm" if algo is None else str(algo).lower()
+            if algo not in ("norm", "value"):
+                raise ValueError(f"configure_gradient_clipping: gradient_clip_algorithm {algo!r} is not 'norm' or 'value'")
+            val = float(gradient_clip_val) if gradient_clip_val else None
+            inner.set_grad_clip(max_norm=val if algo == "norm" else None, value=val if algo == "value" else None)
+            return
+        base = getattr(self, "clip_gradients", None)         # (pl.LightningModule's; the stand-in module of hulc2_amd.compat has none)
+        if base is not None:
+            base(optimizer, gradient_clip_val=gradient_clip_val, gradient_clip_algorithm=gradient_clip_algorithm)
+
     # ---- hot path ----------------------------------------------------------------------------------
     @staticmethod
     def _goal_site(is_lang: bool):

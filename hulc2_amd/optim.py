@@ -21,7 +21,13 @@ Whenever the fused form does not apply — parameters not (yet) in an arena, a p
 FIRST gradient arrives after the others have stepped (torch starts its step count at 1 then), amsgrad / maximize / Adam's decoupled weight
 decay / `fused=True`, several parameter groups, CPU — `step()` is the torch parent's step(), on the same state tensors.  Parameters that
 have NEVER had a gradient are left alone by AdamW and SGD through the kernels' skip ranges (torch skips them, decay included); Adam, whose
-kernel has none, takes torch's step when such parameters meet a weight decay."""
+kernel has none, takes torch's step when such parameters meet a weight decay.
+
+Gradient clipping (`max_grad_norm=` / `clip_grad_value=` at construction, `set_grad_clip()` later, Lightning's `gradient_clip_val` through
+Hulc2.configure_gradient_clipping) happens INSIDE the fused step: one norm pass over the gradient arena (hulc_grad_norm_clip, under a
+GradScaler with its scale as the pass's loss scale), then the step kernel multiplies — or, by value, clamps — every gradient in registers.
+The clipped gradient exists only there: `.grad` is left UNCLIPPED (and, under a GradScaler, still scaled) after a fused `step()`, where
+`clip_grad_norm_` would have rewritten it.  A step that falls back to torch's path clips with torch's own functions, `.grad` included."""
 import importlib
 from typing import Callable, Optional, Tuple
 
@@ -102,6 +108,12 @@ def trainer_kwargs_from_config(cfg) -> dict:
         cfg.pop("decoupled_weight_decay", None)
         out.update(betas=tuple(float(b) for b in cfg.pop("betas", (0.9, 0.999))), eps=float(cfg.pop("eps", 1e-8)),
                    weight_decay=float(cfg.pop("weight_decay", 1e-2 if kind == "adamw" else 0.0)))
+    # the drop-in optimizers' clipping keys (hulc2_amd.optim.Adam(max_grad_norm=... / clip_grad_value=...)) are the trainer's two arguments
+    norm, value = cfg.pop("max_grad_norm", None), cfg.pop("clip_grad_value", None)
+    if norm and value:
+        raise ValueError("optimizer config: max_grad_norm and clip_grad_value exclude each other")
+    if norm or value:
+        out.update(gradient_clip_val=float(norm or value), gradient_clip_algorithm="norm" if norm else "value")
     if cfg:
         raise NotImplementedError(f"optimizer config keys {sorted(cfg)} are not known to the arena trainer")
     return out
@@ -124,6 +136,7 @@ class _ArenaStep:
         self._dev_steps = None       # device words {unused, step count}: the kernel's bias correction reads the count from here
         self._skippable = False      # a GradScaler's found_inf has been handed in since the host count was last read back
         self.fused_launches = 0      # (tests / logging: steps taken by the fused path)
+        self._clip_out = None        # device {gradient norm, clip coefficient} of the fused path's last norm pass
         # torch.amp.GradScaler.step: hand `grad_scale` / `found_inf` over as attributes instead of unscaling and synchronising itself
         self._step_supports_amp_scaling = True
 
@@ -133,7 +146,50 @@ class _ArenaStep:
     def _uncovered(self, g) -> bool:
         raise NotImplementedError
 
-    def _launch(self, tr, flat_g, arenas, g, grad_scale, found_inf, skip_ranges) -> None:
+    # ---- gradient clipping -------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _clip_defaults(kw: dict) -> Tuple[Optional[float], Optional[float]]:
+        """take max_grad_norm / clip_grad_value out of a constructor's keyword arguments (torch's __init__ knows neither)"""
+        return kw.pop("max_grad_norm", None), kw.pop("clip_grad_value", None)
+
+    def set_grad_clip(self, max_norm: Optional[float] = None, value: Optional[float] = None) -> None:
+        """Clip the gradients of every following step: by their global L2 norm (torch.nn.utils.clip_grad_norm_(params, max_norm)) or by value
+        (clip_grad_value_(params, value)); None / 0 for both switches clipping off.  Stored as `max_grad_norm` / `clip_grad_value` in every
+        param group (the key is absent while that form is off: the groups of an unclipped optimizer are torch's own), so the setting travels in
+        state_dict()["param_groups"] and comes back with load_state_dict().  One threshold for all parameters: the norm is global."""
+        for name, x in (("max_norm", max_norm), ("value", value)):
+            if x is not None and not (0.0 <= float(x) < float("inf")):
+                raise ValueError(f"set_grad_clip: {name} must be finite and >= 0 (0 / None: off), got {x!r}")
+        if max_norm and value:
+            raise ValueError("set_grad_clip: clip by norm or by value, not both")
+        for g in self.param_groups:
+            for key, x in (("max_grad_norm", max_norm), ("clip_grad_value", value)):
+                if x:
+                    g[key] = float(x)
+                else:
+                    g.pop(key, None)
+
+    def _clip_kwargs(self, tr, flat_g, g, grad_scale) -> dict:
+        """the fused step's clipping: the norm pass (by norm) and the step kernel's clipping arguments"""
+        if g.get("clip_grad_value"):
+            return {"clip_value": float(g["clip_grad_value"])}
+        if not g.get("max_grad_norm"):
+            return {}
+        if self._clip_out is None or self._clip_out.device != tr.dev:
+            self._clip_out = torch.zeros(2, dtype=torch.float32, device=tr.dev)     # {norm of the unscaled gradients, clip coefficient}
+        kn.grad_norm_clip(flat_g, tr.total, 1.0, grad_scale, float(g["max_grad_norm"]), self._clip_out)
+        return {"clip_coef_dev": self._clip_out[1:2]}
+
+    def _torch_clip(self) -> None:
+        """the same clipping on torch's path, by torch's own functions on the (unscaled) `.grad`s"""
+        g0 = self.param_groups[0]
+        ps = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
+        if ps and g0.get("max_grad_norm"):
+            torch.nn.utils.clip_grad_norm_(ps, float(g0["max_grad_norm"]))
+        elif ps and g0.get("clip_grad_value"):
+            torch.nn.utils.clip_grad_value_(ps, float(g0["clip_grad_value"]))
+
+    def _launch(self, tr, flat_g, arenas, g, grad_scale, found_inf, skip_ranges, clip) -> None:
         raise NotImplementedError
 
     # ---- arena binding -----------------------------------------------------------------------------------------------------------------
@@ -226,6 +282,8 @@ class _ArenaStep:
         the way the scaler itself would have: unscale + inf check over the gradients, one synchronisation, skip on inf."""
         found_inf, grad_scale = getattr(self, "found_inf", None), getattr(self, "grad_scale", None)
         if any(g.get("fused") for g in self.param_groups):       # torch's own fused kernels take the scaler's scalars themselves
+            if any(g.get("max_grad_norm") or g.get("clip_grad_value") for g in self.param_groups):
+                raise NotImplementedError("gradient clipping with torch's fused=True step: its kernel unscales the gradients itself, after any clip")
             return super().step()
         if found_inf is not None or grad_scale is not None:
             grads = [p.grad for g in self.param_groups for p in g["params"] if p.grad is not None]
@@ -240,6 +298,7 @@ class _ArenaStep:
             self.found_inf = self.grad_scale = None             # (torch's foreach path refuses the attributes; GradScaler deletes them afterwards)
             if found_inf is not None and float(found_inf.item()) != 0.0:
                 return
+        self._torch_clip()                                       # (after the unscale, as scaler.unscale_ + clip_grad_norm_ in a torch loop)
         super().step()
 
     @torch.no_grad()
@@ -310,7 +369,7 @@ class _ArenaStep:
             grad_scale = grad_scale.reshape(1).to(device=tr.dev, dtype=torch.float32)
         self._fused_steps += 1
         kn.step_count_advance_if(self._dev_steps, found_inf)
-        self._launch(tr, flat_g, arena[3:], g, grad_scale, found_inf, skip)
+        self._launch(tr, flat_g, arena[3:], g, grad_scale, found_inf, skip, self._clip_kwargs(tr, flat_g, g, grad_scale))
         tr.derive_after_step()
         # the kernel wrote the arena directly: the parameters' version counters did not move, so the keeper's staleness check (sum of the
         # versions) sees nothing to refresh — which is right, its copies came out of the same launches
@@ -352,14 +411,20 @@ class _ArenaStep:
         return super().state_dict()
 
     def load_state_dict(self, state_dict):
+        g0 = self.param_groups[0]
+        mine = (g0.get("max_grad_norm"), g0.get("clip_grad_value"))
         super().load_state_dict(state_dict)
+        if not any("max_grad_norm" in g or "clip_grad_value" in g for g in state_dict["param_groups"]):
+            self.set_grad_clip(*mine)                             # (a state written without clipping keys, e.g. torch's own: this optimizer's setting stays)
         self._arena = None                                        # the loaded tensors are re-homed into the arenas by the next step()
 
 
 class Adam(_ArenaStep, torch.optim.Adam):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, **kw):
+        clip = self._clip_defaults(kw)
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, **kw)
         self._arena_init()
+        self.set_grad_clip(*clip)
 
     def _state_names(self, g) -> tuple:
         return ("exp_avg", "exp_avg_sq")
@@ -367,11 +432,11 @@ class Adam(_ArenaStep, torch.optim.Adam):
     def _uncovered(self, g) -> bool:
         return bool(g.get("amsgrad") or g.get("capturable") or g.get("decoupled_weight_decay"))
 
-    def _launch(self, tr, flat_g, arenas, g, grad_scale, found_inf, skip_ranges) -> None:
+    def _launch(self, tr, flat_g, arenas, g, grad_scale, found_inf, skip_ranges, clip) -> None:
         m, v = arenas
         kn.adam_step(tr.flat_p, flat_g, m, v, tr.flat_bf16, tr.total, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]),
                      float(g["eps"]), float(g["weight_decay"]), self._fused_steps, grad_scale=1.0, step_state_dev=self._dev_steps,
-                     lo=tr.flat_lo, lo_ranges=tr.lo_ranges, loss_scale_dev=grad_scale, found_inf_dev=found_inf)
+                     lo=tr.flat_lo, lo_ranges=tr.lo_ranges, loss_scale_dev=grad_scale, found_inf_dev=found_inf, **clip)
 
 
 class AdamW(_ArenaStep, torch.optim.AdamW):
@@ -380,8 +445,10 @@ class AdamW(_ArenaStep, torch.optim.AdamW):
     _skips = True
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, **kw):
+        clip = self._clip_defaults(kw)
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, **kw)
         self._arena_init()
+        self.set_grad_clip(*clip)
 
     def _state_names(self, g) -> tuple:
         return ("exp_avg", "exp_avg_sq")
@@ -389,11 +456,11 @@ class AdamW(_ArenaStep, torch.optim.AdamW):
     def _uncovered(self, g) -> bool:
         return bool(g.get("amsgrad") or g.get("capturable") or not g.get("decoupled_weight_decay"))
 
-    def _launch(self, tr, flat_g, arenas, g, grad_scale, found_inf, skip_ranges) -> None:
+    def _launch(self, tr, flat_g, arenas, g, grad_scale, found_inf, skip_ranges, clip) -> None:
         m, v = arenas
         kn.adamw_step(tr.flat_p, flat_g, m, v, tr.flat_bf16, tr.total, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]),
                       float(g["eps"]), float(g["weight_decay"]), self._fused_steps, grad_scale=1.0, step_state_dev=self._dev_steps,
-                      lo=tr.flat_lo, lo_ranges=tr.lo_ranges, loss_scale_dev=grad_scale, found_inf_dev=found_inf, skip_ranges=skip_ranges)
+                      lo=tr.flat_lo, lo_ranges=tr.lo_ranges, loss_scale_dev=grad_scale, found_inf_dev=found_inf, skip_ranges=skip_ranges, **clip)
 
 
 class SGD(_ArenaStep, torch.optim.SGD):
@@ -404,8 +471,10 @@ class SGD(_ArenaStep, torch.optim.SGD):
     _counts_steps = False
 
     def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, **kw):
+        clip = self._clip_defaults(kw)
         super().__init__(params, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov, **kw)
         self._arena_init()
+        self.set_grad_clip(*clip)
 
     def _state_names(self, g) -> tuple:
         return ("momentum_buffer",) if g["momentum"] != 0 else ()
@@ -413,8 +482,8 @@ class SGD(_ArenaStep, torch.optim.SGD):
     def _uncovered(self, g) -> bool:
         return False
 
-    def _launch(self, tr, flat_g, arenas, g, grad_scale, found_inf, skip_ranges) -> None:
+    def _launch(self, tr, flat_g, arenas, g, grad_scale, found_inf, skip_ranges, clip) -> None:
         kn.sgd_step(tr.flat_p, flat_g, arenas[0] if arenas else None, tr.flat_bf16, tr.total, float(g["lr"]), float(g["momentum"]),
                     float(g["dampening"]), bool(g["nesterov"]), float(g["weight_decay"]), self._fused_steps, grad_scale=1.0,
                     step_state_dev=self._dev_steps, lo=tr.flat_lo, lo_ranges=tr.lo_ranges, loss_scale_dev=grad_scale, found_inf_dev=found_inf,
-                    skip_ranges=skip_ranges)
+                    skip_ranges=skip_ranges, **clip)

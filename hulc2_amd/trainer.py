@@ -315,12 +315,17 @@ class ArenaTrainer(WeightKeeper):
     def __init__(self, model: torch.nn.Module, lr: float = 2e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                  bucket_mb: int = 32, group=None, overlap: bool = True, comm_algo: Optional[str] = None, grad_payload: Optional[str] = None,
                  force_comm: bool = False, optimizer: str = "adam", momentum: float = 0.0, dampening: float = 0.0, nesterov: bool = False,
-                 skip_params=()):
+                 skip_params=(), gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm"):
         """optimizer: the update rule of optimizer_step() — "adam" (torch.optim.Adam, L2 weight decay), "adamw" (torch.optim.AdamW, decoupled
         decay) or "sgd" (torch.optim.SGD with momentum / dampening / nesterov, L2 weight decay): conf/model/optimizer/{adam,adamw,sgd}.yaml;
         hulc2_amd.optim.trainer_kwargs_from_config maps such a config to these arguments.
         skip_params (adamw / sgd): parameters that never receive a gradient.  Their arena ranges (neighbours merged, at most 8) are left
         untouched by the step, as torch leaves a parameter without a gradient — weight decay would shrink them otherwise.
+        gradient_clip_val / gradient_clip_algorithm: Lightning's trainer flags of the same names (0 / None: off).  "norm": the global L2 norm
+        of the finished (all-reduced, 1 / world scaled) gradient arena is taken by one deterministic pass (hulc_grad_norm_clip) and the
+        step multiplies every gradient by min(1, gradient_clip_val / (norm + 1e-6)) in registers, as torch.nn.utils.clip_grad_norm_ would
+        have in memory; "value": the step clamps every gradient to [-gradient_clip_val, gradient_clip_val] (clip_grad_value_).  Every rank
+        reads the same arena with the same kernel, so all ranks apply the same bits; set_gradient_clip changes the threshold later.
         force_comm: run the multi-rank control flow (split graphs, comm stream, collectives) even with a single rank in the process
         group — how the RCCL path is exercised on a one-GPU box."""
         if optimizer not in ("adam", "adamw", "sgd"):
@@ -330,6 +335,7 @@ class ArenaTrainer(WeightKeeper):
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
         self.optimizer, self.momentum, self.dampening, self.nesterov = optimizer, float(momentum), float(dampening), bool(nesterov)
         self.base_lr = lr                                  # what a schedule's factor multiplies (torch: the group's initial_lr)
+        self.clip_val, self.clip_algorithm = self._check_clip(gradient_clip_val, gradient_clip_algorithm)
         self.step_node = False                             # (the step node is the keeper's, under an external optimizer)
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.multi = self.world > 1 or (force_comm and dist.is_initialized())
@@ -353,6 +359,7 @@ class ArenaTrainer(WeightKeeper):
         if use_sinks:                                      # no per-parameter all-reduce hooks depend on AccumulateGrad
             self._register_sinks(None)
             self._acc_hooks = [p.register_post_accumulate_grad_hook(self._saw_autograd_grad) for p in self.params]
+        self._clip_out = torch.zeros(2, dtype=torch.float32, device=dev)      # {gradient norm, clip coefficient} of the last norm pass
         self.step_count = 0
         if dev.type == "cuda":
             kn.step_state(dev)[1] = 0               # the device-resident Adam step count starts with this trainer (the RNG word keeps walking)
@@ -623,6 +630,44 @@ class ArenaTrainer(WeightKeeper):
         if self._lr_lambda is not None:
             self.set_lr(float(self.base_lr) * self._lr_lambda(self._opt_steps))
 
+    # ---- gradient clipping (Lightning: trainer.gradient_clip_val / gradient_clip_algorithm) ------------------------------------------------
+    @staticmethod
+    def _check_clip(val, algorithm):
+        if algorithm not in ("norm", "value"):
+            raise ValueError(f"ArenaTrainer: gradient_clip_algorithm {algorithm!r} is not 'norm' or 'value'")
+        val = 0.0 if val is None else float(val)
+        if not (0.0 <= val < float("inf")):
+            raise ValueError(f"ArenaTrainer: gradient_clip_val must be finite and >= 0 (0 / None: off), got {val!r}")
+        return val, algorithm
+
+    def set_gradient_clip(self, val: Optional[float], algorithm: Optional[str] = None) -> None:
+        """The clipping threshold (and, optionally, the algorithm) of the following optimizer steps; 0 / None switches clipping off.  Both are
+        kernel arguments of the captured optimizer graph, so a change drops the graphs (as _set_hparams does for lr / betas): replay() then
+        asks for a new capture() instead of clipping at the old threshold."""
+        new = self._check_clip(val, self.clip_algorithm if algorithm is None else algorithm)
+        if new != (self.clip_val, self.clip_algorithm) and getattr(self, "graph_opt", None) is not None:
+            self.graph_fb = self.graph_enc = self.graph_opt = None
+        self.clip_val, self.clip_algorithm = new
+
+    @property
+    def grad_norm(self) -> torch.Tensor:
+        """one-element device tensor: the global L2 norm of the gradients the last optimizer step saw (before clipping), written by the norm
+        pass of gradient_clip_algorithm="norm" — for logging without a synchronisation; it follows the replays of a captured graph."""
+        return self._clip_out[0:1]
+
+    def last_grad_norm(self) -> float:
+        """grad_norm as a Python float.  SYNCHRONISES the host with the device (a .item()): call it where a sync happens anyway."""
+        return float(self._clip_out[0].item())
+
+    def _clip_args(self) -> dict:
+        """launch the norm pass when clipping by norm and hand the step kernel its clipping arguments"""
+        if not self.clip_val:
+            return {}
+        if self.clip_algorithm == "value":
+            return {"clip_value": self.clip_val}
+        kn.grad_norm_clip(self.flat_g, self.total, 1.0 / self.world, None, self.clip_val, self._clip_out)
+        return {"clip_coef_dev": self._clip_out[1:2]}
+
     # ---- KL annealing: the KL weight as a device scalar the captured KL launches read (Hulc2.set_kl_beta) --------------------------------
     _kl_captured = None            # the by-value KL weight baked into the captured graphs; None: no graphs, or they read the model's device word
     _kl_schedule = None            # the attached annealing rule (set_kl_schedule)
@@ -712,7 +757,8 @@ class ArenaTrainer(WeightKeeper):
         common = dict(grad_scale=1.0 / self.world,
                       step_state_dev=kn.step_state(self.dev),      # step count lives on the device (graph replay)
                       lo=self.flat_lo, lo_ranges=self.lo_ranges,   # (the split operands' remainders come out of the same pass)
-                      lr_dev=self._lr_dev)                         # (None unless set_lr / set_lr_schedule was called)
+                      lr_dev=self._lr_dev,                         # (None unless set_lr / set_lr_schedule was called)
+                      **self._clip_args())                         # (gradient clipping: the norm pass runs here, in front of the step)
         if self.optimizer == "adam":
             kn.adam_step(self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.flat_bf16, self.total, self.lr, self.betas[0],
                          self.betas[1], self.eps, self.wd, self.step_count, **common)

@@ -741,6 +741,40 @@ int hulc_sgd_step(float* p, const float* g, float* buf, void* bf16_shadow, long 
                   int nesterov, float weight_decay, int step, const unsigned long long* step_state, float grad_scale,
                   const int* skip_flag, void* lo_shadow, const long* lo_ranges, int n_ranges, const float* loss_scale,
                   const float* found_inf, const float* lr_dev, const long* skip_ranges, int n_skip, void* stream);
+/* (added under ABI 7 — new symbols only; every earlier prototype and hulc_abi_version() are unchanged.)  GRADIENT CLIPPING on the arena, in
+ * Lightning's two forms (trainer.gradient_clip_val / gradient_clip_algorithm = norm | value).
+ * hulc_grad_norm_clip: out[0] = the L2 norm of the effective gradient g * s over [0, n), s = grad_scale * (float)(1.0 / (double)*loss_scale)
+ * as the step kernels form it (loss_scale optional, a device float): (float)(sqrt(S) * (double)s) with S = sum g^2 accumulated in double.
+ * out[1] = the multiplier torch.nn.utils.clip_grad_norm_ applies, min(1, fl(fl(1 / fl(out[0] + 1e-6f)) * max_norm)) — reciprocal, then
+ * multiply, each rounded to fp32, which is what torch's `max_norm / (total_norm + 1e-6)` evaluates; a NaN norm gives a NaN multiplier, an
+ * infinite one 0.  out: device float[2], 4-byte aligned.  Two launches, deterministic (no atomics: a grid that depends on n alone, one
+ * double per workgroup into ws, summed in index order by one workgroup), no host synchronisation, capturable.  ws: device memory of
+ * hulc_grad_norm_ws_bytes(n) bytes, 8-byte aligned, needs no clearing.  Elements of the arena that belong to no gradient must be zero.
+ * max_norm < 0 or NaN is refused (-2), g not 16-byte aligned -4. */
+long hulc_grad_norm_ws_bytes(long n);
+int hulc_grad_norm_clip(const float* g, long n, float grad_scale, const float* loss_scale, float max_norm, float* out, void* ws, void* stream);
+/* The three optimizer steps with the clip applied to the effective gradient IN REGISTERS (the gradient arena is not written, no second pass).
+ * Arguments: those of hulc_adam_step_sched (lr_dev OPTIONAL here, NULL = the scalar lr) / hulc_adamw_step / hulc_sgd_step, then
+ *   clip_coef   optional device float (4-byte aligned), read once per thread at kernel start — out + 1 of hulc_grad_norm_clip.  The effective
+ *               gradient is fl(fl(g * s) * *clip_coef): two rounded products in torch's order (unscale_, then the clip), never contracted
+ *               into the weight-decay term that follows
+ *   clip_value  0 = off; c > 0: the effective gradient is g * s clamped to [-c, c] by comparisons (torch.nn.utils.clip_grad_value_: a NaN
+ *               stays a NaN)
+ * AdamW's moments and SGD's first-step copy see the clipped gradient.  Both a coefficient and a value, and a negative or non-finite
+ * clip_value, are refused (-2).  With clip_coef == NULL and clip_value == 0 these ARE the unclipped entry points (same kernel, same bits). */
+int hulc_adam_step_clip(float* p, const float* g, float* m, float* v, void* bf16_shadow, long n, float lr, float beta1, float beta2,
+                        float eps, float weight_decay, int step, const unsigned long long* step_state, float grad_scale, const int* skip_flag,
+                        void* lo_shadow, const long* lo_ranges, int n_ranges, const float* loss_scale, const float* found_inf,
+                        const float* lr_dev, const float* clip_coef, float clip_value, void* stream);
+int hulc_adamw_step_clip(float* p, const float* g, float* m, float* v, void* bf16_shadow, long n, float lr, float beta1, float beta2,
+                         float eps, float weight_decay, int step, const unsigned long long* step_state, float grad_scale, const int* skip_flag,
+                         void* lo_shadow, const long* lo_ranges, int n_ranges, const float* loss_scale, const float* found_inf,
+                         const float* lr_dev, const long* skip_ranges, int n_skip, const float* clip_coef, float clip_value, void* stream);
+int hulc_sgd_step_clip(float* p, const float* g, float* buf, void* bf16_shadow, long n, float lr, float momentum, float dampening,
+                       int nesterov, float weight_decay, int step, const unsigned long long* step_state, float grad_scale,
+                       const int* skip_flag, void* lo_shadow, const long* lo_ranges, int n_ranges, const float* loss_scale,
+                       const float* found_inf, const float* lr_dev, const long* skip_ranges, int n_skip, const float* clip_coef,
+                       float clip_value, void* stream);
 /* Device-resident step state {rng word, optimizer step count}: advanced by one kernel per training step so that
  * a captured hipGraph replays with fresh dropout masks / plan samples and the right Adam bias correction.
  * RNG kernels xor state[0] into their site seed (seed_dev = state); hulc_adam_step reads state[1] when
