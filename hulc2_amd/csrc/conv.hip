@@ -19,24 +19,10 @@
 //       workgroups, fp32 partial slabs summed by a second deterministic pass; the bias gradient
 //       (column sums of dY) rides along.
 #include "hulc_common.h"
-#include "hulc_abi_internal.h"
+#include "conv_band.h"
 #include <stdlib.h>
 
-// LDS-band kernel (conv_band.hip): 0 = launched, 1 = geometry not covered (use the gather kernel), < 0 = error
-int hulc_conv_band_dispatch(int C, int NSET, int TH, int TW, int S, const void* x, int x_dtype, int N, int H, int W, int pad_y, int pad_x,
-                            long x_sn, long x_sy, long x_sx, void* y, int y_dtype, long y_sn, long y_sy, long y_sx, const void* wt,
-                            int w_dtype, long ldw, const float* bias, const void* mask, int mask_dtype, int relu, int ncls,
-                            const int* cls_OH, const int* cls_OW, const long* cls_yoff, const int* cls_cobase, const long* cls_wrow0,
-                            const long* cls_wtap, const void* add, unsigned* bits_out, const unsigned* bits_in, int bits_channels, void* y16,
-                            hipStream_t s);
-// LDS-band conv1 forward (conv1_band.hip): NCHW fp32 frames, 3 -> 32 channels, 8x8 stride 4; same return convention
-int hulc_conv1_band_dispatch(const float* x, const void* w, int w_dtype, long ldw, const float* bias, void* y, int y_dtype, int relu,
-                             int N, int H, int W, int u8, int pad, const int* shift, const int* fidx, unsigned* relu_bits, const void* w_lo,
-                             const void* x2, int n_split, const void* x_slot, const void* x2_slot, int slots, hipStream_t s);
-// LDS-band weight gradient (conv_wgrad_band.hip): same return convention
-int hulc_conv_wgrad_band_dispatch(int nchw, int Cin, int Cout, int KH, int KW, int S, const void* x, int x_dtype, const void* dy, int dy_dtype,
-                                  int N, int H, int W, float* dw, float* db, void* ws, long ws_bytes, int dw_oihw, int accumulate, int u8, int pad,
-                                  const int* shift, const int* fidx, const void* x2, int n_split, const void* x_slot, const void* x2_slot, int slots, hipStream_t s);
+using namespace hulc_band;
 
 namespace {
 
@@ -603,7 +589,7 @@ __global__ __launch_bounds__(1024) void reduce_partials_kernel(const float* __re
 void fill_gather(GatherP& g, const hulc_conv_desc* d) {
     g.x_dtype = d->x_dtype; g.w_dtype = d->w_dtype;
     g.Nimg = d->N; g.H = d->H; g.W = d->W;
-    g.OH = (d->H - d->KH) / d->stride + 1; g.OW = (d->W - d->KW) / d->stride + 1;
+    g.OH = conv_OH(*d); g.OW = conv_OW(*d);
     g.Cout = d->Cout; g.stride = d->stride; g.check_bounds = 0; g.grid_kw = 0; g.grid_pad = 0; g.stride_x = d->stride;
     if (d->x_nchw) {   // k = (c, kh, kw): one tap per (c, kh), inner run = KW along x
         g.x_sn = (long)d->Cin * d->H * d->W; g.x_sy = d->W; g.x_sx = 1;
@@ -629,7 +615,7 @@ void fill_gather(GatherP& g, const hulc_conv_desc* d) {
     g.ldw = (long)g.ntaps << g.inner_log2;
 }
 
-int validate(const hulc_conv_desc* d, const char* who) {
+int validate(const hulc_conv_desc* d) {
     if (!d) return hulc_fail(-1, "conv: null descriptor");
     if (d->N <= 0 || d->H < d->KH || d->W < d->KW || d->stride <= 0) return hulc_fail(-2, "conv: bad geometry");
     const int taps = d->x_nchw ? d->Cin * d->KH : d->KH * d->KW;
@@ -639,8 +625,24 @@ int validate(const hulc_conv_desc* d, const char* who) {
     if (d->Cout != 32 && d->Cout != 64) return hulc_fail(-5, "conv: Cout must be 32 or 64");
     if (d->compute == HULC_F32 && (d->x_dtype != HULC_F32 || d->w_dtype != HULC_F32)) return hulc_fail(-6, "conv: f32 compute requires f32 operands");
     if (d->frame_index && !d->x_u8_nhwc) return hulc_fail(-7, "conv: frame_index addresses a uint8 NHWC episode store (x_u8_nhwc = 1)");
-    (void)who;
     return 0;
+}
+
+// The band request of a forward conv with the gather description g: the Cout / 32 output-channel tiles of one grid as the classes (planes, twin: the caller's)
+BandReq forward_band_request(const hulc_conv_desc* d, const GatherP& g, int pad) {
+    BandReq rq = {};
+    rq.C = d->Cin; rq.NSET = d->Cout / 32; rq.TH = d->KH; rq.TW = d->KW; rq.S = d->stride;
+    BandP& p = rq.p;
+    p.X = g.X; p.x_dtype = g.x_dtype; p.Y = g.Y; p.y_dtype = g.y_dtype; p.Wt = g.Wt; p.w_dtype = g.w_dtype;
+    p.Nimg = d->N; p.H = d->H; p.W = d->W; p.pad_y = pad; p.pad_x = pad;
+    p.x_sn = g.x_sn; p.x_sy = g.x_sy; p.x_sx = g.x_sx; p.y_sn = g.y_sn; p.y_sy = g.y_sy; p.y_sx = g.y_sx; p.ldw = g.ldw;
+    p.bias = g.bias; p.mask_dtype = g.mask_dtype; p.add = g.add; p.relu = d->relu;
+    for (int c = 0; c < rq.NSET && c < BAND_MAXCLS; ++c) {      // (more sets than classes: the dispatcher hands the launch back)
+        BandCls& cl = p.cls[c];
+        cl.OH = g.OH; cl.OW = g.OW; cl.y_off = 0; cl.co_base = 32 * c; cl.w_row0 = 32 * c;
+        for (int t = 0; t < 16 && t < d->KH * d->KW; ++t) cl.w_tap_off[t] = g.w_tap_off[t];
+    }
+    return rq;
 }
 
 }  // namespace
@@ -669,15 +671,16 @@ __global__ __launch_bounds__(256) void relu_bits_kernel(const void* __restrict__
     bits[(i % nw) * npix + i / nw] = m;
 }
 static void launch_relu_bits(const hulc_conv_desc* d, const void* y, hipStream_t s) {
-    const int OH = (d->H - d->KH) / d->stride + 1, OW = (d->W - d->KW) / d->stride + 1;
-    const long npix = (long)d->N * OH * OW;
+    const long npix = (long)d->N * conv_OH(*d) * conv_OW(*d);
     const int nw = d->Cout / 32;
     relu_bits_kernel<<<(unsigned)((npix * nw + 255) / 256), 256, 0, s>>>(y, d->y_dtype, npix, nw, (unsigned*)d->relu_bits);
 }
+// behind a band launch that left the planes the caller asked for, reported in its path
+static void relu_bits_pass(const hulc_conv_desc* d, const void* y, hipStream_t s) { launch_relu_bits(d, y, s); hulc_conv_path_append(" +relu_bits_pass"); }
 
 extern "C" int hulc_conv2d_fwd(const hulc_conv_desc* d, const void* x, const void* w, const float* bias, void* y, void* stream) {
     hulc_conv_path_clear();
-    int rc = validate(d, "fwd"); if (rc) return rc;
+    int rc = validate(d); if (rc) return rc;
     if (!x || !w || !y) return hulc_fail(-1, "hulc_conv2d_fwd: null pointer");
     GatherP g; fill_gather(g, d);
     if (d->relu_bits && (d->Cout % 32 || !d->relu)) return hulc_fail(-4, "hulc_conv2d_fwd: relu_bits needs relu and Cout % 32 == 0");
@@ -692,44 +695,31 @@ extern "C" int hulc_conv2d_fwd(const hulc_conv_desc* d, const void* x, const voi
     g.X = x; g.Wt = w; g.bias = bias; g.Y = y; g.mask = nullptr; g.mask_dtype = HULC_F32; g.mask_scale = 1.f; g.add = nullptr; g.add_dtype = HULC_F32;
     g.y_dtype = d->y_dtype; g.relu = d->relu;
     g.y_sn = (long)g.OH * g.OW * d->Cout; g.y_sy = (long)g.OW * d->Cout; g.y_sx = d->Cout;
+    // the band kernels' epilogues write the planes of a bf16 output; for any other launch that leaves them (an fp32 output, or a launch whose
+    // plane preconditions failed and that is repeated without them) the second pass over y follows
+    unsigned* planes = (d->relu && d->y_dtype == HULC_BF16) ? (unsigned*)d->relu_bits : nullptr;
     if (d->compute == HULC_BF16 && !d->x_nchw && d->KH * d->KW <= 16 && d->Cout % 32 == 0 && d->Cout / 32 <= 4) {
-        const int nset = d->Cout / 32;
-        int cOH[4], cOW[4], cco[4]; long cyo[4], cw0[4], ctap[4 * 16];
-        for (int c = 0; c < nset; ++c) {
-            cOH[c] = g.OH; cOW[c] = g.OW; cyo[c] = 0; cco[c] = 32 * c; cw0[c] = 32 * c;
-            for (int t = 0; t < 16; ++t) ctap[c * 16 + t] = t < d->KH * d->KW ? g.w_tap_off[t] : 0;
-        }
-        // the band kernel's epilogue writes the planes of a bf16 output; for any other launch that leaves them (an fp32 output, or a launch whose
-        // plane preconditions failed and that is repeated without them) the second pass over y follows
-        unsigned* planes = (d->relu && d->y_dtype == HULC_BF16) ? (unsigned*)d->relu_bits : nullptr;
-        void* y16 = d->y_dtype != HULC_BF16 ? d->y_bf16 : nullptr;
-        rc = hulc_conv_band_dispatch(d->Cin, nset, d->KH, d->KW, d->stride, x, d->x_dtype, d->N, d->H, d->W, 0, 0, g.x_sn, g.x_sy, g.x_sx,
-                                     y, d->y_dtype, g.y_sn, g.y_sy, g.y_sx, w, d->w_dtype, g.ldw, bias, nullptr, HULC_F32, d->relu, nset,
-                                     cOH, cOW, cyo, cco, cw0, ctap, nullptr, planes, nullptr, d->Cout, y16, (hipStream_t)stream);
-        if (rc == 1 && planes) {                // (the planes' preconditions failed, not the geometry: the same launch without them)
-            planes = nullptr;
-            rc = hulc_conv_band_dispatch(d->Cin, nset, d->KH, d->KW, d->stride, x, d->x_dtype, d->N, d->H, d->W, 0, 0, g.x_sn, g.x_sy, g.x_sx,
-                                         y, d->y_dtype, g.y_sn, g.y_sy, g.y_sx, w, d->w_dtype, g.ldw, bias, nullptr, HULC_F32, d->relu, nset,
-                                         cOH, cOW, cyo, cco, cw0, ctap, nullptr, nullptr, nullptr, 0, y16, (hipStream_t)stream);
-        }
+        BandReq rq = forward_band_request(d, g, 0);
+        rq.p.bits_out = planes; rq.bits_channels = d->Cout;
+        rq.p.Y16 = d->y_dtype != HULC_BF16 ? d->y_bf16 : nullptr;
+        rc = hulc_conv_band_dispatch(rq, (hipStream_t)stream);
+        if (rc == 1 && planes) { planes = nullptr; rq.drop_planes(); rc = hulc_conv_band_dispatch(rq, (hipStream_t)stream); }   // (the planes' preconditions failed, not the geometry)
         if (rc < 0) return rc;
         if (rc == 0) {
-            if (d->relu_bits && !planes) { launch_relu_bits(d, y, (hipStream_t)stream); hulc_conv_path_append(" +relu_bits_pass"); }
+            if (d->relu_bits && !planes) relu_bits_pass(d, y, (hipStream_t)stream);
             return hulc_check_launch("hulc_conv2d_fwd(band)");
         }
     }
     if (d->y_dtype == HULC_F16)
         return hulc_fail(-6, "hulc_conv2d_fwd: the fp16 twin is stored by the direct-to-LDS band kernel only (bf16 compute, NHWC 23 x 23 x 64 -> 64, 3 x 3)");
     if (conv1_geom) {
-        unsigned* planes = (d->relu && d->y_dtype == HULC_BF16) ? (unsigned*)d->relu_bits : nullptr;
-        rc = hulc_conv1_band_dispatch((const float*)x, w, d->w_dtype, g.ldw, bias, y, d->y_dtype, d->relu, d->N, d->H, d->W, d->x_u8_nhwc, d->aug_pad,
-                                      d->aug_shift, d->frame_index, planes, d->w_lo, d->x2, d->n_split, d->x_slot, d->x2_slot, d->conv1_slots, (hipStream_t)stream);
+        rc = hulc_conv1_band_dispatch(*d, (const float*)x, w, g.ldw, bias, y, planes, (hipStream_t)stream);
         if (rc < 0) return rc;
         if (rc != 0 && d->x2) return hulc_fail(-6, "hulc_conv2d_fwd: a second frame tensor (x2) is taken by the conv1 band kernel only");
         if (rc != 0 && (d->x_slot || d->x2_slot)) return hulc_fail(-6, "hulc_conv2d_fwd: frame slots are taken by the conv1 band kernel only");
         if (rc != 0 && d->w_lo) return hulc_fail(-6, "hulc_conv2d_fwd: split operands (w_lo) are taken by the conv1 band kernel only");
         if (rc == 0) {
-            if (d->relu_bits && !planes) { launch_relu_bits(d, y, (hipStream_t)stream); hulc_conv_path_append(" +relu_bits_pass"); }
+            if (d->relu_bits && !planes) relu_bits_pass(d, y, (hipStream_t)stream);
             return hulc_check_launch("hulc_conv2d_fwd(conv1 band)");
         }
     }
@@ -762,7 +752,7 @@ extern "C" int hulc_conv2d_padded_fwd(const hulc_conv_desc* d, int pad, const vo
     g.x_dtype = d->x_dtype; g.w_dtype = d->w_dtype; g.y_dtype = d->y_dtype; g.relu = d->relu;
     g.Nimg = d->N; g.H = d->H; g.W = d->W; g.Cout = d->Cout; g.stride = d->stride; g.check_bounds = pad > 0;
     g.grid_kw = d->KW; g.grid_pad = pad; g.stride_x = d->stride;
-    g.OH = (d->H + 2 * pad - d->KH) / d->stride + 1; g.OW = (d->W + 2 * pad - d->KW) / d->stride + 1;
+    g.OH = conv_OH(*d, pad); g.OW = conv_OW(*d, pad);
     g.x_sn = (long)d->H * d->W * d->Cin; g.x_sy = (long)d->W * d->Cin; g.x_sx = d->Cin;
     g.y_sn = (long)g.OH * g.OW * d->Cout; g.y_sy = (long)g.OW * d->Cout; g.y_sx = d->Cout;
     g.ntaps = d->KH * d->KW; g.inner_log2 = log2_exact(d->Cin);
@@ -777,14 +767,9 @@ extern "C" int hulc_conv2d_padded_fwd(const hulc_conv_desc* d, int pad, const vo
     // 64 -> 64, 3 x 3, stride 1 (ResNet layer1): the LDS-band kernel stages every input row once instead of gathering it nine times
     if (d->compute == HULC_BF16 && d->Cin == 64 && d->Cout == 64 && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->x_dtype == HULC_BF16 &&
         d->y_dtype == HULC_BF16 && d->w_dtype == HULC_BF16) {
-        int cOH[4], cOW[4], cco[4]; long cyo[4], cw0[4], ctap[4 * 16];
-        for (int c = 0; c < 2; ++c) {
-            cOH[c] = g.OH; cOW[c] = g.OW; cyo[c] = 0; cco[c] = 32 * c; cw0[c] = 32 * c;
-            for (int t = 0; t < 16; ++t) ctap[c * 16 + t] = t < 9 ? g.w_tap_off[t] : 0;
-        }
-        const int rc = hulc_conv_band_dispatch(64, 2, 3, 3, 1, x, d->x_dtype, d->N, d->H, d->W, pad, pad, g.x_sn, g.x_sy, g.x_sx, y, d->y_dtype, g.y_sn,
-                                               g.y_sy, g.y_sx, w, d->w_dtype, g.ldw, bias, nullptr, HULC_BF16, d->relu, 2, cOH, cOW, cyo, cco, cw0, ctap,
-                                               add, nullptr, nullptr, 0, nullptr, (hipStream_t)stream);
+        BandReq rq = forward_band_request(d, g, pad);
+        rq.p.mask_dtype = HULC_BF16;                         // (no mask: the value this launch's kernel arguments have always carried)
+        const int rc = hulc_conv_band_dispatch(rq, (hipStream_t)stream);
         if (rc < 0) return rc;
         if (rc == 0) return hulc_check_launch("hulc_conv2d_padded_fwd(band)");
     }
@@ -830,34 +815,35 @@ extern "C" int hulc_conv2d_bwd_data(const hulc_conv_desc* d, const void* dy, con
     if (d->x_nchw) return hulc_fail(-7, "hulc_conv2d_bwd_data: only NHWC activations have a data gradient on this path");
     if (log2_exact(d->Cout) < 3) return hulc_fail(-4, "conv bwd_data: Cout must be a power of two >= 8");
     if (d->Cin != 32 && d->Cin != 64) return hulc_fail(-5, "conv bwd_data: Cin must be 32 or 64");
-    const int OH = (d->H - d->KH) / d->stride + 1, OW = (d->W - d->KW) / d->stride + 1, s = d->stride;
+    const int OH = conv_OH(*d), OW = conv_OW(*d), s = d->stride;
     const int xsz = d->x_dtype == HULC_F32 ? 4 : 2;
     // LDS-band kernel: all stride^2 parity classes x Cin/32 channel tiles in ONE launch sharing one staged dY band
     if (d->compute == HULC_BF16 && d->Cin % 32 == 0 && d->KH % s == 0 && d->KW % s == 0) {
         const int U = d->KH / s, V = d->KW / s, tiles = d->Cin / 32, nset = s * s * tiles;
         if (nset <= 4 && U * V <= 16) {
-            int cOH[4], cOW[4], cco[4]; long cyo[4], cw0[4], ctap[4 * 16];
+            BandReq rq = {};
+            rq.C = d->Cout; rq.NSET = nset; rq.TH = U; rq.TW = V; rq.S = 1;
+            BandP& p = rq.p;
+            p.X = dy; p.x_dtype = d->y_dtype; p.Y = dx; p.y_dtype = d->x_dtype; p.Wt = wt; p.w_dtype = d->w_dtype;
+            p.Nimg = d->N; p.H = OH; p.W = OW; p.pad_y = U - 1; p.pad_x = V - 1;                   // the staged tensor is dY
+            p.x_sn = (long)OH * OW * d->Cout; p.x_sy = (long)OW * d->Cout; p.x_sx = d->Cout;
+            p.y_sn = (long)d->H * d->W * d->Cin; p.y_sy = (long)s * d->W * d->Cin; p.y_sx = (long)s * d->Cin;   // a class' sub-grid of dX
+            p.ldw = (long)d->KH * d->KW * d->Cout;
+            p.mask = relu_src; p.mask_dtype = d->x_dtype;
+            p.bits_in = (const unsigned*)d->relu_bits; rq.bits_channels = d->Cin;
             int c = 0;
             for (int py = 0; py < s; ++py)
                 for (int px = 0; px < s; ++px)
                     for (int j = 0; j < tiles; ++j, ++c) {
-                        cOH[c] = (d->H - py + s - 1) / s; cOW[c] = (d->W - px + s - 1) / s;
-                        cyo[c] = ((long)py * d->W + px) * d->Cin; cco[c] = 32 * j; cw0[c] = 32 * j;
-                        for (int t = 0; t < 16; ++t) ctap[c * 16 + t] = 0;
+                        BandCls& cl = p.cls[c];
+                        cl.OH = (d->H - py + s - 1) / s; cl.OW = (d->W - px + s - 1) / s;
+                        cl.y_off = ((long)py * d->W + px) * d->Cin; cl.co_base = 32 * j; cl.w_row0 = 32 * j;
                         for (int ty = 0; ty < U; ++ty)
                             for (int tx = 0; tx < V; ++tx)
-                                ctap[c * 16 + ty * V + tx] = ((long)(py + s * (U - 1 - ty)) * d->KW + (px + s * (V - 1 - tx))) * d->Cout;
+                                cl.w_tap_off[ty * V + tx] = ((long)(py + s * (U - 1 - ty)) * d->KW + (px + s * (V - 1 - tx))) * d->Cout;
                     }
-            int brc = hulc_conv_band_dispatch(d->Cout, nset, U, V, 1, dy, d->y_dtype, d->N, OH, OW, U - 1, V - 1, (long)OH * OW * d->Cout,
-                                                    (long)OW * d->Cout, d->Cout, dx, d->x_dtype, (long)d->H * d->W * d->Cin,
-                                                    (long)s * d->W * d->Cin, (long)s * d->Cin, wt, d->w_dtype, (long)d->KH * d->KW * d->Cout,
-                                                    nullptr, relu_src, d->x_dtype, 0, nset, cOH, cOW, cyo, cco, cw0, ctap, nullptr, nullptr,
-                                                    (const unsigned*)d->relu_bits, d->Cin, nullptr, (hipStream_t)stream);
-            if (brc == 1 && d->relu_bits)       // the planes' preconditions failed: the same launch with the activation as the mask
-                brc = hulc_conv_band_dispatch(d->Cout, nset, U, V, 1, dy, d->y_dtype, d->N, OH, OW, U - 1, V - 1, (long)OH * OW * d->Cout,
-                                              (long)OW * d->Cout, d->Cout, dx, d->x_dtype, (long)d->H * d->W * d->Cin,
-                                              (long)s * d->W * d->Cin, (long)s * d->Cin, wt, d->w_dtype, (long)d->KH * d->KW * d->Cout,
-                                              nullptr, relu_src, d->x_dtype, 0, nset, cOH, cOW, cyo, cco, cw0, ctap, nullptr, nullptr, nullptr, 0, nullptr, (hipStream_t)stream);
+            int brc = hulc_conv_band_dispatch(rq, (hipStream_t)stream);
+            if (brc == 1 && d->relu_bits) { rq.drop_planes(); brc = hulc_conv_band_dispatch(rq, (hipStream_t)stream); }   // (the planes' preconditions failed: the activation is the mask)
             if (brc < 0) return brc;
             if (brc == 0) return hulc_check_launch("hulc_conv2d_bwd_data(band)");
         }
@@ -903,9 +889,8 @@ extern "C" int hulc_conv2d_bwd_data(const hulc_conv_desc* d, const void* dy, con
 
 // pixel split: ~1024 workgroups in total (4 per CU) with at least 256 pixels each
 static void wgrad_split(const hulc_conv_desc* d, long& P, long& ppb, long& K, long& Mtot) {
-    const int OH = (d->H - d->KH) / d->stride + 1, OW = (d->W - d->KW) / d->stride + 1;
     K = (long)d->Cin * d->KH * d->KW;
-    Mtot = (long)d->N * OH * OW;
+    Mtot = (long)d->N * conv_OH(*d) * conv_OW(*d);
     const long kslices = (K + 255) / 256;
     ppb = (Mtot * kslices + 1023) / 1024;
     if (ppb < 256) ppb = 256;
@@ -925,13 +910,10 @@ extern "C" long hulc_conv2d_bwd_weight_workspace(const hulc_conv_desc* d) {
 // hulc_conv2d_bwd_weight_workspace() bytes.
 extern "C" int hulc_conv2d_bwd_weight(const hulc_conv_desc* d, const void* x, const void* dy, float* dw, float* db, void* ws, void* stream) {
     hulc_conv_path_clear();
-    int rc = validate(d, "bwd_weight"); if (rc) return rc;
+    int rc = validate(d); if (rc) return rc;
     if (!x || !dy || !dw || !ws) return hulc_fail(-1, "hulc_conv2d_bwd_weight: null pointer");
     if (d->compute == HULC_BF16) {                           // LDS-band kernel (conv_wgrad_band.hip) for the geometries it covers
-        const long wsb = hulc_conv2d_bwd_weight_workspace(d);
-        const int brc = hulc_conv_wgrad_band_dispatch(d->x_nchw, d->Cin, d->Cout, d->KH, d->KW, d->stride, x, d->x_dtype, dy, d->y_dtype,
-                                                      d->N, d->H, d->W, dw, db, ws, wsb, d->dw_oihw, d->dw_accumulate, d->x_u8_nhwc, d->aug_pad,
-                                                      d->aug_shift, d->frame_index, d->x2, d->n_split, d->x_slot, d->x2_slot, d->conv1_slots, (hipStream_t)stream);
+        const int brc = hulc_conv_wgrad_band_dispatch(*d, x, dy, dw, db, ws, hulc_conv2d_bwd_weight_workspace(d), (hipStream_t)stream);
         if (brc < 0) return brc;
         if (brc == 0) return hulc_check_launch("hulc_conv2d_bwd_weight(band)");
     }

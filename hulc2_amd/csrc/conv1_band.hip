@@ -10,7 +10,7 @@
 // fragments, and a wave computes D[channel][pixel] for 32 consecutive output pixels per tile: the B fragment of k-step
 // (c, kh pair) is the 8 contiguous kw of the patch row — two aligned ds_read_b64, conflict-free across the 32 pixels.
 #include "hulc_common.h"
-#include "hulc_abi_internal.h"
+#include "conv_band.h"
 #include "u8_frames.h"
 #include <stdlib.h>
 
@@ -367,29 +367,23 @@ int launch_conv1(C1P& p, int slots, hipStream_t s) {
 
 }  // namespace
 
-// 0 = launched, 1 = geometry not covered (caller uses the gather kernel), < 0 = error
-int hulc_conv1_band_dispatch(const float* x, const void* w, int w_dtype, long ldw, const float* bias, void* y, int y_dtype, int relu,
-                             int N, int H, int W, int u8, int pad, const int* shift, const int* fidx, unsigned* relu_bits, const void* w_lo,
-                             const void* x2, int n_split, const void* x_slot, const void* x2_slot, int slots, hipStream_t s) {
-    if (w_dtype != HULC_BF16 || ((uintptr_t)w % 16) || ldw % 8) return u8 ? hulc_fail(-6, "conv1 band: bf16 weights, 16-byte aligned rows") : 1;
+int hulc_conv1_band_dispatch(const hulc_conv_desc& d, const float* x, const void* w, long ldw, const float* bias, void* y, unsigned* relu_bits,
+                             hipStream_t s) {
+    const int u8 = d.x_u8_nhwc, H = d.H, W = d.W;
+    if (d.w_dtype != HULC_BF16 || ((uintptr_t)w % 16) || ldw % 8) return u8 ? hulc_fail(-6, "conv1 band: bf16 weights, 16-byte aligned rows") : 1;
     if (W % 4 || ((uintptr_t)x % (u8 ? 4 : 16)) || (bias && ((uintptr_t)bias % 16)) || (H - 8) % 4 || (W - 8) % 4) return 1;
     C1P p;
-    if (relu_bits && (y_dtype != HULC_BF16 || !relu)) return 1;       // (planes describe the stored bf16 ReLU output)
-    if (w_lo && (u8 || (uintptr_t)w_lo % 16)) return hulc_fail(-6, "conv1 band: split operands need fp32 frames and 16-byte aligned remainders");
-    p.u8 = u8; p.pad = pad; p.shift = shift; p.fidx = fidx; p.bits = relu_bits; p.Wlo = w_lo;
-    p.X = x; p.Wt = w; p.bias = bias; p.Y = y; p.w_dtype = w_dtype; p.y_dtype = y_dtype; p.relu = relu;
-    p.X2 = x; p.nsplit = N;
-    p.xs = (const void* const*)x_slot; p.xs2 = (const void* const*)x2_slot;
-    if ((x_slot || x2_slot) && (u8 || !x_slot || (x2_slot && !x2) || ((uintptr_t)x_slot | (uintptr_t)x2_slot) % 8))
+    if (relu_bits && (d.y_dtype != HULC_BF16 || !d.relu)) return 1;       // (planes describe the stored bf16 ReLU output)
+    if (d.w_lo && (u8 || (uintptr_t)d.w_lo % 16)) return hulc_fail(-6, "conv1 band: split operands need fp32 frames and 16-byte aligned remainders");
+    p.u8 = u8; p.pad = d.aug_pad; p.shift = d.aug_shift; p.fidx = d.frame_index; p.bits = relu_bits; p.Wlo = d.w_lo;
+    p.X = x; p.Wt = w; p.bias = bias; p.Y = y; p.w_dtype = d.w_dtype; p.y_dtype = d.y_dtype; p.relu = d.relu;
+    const int bad = conv1_frames(d, x, p);
+    if (bad & CONV1_BAD_SLOTS)
         return hulc_fail(-6, "conv1 band: frame slots are for fp32 frames (x_slot with every launch, x2_slot next to x2), 8-byte aligned");
-    if (x2) {
-        if (n_split < 0 || n_split > N || ((uintptr_t)x2 % (u8 ? 4 : 16)) || (u8 && fidx))
-            return hulc_fail(-6, "conv1 band: x2 needs 0 <= n_split <= N, 16-byte (uint8 frames: 4-byte) alignment and no frame_index");
-        p.X2 = u8 ? (const float*)((const unsigned char*)x2 - (long)n_split * 3 * H * W) : (const float*)x2 - (long)n_split * 3 * H * W;
-        p.nsplit = n_split;
-    }
-    p.Nimg = N; p.H = H; p.W = W; p.OH = (H - 8) / 4 + 1; p.OW = (W - 8) / 4 + 1; p.R = 1; p.ldw = ldw;
-    const int rc = launch_conv1<3, 2>(p, slots, s);
+    if (bad & CONV1_BAD_X2)
+        return hulc_fail(-6, "conv1 band: x2 needs 0 <= n_split <= N, 16-byte (uint8 frames: 4-byte) alignment and no frame_index");
+    p.Nimg = d.N; p.H = H; p.W = W; p.OH = (H - 8) / 4 + 1; p.OW = (W - 8) / 4 + 1; p.R = 1; p.ldw = ldw;
+    const int rc = launch_conv1<3, 2>(p, d.conv1_slots, s);
     if (rc == -1) return 1;
     if (rc < 0) return hulc_fail(-8, "conv1 band: could not raise the dynamic LDS limit");
     return 0;

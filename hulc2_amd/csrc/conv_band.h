@@ -1,6 +1,8 @@
-// conv_band.h — launch parameters shared by the LDS-band convolution kernels (conv_band.hip, conv_band_planes.hip).
+// conv_band.h — launch parameters shared by the LDS-band convolution kernels (conv_band.hip, conv_band_planes.hip), and what conv.hip
+// asks the three band dispatchers for (conv_band.hip, conv1_band.hip, conv_wgrad_band.hip): declared here and nowhere else.
 #pragma once
 #include "hulc_common.h"
+#include "hulc_abi_internal.h"
 
 namespace hulc_band {
 
@@ -31,6 +33,14 @@ struct BandP {
     int bshift; long bplane;        // log2(channels of the tensor the planes describe), pixels of that tensor: planes are [channels / 32][pixels]
     BandCls cls[BAND_MAXCLS];
 };
+// One band launch as conv.hip requests it.  The caller fills p's operands, dtypes, Nimg / H / W, pads, strides, ldw, relu, planes and one cls
+// entry per weight set (taps past TH * TW need not be set); the dispatcher derives R, F, OHmax, OWmax, bshift and bplane.
+struct BandReq {
+    int C, NSET, TH, TW, S;         // kernel instance: input channels, weight sets (= entries of p.cls), taps, input stride
+    int bits_channels;              // channels of the tensor p.bits_out / p.bits_in describe
+    BandP p;
+    void drop_planes() { p.bits_out = nullptr; p.bits_in = nullptr; bits_channels = 0; }
+};
 
 // bf16 operands only (input band, weights, ReLU mask): a run-time dtype branch around a load makes hipcc wait for it at the join, which
 // turned the 32+ weight-fragment loads of a launch and the 10+ chunk loads of every prefetch into as many serial memory round trips.
@@ -49,3 +59,30 @@ HULC_DEVICE uint4 band_load_x(const void* X, long off) {
 int launch_band_planes(BandP& p, int NSET, int TH, int TW, hipStream_t s);
 
 }  // namespace hulc_band
+
+// The band dispatchers: 0 = launched, 1 = geometry not covered (the caller uses its gather kernel), < 0 = error (hulc_fail).
+int hulc_conv_band_dispatch(const hulc_band::BandReq& rq, hipStream_t s);
+// conv1 forward (NCHW fp32 or uint8 NHWC frames, 3 -> 32 channels, 8x8 stride 4); relu_bits: the planes this launch is to write, or null
+int hulc_conv1_band_dispatch(const hulc_conv_desc& d, const float* x, const void* w, long ldw, const float* bias, void* y, unsigned* relu_bits, hipStream_t s);
+// weight gradient; dw is [Cout][K] fp32 in the forward k order
+int hulc_conv_wgrad_band_dispatch(const hulc_conv_desc& d, const void* x, const void* dy, float* dw, float* db, void* ws, long ws_bytes, hipStream_t s);
+
+static inline int conv_OH(const hulc_conv_desc& d, int pad = 0) { return (d.H + 2 * pad - d.KH) / d.stride + 1; }
+static inline int conv_OW(const hulc_conv_desc& d, int pad = 0) { return (d.W + 2 * pad - d.KW) / d.stride + 1; }
+
+// conv1's frame sources, written into the kernel parameters P = C1P / W1P: frames n >= nsplit come from X2, pre-offset by -nsplit frames (X2 == x
+// and nsplit == N without x2); xs / xs2: the optional device slots.  Returns which fields are unacceptable: the launchers word and order their refusals.
+enum { CONV1_BAD_SLOTS = 1, CONV1_BAD_X2 = 2 };
+template <typename P>
+int conv1_frames(const hulc_conv_desc& d, const void* x, P& p) {
+    const int u8 = d.x_u8_nhwc;
+    int bad = 0;
+    p.X2 = x; p.nsplit = d.N; p.xs = (const void* const*)d.x_slot; p.xs2 = (const void* const*)d.x2_slot;
+    if ((d.x_slot || d.x2_slot) && (u8 || !d.x_slot || (d.x2_slot && !d.x2) || ((uintptr_t)d.x_slot | (uintptr_t)d.x2_slot) % 8)) bad |= CONV1_BAD_SLOTS;
+    if (d.x2) {
+        if (d.n_split < 0 || d.n_split > d.N || ((uintptr_t)d.x2 % (u8 ? 4 : 16)) || (u8 && d.frame_index)) return bad | CONV1_BAD_X2;
+        p.X2 = (const char*)d.x2 - (long)d.n_split * 3 * d.H * d.W * (u8 ? 1 : 4);
+        p.nsplit = d.n_split;
+    }
+    return bad;
+}

@@ -15,7 +15,6 @@
 //   * MFMA roles are swapped (A = weights, B = pixels) so D[channel][pixel] leaves every lane with ONE pixel and groups of
 //     four consecutive channels: the epilogue is 8-byte (bf16) / 16-byte (fp32) stores, no LDS transpose, no divisions.
 #include "hulc_common.h"
-#include "hulc_abi_internal.h"
 #include "conv_band.h"
 #include <stdlib.h>
 
@@ -590,43 +589,33 @@ inline bool mask_only(const void* mask, const unsigned* bits_in) { return mask !
 
 }  // namespace
 
-// One launch covering `ncls` weight sets (output-channel tiles of a forward conv, or parity classes of a data gradient).
+// One launch covering rq.NSET weight sets (output-channel tiles of a forward conv, or parity classes of a data gradient).
 // returns 0 when the band kernel took the launch, 1 when the geometry is not covered (caller falls back to the gather
 // kernel), negative on error.  bf16 compute only; NHWC input with C in {32, 64}; 32 output channels per set.
-int hulc_conv_band_dispatch(int C, int NSET, int TH, int TW, int S, const void* x, int x_dtype, int N, int H, int W, int pad_y, int pad_x,
-                            long x_sn, long x_sy, long x_sx, void* y, int y_dtype, long y_sn, long y_sy, long y_sx, const void* wt,
-                            int w_dtype, long ldw, const float* bias, const void* mask, int mask_dtype, int relu, int ncls,
-                            const int* cls_OH, const int* cls_OW, const long* cls_yoff, const int* cls_cobase, const long* cls_wrow0,
-                            const long* cls_wtap /* [ncls][16] */, const void* add, unsigned* bits_out, const unsigned* bits_in, int bits_channels,
-                            void* y16, hipStream_t s) {
-    if (ncls != NSET || ncls > BAND_MAXCLS || TH * TW > 16) return 1;
-    if (y16 && ((y_dtype != HULC_F32 && y_dtype != HULC_F16) || mask || add || bits_out || bits_in)) return 1;      // (the copy rides on the plain forward only)
-    if (y_dtype == HULC_F16 && !y16) return 1;
-    BandP p;
-    p.X = x; p.Y = y; p.Wt = wt; p.bias = bias; p.mask = mask; p.add = add; p.Y16 = y16;
-    p.bits_out = bits_out; p.bits_in = bits_in; p.bshift = 0; p.bplane = 0;
-    if (bits_out || bits_in) {
+int hulc_conv_band_dispatch(const BandReq& rq, hipStream_t s) {
+    const int C = rq.C, NSET = rq.NSET, TH = rq.TH, TW = rq.TW, S = rq.S;
+    if (NSET > BAND_MAXCLS || TH * TW > 16) return 1;
+    BandP p = rq.p;
+    const int y_dtype = p.y_dtype;
+    if (p.Y16 && ((y_dtype != HULC_F32 && y_dtype != HULC_F16) || p.mask || p.add || p.bits_out || p.bits_in)) return 1;      // (the copy rides on the plain forward only)
+    if (y_dtype == HULC_F16 && !p.Y16) return 1;
+    p.bshift = 0; p.bplane = 0;
+    if (p.bits_out || p.bits_in) {
         // planes exist for bf16 tensors of 32 / 64 / 128 channels whose pixels are whole multiples of the channel count apart
-        if (y_dtype != HULC_BF16 || (bits_channels != 32 && bits_channels != 64 && bits_channels != 128) || y_sx % bits_channels || y_sy % bits_channels ||
-            y_sn % bits_channels) return 1;
-        for (int c = 0; c < ncls; ++c) if (cls_yoff[c] % bits_channels) return 1;
-        while ((1 << p.bshift) < bits_channels) ++p.bshift;
-        p.bplane = (long)N * y_sn / bits_channels;           // pixels of the (dense) tensor the planes describe
+        const int bc = rq.bits_channels;
+        if (y_dtype != HULC_BF16 || (bc != 32 && bc != 64 && bc != 128) || p.y_sx % bc || p.y_sy % bc || p.y_sn % bc) return 1;
+        for (int c = 0; c < NSET; ++c) if (p.cls[c].y_off % bc) return 1;
+        while ((1 << p.bshift) < bc) ++p.bshift;
+        p.bplane = (long)p.Nimg * p.y_sn / bc;               // pixels of the (dense) tensor the planes describe
     }
-    if (add && y_dtype != HULC_BF16) return 1;
-    if (bits_out && !relu) return 1;                        // (the planes describe a rectified map: positive <=> non-zero)
-    if (w_dtype != HULC_BF16 || (mask && mask_dtype != HULC_BF16)) return 1;   // the gather kernel serves other storage types
-    p.x_dtype = x_dtype; p.y_dtype = y_dtype; p.w_dtype = w_dtype; p.mask_dtype = mask_dtype;
-    p.Nimg = N; p.H = H; p.W = W; p.pad_y = pad_y; p.pad_x = pad_x; p.R = 1; p.F = 1;
-    p.x_sn = x_sn; p.x_sy = x_sy; p.x_sx = x_sx; p.y_sn = y_sn; p.y_sy = y_sy; p.y_sx = y_sx;
-    p.ldw = ldw; p.relu = relu;
-    p.OHmax = 0; p.OWmax = 0;
-    for (int c = 0; c < ncls; ++c) {
-        p.cls[c].OH = cls_OH[c]; p.cls[c].OW = cls_OW[c]; p.cls[c].y_off = cls_yoff[c]; p.cls[c].co_base = cls_cobase[c];
-        p.cls[c].w_row0 = cls_wrow0[c];
-        for (int t = 0; t < 16; ++t) p.cls[c].w_tap_off[t] = t < TH * TW ? cls_wtap[c * 16 + t] : 0;
-        if (cls_OH[c] > p.OHmax) p.OHmax = cls_OH[c];
-        if (cls_OW[c] > p.OWmax) p.OWmax = cls_OW[c];
+    if (p.add && y_dtype != HULC_BF16) return 1;
+    if (p.bits_out && !p.relu) return 1;                    // (the planes describe a rectified map: positive <=> non-zero)
+    if (p.w_dtype != HULC_BF16 || (p.mask && p.mask_dtype != HULC_BF16)) return 1;   // the gather kernel serves other storage types
+    p.R = 1; p.F = 1; p.OHmax = 0; p.OWmax = 0;
+    for (int c = 0; c < NSET; ++c) {
+        for (int t = TH * TW; t < 16; ++t) p.cls[c].w_tap_off[t] = 0;      // (whatever the caller left behind its taps does not reach the kernel arguments)
+        if (p.cls[c].OH > p.OHmax) p.OHmax = p.cls[c].OH;
+        if (p.cls[c].OW > p.OWmax) p.OWmax = p.cls[c].OW;
     }
     int rc = 1;
     if (y_dtype == HULC_F16 && !(C == 64 && S == 1 && NSET == 2 && TH == 3 && TW == 3)) return 1;
@@ -639,13 +628,13 @@ int hulc_conv_band_dispatch(int C, int NSET, int TH, int TW, int S, const void* 
         rc = -1;
         if (NSET == 2 && TH == 3 && TW == 3) rc = launch_band_planes(p, NSET, TH, TW, s);
         if (rc == -1 && y_dtype == HULC_F16) return 1;       // (the fp16 twin is stored by the direct-to-LDS kernel only)
-        const bool contiguous = x_sx == 64 && x_sy == (long)W * 64 && x_sn == (long)H * W * 64 && ((uintptr_t)x % 16) == 0;
-        if (rc == -1 && !mask_only(mask, bits_in) && !add && !bits_out && x_dtype == HULC_BF16 && y_dtype == HULC_BF16 && contiguous &&
+        const bool contiguous = p.x_sx == 64 && p.x_sy == (long)p.W * 64 && p.x_sn == (long)p.H * p.W * 64 && ((uintptr_t)p.X % 16) == 0;
+        if (rc == -1 && !mask_only(p.mask, p.bits_in) && !p.add && !p.bits_out && p.x_dtype == HULC_BF16 && y_dtype == HULC_BF16 && contiguous &&
             (long)p.OHmax * p.OWmax >= 256) {
-            const bool padded = pad_y != 0 || pad_x != 0;
-            if (NSET == 2 && !padded && !bits_in) rc = launch_band_glds<2, 3, 3, 0, false>(p, s);
-            else if (NSET == 2 && padded && bits_in) rc = launch_band_glds<2, 3, 3, 2, true>(p, s);
-            else if (NSET == 4 && padded && bits_in) rc = launch_band_glds<4, 2, 2, 2, true>(p, s);
+            const bool padded = p.pad_y != 0 || p.pad_x != 0;
+            if (NSET == 2 && !padded && !p.bits_in) rc = launch_band_glds<2, 3, 3, 0, false>(p, s);
+            else if (NSET == 2 && padded && p.bits_in) rc = launch_band_glds<2, 3, 3, 2, true>(p, s);
+            else if (NSET == 4 && padded && p.bits_in) rc = launch_band_glds<4, 2, 2, 2, true>(p, s);
         }
         if (rc == -1) rc = NSET == 2 ? launch_band<64, 2, 3, 3, 1, 10, 2>(p, s) : launch_band<64, 4, 2, 2, 1, 12, 2>(p, s);
     }

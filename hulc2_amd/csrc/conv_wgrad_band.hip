@@ -17,11 +17,14 @@
 //     k tiles x all channel tiles; one slab per workgroup is written at the end and summed by a fixed-order pass;
 //   * the next unit's bands are prefetched into registers during the MFMA loop (single LDS buffer).
 #include "hulc_common.h"
-#include "hulc_abi_internal.h"
+#include "conv_band.h"
 #include "u8_frames.h"
 #include <stdlib.h>
 
 namespace {
+
+// where a weight-gradient launch leaves its results: dW [Cout][K] / db [Cout] (fp32; stored, or added when `accumulate`), the slab workspace
+struct WgradOut { float* dw; float* db; void* ws; long ws_bytes; int dw_oihw, accumulate; };
 
 struct WBandP {
     const void* X; const void* dY;
@@ -822,7 +825,7 @@ __global__ __launch_bounds__(512, 4) void conv1_wgrad_kernel(W1P p, unsigned lon
     }
 }
 
-int launch_conv1_wgrad(W1P& p, float* dw, float* db, void* ws, long ws_bytes, int accumulate, int slots, hipStream_t s) {
+int launch_conv1_wgrad(W1P& p, const WgradOut& o, int slots, hipStream_t s) {
     constexpr int XCH = 3, YCH = 2, K = 192;
     if (p.W % 4) return -1;
     p.OWP = (p.OW + 7) / 8 * 8;
@@ -846,9 +849,9 @@ int launch_conv1_wgrad(W1P& p, float* dw, float* db, void* ws, long ws_bytes, in
     if (slots <= 0 || slots > 512) slots = 512;
     const int per = (p.Nimg + slots - 1) / slots;            // frames per workgroup
     const int grid = (p.Nimg + per - 1) / per;
-    if ((long)grid * 32 * (K + 1) * 4 > ws_bytes) return -1;
-    p.partial_w = (float*)ws;
-    p.partial_b = db ? p.partial_w + (long)grid * 32 * K : nullptr;
+    if ((long)grid * 32 * (K + 1) * 4 > o.ws_bytes) return -1;
+    p.partial_w = (float*)o.ws;
+    p.partial_b = o.db ? p.partial_w + (long)grid * 32 * K : nullptr;
     static bool attr_set = false;
     if (!attr_set) {
         if (hipFuncSetAttribute((const void*)conv1_wgrad_kernel<XCH, YCH, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess ||
@@ -871,13 +874,13 @@ int launch_conv1_wgrad(W1P& p, float* dw, float* db, void* ws, long ws_bytes, in
     else conv1_wgrad_kernel<XCH, YCH, false><<<grid, 512, (size_t)lds_of(R), s>>>(p);
     const long Rw = 32L * K;
     const int nbw = (int)((Rw + 63) / 64);
-    wband_reduce_kernel<<<nbw + (db ? 1 : 0), 1024, 0, s>>>(p.partial_w, dw, grid, Rw, accumulate, 0, 64, nbw, p.partial_b, db, 32);
+    wband_reduce_kernel<<<nbw + (o.db ? 1 : 0), 1024, 0, s>>>(p.partial_w, o.dw, grid, Rw, o.accumulate, 0, 64, nbw, p.partial_b, o.db, 32);
     hulc_conv_path_set("conv1_wgrad u8=%d R=%d grid=%d", p.u8 ? 1 : 0, R, grid);
     return 0;
 }
 
 template <int C, int CT, int TH, int TW, int S, bool NCHW, int XCH, int YCH, int BPC, bool PURE16 = false>
-int launch_wband(WBandP& p, float* dw, float* db, void* ws, long ws_bytes, int dw_oihw, int accumulate, hipStream_t s) {
+int launch_wband(WBandP& p, const WgradOut& o, hipStream_t s) {
     constexpr int COUT = CT * 32, K = TH * TW * C;
     constexpr int PS = NCHW ? 2 : C * 2 + 16;
     const int Wb = p.W, Wp = Wb;
@@ -913,9 +916,9 @@ int launch_wband(WBandP& p, float* dw, float* db, void* ws, long ws_bytes, int d
     const int slots = 256 * BPC;                             // resident workgroups
     const int per = (nunits + slots - 1) / slots;            // balanced persistent grid: every workgroup gets `per` (or per - 1) units
     const int grid = (nunits + per - 1) / per;
-    if ((long)grid * COUT * (K + 1) * 4 > ws_bytes) return -1;
-    p.partial_w = (float*)ws;
-    p.partial_b = db ? p.partial_w + (long)grid * COUT * K : nullptr;
+    if ((long)grid * COUT * (K + 1) * 4 > o.ws_bytes) return -1;
+    p.partial_w = (float*)o.ws;
+    p.partial_b = o.db ? p.partial_w + (long)grid * COUT * K : nullptr;
     auto kern = conv_wgrad_band_kernel<C, CT, TH, TW, S, NCHW, XCH, YCH, BPC, PURE16>;
     static bool attr_set = false;
     if (!attr_set) {
@@ -937,7 +940,7 @@ int launch_wband(WBandP& p, float* dw, float* db, void* ws, long ws_bytes, int d
     kern<<<grid, 512, (size_t)lds_of(R, F), s>>>(p, nullptr);
     const long Rw = (long)COUT * K;
     const int nbw = (int)((Rw + 63) / 64);
-    wband_reduce_kernel<<<nbw + (db ? 1 : 0), 1024, 0, s>>>(p.partial_w, dw, grid, Rw, accumulate, (dw_oihw && !NCHW) ? C : 0, TH * TW, nbw, p.partial_b, db,
+    wband_reduce_kernel<<<nbw + (o.db ? 1 : 0), 1024, 0, s>>>(p.partial_w, o.dw, grid, Rw, o.accumulate, (o.dw_oihw && !NCHW) ? C : 0, TH * TW, nbw, p.partial_b, o.db,
                                                           COUT);
     hulc_conv_path_set("wband<%d,%d,%d,%d,%d> pure16=%d R=%d F=%d units=%d grid=%d", C, CT, TH, TW, S, (int)PURE16, R, F, nunits, grid);
     return 0;
@@ -945,48 +948,42 @@ int launch_wband(WBandP& p, float* dw, float* db, void* ws, long ws_bytes, int d
 
 }  // namespace
 
-// 0 = launched, 1 = geometry not covered (caller uses the gather kernel), < 0 = error.  dw is [Cout][K] fp32 in the forward k order.
-int hulc_conv_wgrad_band_dispatch(int nchw, int Cin, int Cout, int KH, int KW, int S, const void* x, int x_dtype, const void* dy, int dy_dtype,
-                                  int N, int H, int W, float* dw, float* db, void* ws, long ws_bytes, int dw_oihw, int accumulate, int u8, int pad,
-                                  const int* shift, const int* fidx, const void* x2, int n_split, const void* x_slot, const void* x2_slot, int slots, hipStream_t s) {
+int hulc_conv_wgrad_band_dispatch(const hulc_conv_desc& d, const void* x, const void* dy, float* dw, float* db, void* ws, long ws_bytes, hipStream_t s) {
+    const int nchw = d.x_nchw, Cin = d.Cin, Cout = d.Cout, KH = d.KH, KW = d.KW, S = d.stride, x_dtype = d.x_dtype, dy_dtype = d.y_dtype;
+    const int N = d.N, H = d.H, W = d.W, u8 = d.x_u8_nhwc;
+    const WgradOut o = {dw, db, ws, ws_bytes, d.dw_oihw, d.dw_accumulate};
     WBandP p;
-    p.u8 = u8; p.pad = pad; p.shift = shift; p.fidx = fidx;
+    p.u8 = u8; p.pad = d.aug_pad; p.shift = d.aug_shift; p.fidx = d.frame_index;
     p.X = x; p.dY = dy; p.x_dtype = x_dtype; p.dy_dtype = dy_dtype;
-    p.Nimg = N; p.H = H; p.W = W; p.OH = (H - KH) / S + 1; p.OW = (W - KW) / S + 1; p.R = 1; p.F = 1;
+    p.Nimg = N; p.H = H; p.W = W; p.OH = conv_OH(d); p.OW = conv_OW(d); p.R = 1; p.F = 1;
     if (nchw) { p.x_sn = (long)Cin * H * W; p.x_sc = (long)H * W; p.x_sy = W; p.x_sx = 1; }
     else { p.x_sn = (long)H * W * Cin; p.x_sy = (long)W * Cin; p.x_sx = Cin; p.x_sc = 1; }
     p.dy_sn = (long)p.OH * p.OW * Cout; p.dy_sy = (long)p.OW * Cout; p.dy_sx = Cout;
     int rc = 1;
     const bool pure16 = x_dtype == HULC_BF16 && dy_dtype == HULC_BF16;
+    const bool slotted = d.x_slot || d.x2_slot, conv1 = nchw && Cin == 3 && Cout == 32 && KH == 8 && KW == 8 && S == 4;
     // (the NHWC instances know neither field: ignoring x2 would read N frames from a tensor that holds n_split of them)
-    if ((x2 || x_slot || x2_slot) && !(nchw && Cin == 3 && Cout == 32 && KH == 8 && KW == 8 && S == 4))
+    if ((d.x2 || slotted) && !conv1)
         return hulc_fail(-6, "conv weight gradient: x2 / frame slots are for conv1 only");
     if (!nchw && Cin == 64 && Cout == 64 && KH == 3 && KW == 3 && S == 1)
-        rc = pure16 ? launch_wband<64, 2, 3, 3, 1, false, 5, 4, 1, true>(p, dw, db, ws, ws_bytes, dw_oihw, accumulate, s)
-                    : launch_wband<64, 2, 3, 3, 1, false, 5, 4, 1>(p, dw, db, ws, ws_bytes, dw_oihw, accumulate, s);
+        rc = pure16 ? launch_wband<64, 2, 3, 3, 1, false, 5, 4, 1, true>(p, o, s) : launch_wband<64, 2, 3, 3, 1, false, 5, 4, 1>(p, o, s);
     else if (!nchw && Cin == 32 && Cout == 64 && KH == 4 && KW == 4 && S == 2)
-        rc = pure16 ? launch_wband<32, 2, 4, 4, 2, false, 10, 5, 1, true>(p, dw, db, ws, ws_bytes, dw_oihw, accumulate, s)
-                    : launch_wband<32, 2, 4, 4, 2, false, 10, 5, 1>(p, dw, db, ws, ws_bytes, dw_oihw, accumulate, s);
-    else if (nchw && Cin == 3 && Cout == 32 && KH == 8 && KW == 8 && S == 4 && (x_dtype == HULC_F32 || (u8 && W % 4 == 0 && (uintptr_t)x % 4 == 0))) {
-        if (x2 && (dy_dtype != HULC_BF16 || n_split < 0 || n_split > N || ((uintptr_t)x2 % (u8 ? 4 : 16)) || (u8 && fidx)))
+        rc = pure16 ? launch_wband<32, 2, 4, 4, 2, false, 10, 5, 1, true>(p, o, s) : launch_wband<32, 2, 4, 4, 2, false, 10, 5, 1>(p, o, s);
+    else if (conv1 && (x_dtype == HULC_F32 || (u8 && W % 4 == 0 && (uintptr_t)x % 4 == 0))) {
+        W1P q;
+        const int bad = conv1_frames(d, x, q);
+        if (d.x2 && (dy_dtype != HULC_BF16 || (bad & CONV1_BAD_X2)))
             return hulc_fail(-6, "conv1 weight gradient: x2 needs a bf16 gradient map, 0 <= n_split <= N, 16-byte (uint8 frames: 4-byte) alignment, no frame_index");
-        if ((x_slot || x2_slot) && dy_dtype != HULC_BF16)
+        if (slotted && dy_dtype != HULC_BF16)
             return hulc_fail(-6, "conv1 weight gradient: frame slots need the phase-plane kernel (bf16 gradient map)");
-        if (dy_dtype != HULC_BF16) rc = launch_wband<3, 1, 8, 8, 4, true, 6, 4, 2>(p, dw, db, ws, ws_bytes, dw_oihw, accumulate, s);
+        if (dy_dtype != HULC_BF16) rc = launch_wband<3, 1, 8, 8, 4, true, 6, 4, 2>(p, o, s);
         else {
-            W1P q;
+            if (bad & CONV1_BAD_SLOTS)
+                return hulc_fail(-6, "conv1 weight gradient: frame slots are for fp32 frames (x_slot with every launch, x2_slot next to x2), 8-byte aligned");
             q.X = x; q.dY = dy; q.dy_dtype = dy_dtype; q.Nimg = N; q.H = H; q.W = W; q.OH = p.OH; q.OW = p.OW;
             q.dy_sn = p.dy_sn; q.dy_sy = p.dy_sy; q.dy_sx = p.dy_sx;
-            q.u8 = u8; q.pad = pad; q.shift = shift; q.fidx = fidx;
-            q.X2 = x; q.nsplit = N;
-            q.xs = (const void* const*)x_slot; q.xs2 = (const void* const*)x2_slot;
-            if ((x_slot || x2_slot) && (u8 || !x_slot || (x2_slot && !x2) || ((uintptr_t)x_slot | (uintptr_t)x2_slot) % 8))
-                return hulc_fail(-6, "conv1 weight gradient: frame slots are for fp32 frames (x_slot with every launch, x2_slot next to x2), 8-byte aligned");
-            if (x2) {
-                q.X2 = u8 ? (const float*)((const unsigned char*)x2 - (long)n_split * 3 * H * W) : (const float*)x2 - (long)n_split * 3 * H * W;
-                q.nsplit = n_split;
-            }
-            rc = launch_conv1_wgrad(q, dw, db, ws, ws_bytes, accumulate, slots, s);
+            q.u8 = u8; q.pad = p.pad; q.shift = p.shift; q.fidx = p.fidx;
+            rc = launch_conv1_wgrad(q, o, d.conv1_slots, s);
         }
     }
     else return 1;

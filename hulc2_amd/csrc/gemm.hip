@@ -753,9 +753,6 @@ void launch_ct(const GemmP& p, int ak, int bk, float* ws, long ws_bytes, hipStre
 
 }  // namespace
 
-int hulc_gemm_tn128_try(const hulc_gemm_desc* d, hipStream_t s);   // gemm_tn128.hip
-int hulc_gemm_nt128_try(const hulc_gemm_desc* d, hipStream_t s);   // gemm_nt128.hip
-
 extern "C" int hulc_gemm(const hulc_gemm_desc* d, void* stream) {
     if (!d || !d->A || !d->B || !d->C) return hulc_fail(-1, "hulc_gemm: null operand");
     if (d->M <= 0 || d->N <= 0 || d->K <= 0) return hulc_fail(-2, "hulc_gemm: non-positive dimension");

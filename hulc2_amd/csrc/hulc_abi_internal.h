@@ -16,3 +16,7 @@ void hulc_conv_path_append(const char* suffix);
 int hulc_wgrad_taps_takes(const hulc_wgrad_item* d);
 long hulc_wgrad_taps_workspace(const hulc_wgrad_item* const* items, int n);       // slab bytes
 int hulc_wgrad_taps_launch(const hulc_wgrad_item* const* items, int n, void* slabs, hipStream_t s);
+
+// gemm_tn128.hip / gemm_nt128.hip, tried first by hulc_gemm (gemm.hip): 1 = the shape was taken, 0 = the generic kernel must run, < 0 = error
+int hulc_gemm_tn128_try(const hulc_gemm_desc* d, hipStream_t s);
+int hulc_gemm_nt128_try(const hulc_gemm_desc* d, hipStream_t s);

@@ -680,3 +680,38 @@ def test_refusals(dev):
         d = kn._conv_desc(2, 20, 20, Cin, 64, 4, 4, 2, nchw, kn.BF16, kn.BF16, kn.BF16, False, kn.BF16)
         refused(lambda: kn._call("hulc_conv2d_bwd_data", ctypes.byref(d), t(BF, 2, 9, 9, 64), t(BF, Cin, 4, 4, 64), dx.t, None), msg, dx)
         no_path()
+    # conv1's frame sources (x2 / n_split / x_slot / x2_slot), which both conv1 band launchers judge, each with its own message — and its own
+    # order where two apply: the forward names the slots first, the weight gradient x2.  The smallest frames the band kernels take; x holds all
+    # N frames and the slot x's address, so no field points anywhere a launch could not read.  (the Python wrappers never build these.)
+    N, H, W = 2, 24, 24
+    x, xu8 = t(F32, N, 3, H, W), torch.zeros(N, H, W, 3, dtype=torch.uint8, device=dev)
+    slot = torch.tensor([x.data_ptr()], dtype=torch.int64, device=dev)
+    SLOTS = "frame slots are for fp32 frames (x_slot with every launch, x2_slot next to x2), 8-byte aligned"
+
+    def conv1_desc(ydt, u8=False, **fields):
+        d = kn._conv_desc(N, H, W, 3, 32, 8, 8, 4, True, kn.F32, ydt, kn.BF16, True, kn.BF16)
+        d.x_u8_nhwc = int(u8)
+        for k, v in fields.items():
+            setattr(d, k, v.data_ptr() if isinstance(v, torch.Tensor) else v)
+        return d
+
+    w, b, y = t(BF, 32, 192), t(F32, 32), out_flat(dev, N * 5 * 5 * 32, BF)
+    for msg, xin, d in (
+            ("conv1 band: x2 needs 0 <= n_split <= N", x, conv1_desc(kn.BF16, x2=x, n_split=N + 1)),
+            ("conv1 band: x2 needs 0 <= n_split <= N", x, conv1_desc(kn.BF16, x2=x, n_split=-1)),
+            ("conv1 band: " + SLOTS, xu8, conv1_desc(kn.BF16, u8=True, x_slot=slot)),
+            ("conv1 band: " + SLOTS, x, conv1_desc(kn.BF16, x_slot=slot, x2_slot=slot)),
+            ("conv1 band: " + SLOTS, x, conv1_desc(kn.BF16, x2=x, n_split=N + 1, x2_slot=slot))):
+        refused(lambda: kn._call("hulc_conv2d_fwd", ctypes.byref(d), xin, w, b, y.t), msg, y)
+        no_path()
+    dw, db = out_flat(dev, 32 * 192, F32), out_flat(dev, 32, F32)
+    ws = torch.empty(kn._L.load().hulc_conv2d_bwd_weight_workspace(ctypes.byref(conv1_desc(kn.BF16))) // 4, dtype=F32, device=dev)
+    for msg, xin, dydt, d in (
+            ("conv1 weight gradient: x2 needs a bf16 gradient map", x, F32, conv1_desc(kn.F32, x2=x, n_split=1)),
+            ("conv1 weight gradient: x2 needs a bf16 gradient map", x, BF, conv1_desc(kn.BF16, x2=x, n_split=N + 1)),
+            ("conv1 weight gradient: x2 needs a bf16 gradient map", x, BF, conv1_desc(kn.BF16, x2=x, n_split=N + 1, x2_slot=slot)),
+            ("conv1 weight gradient: frame slots need the phase-plane kernel (bf16 gradient map)", x, F32, conv1_desc(kn.F32, x_slot=slot)),
+            ("conv1 weight gradient: " + SLOTS, xu8, BF, conv1_desc(kn.BF16, u8=True, x_slot=slot)),
+            ("conv1 weight gradient: " + SLOTS, x, BF, conv1_desc(kn.BF16, x_slot=slot, x2_slot=slot))):
+        refused(lambda: kn._call("hulc_conv2d_bwd_weight", ctypes.byref(d), xin, t(dydt, N, 5, 5, 32), dw.t, db.t, ws), msg, dw, db)
+        no_path()
