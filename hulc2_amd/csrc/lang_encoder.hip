@@ -117,10 +117,18 @@ extern "C" int hulc_ln_wide_fwd(const float* x, const float* add, const float* g
     return hulc_check_launch("hulc_ln_wide_fwd");
 }
 
+static size_t mha_smem(int S, int hd) { return ((size_t)2 * S * (hd + 1) + S) * sizeof(float); }
+static int mha_lds_ok() {
+    static int rc = hipFuncSetAttribute((const void*)mha_masked_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mha_smem(128, 64)) == hipSuccess ? 0 : -8;
+    return rc;
+}
+
 extern "C" int hulc_mha_masked_fwd(const float* qkv, const int* mask, int B, int S, int nhead, int hd, float* out, void* stream) {
     if (!qkv || !mask || !out) return hulc_fail(-1, "hulc_mha_masked_fwd: null pointer");
     if (B <= 0 || S <= 0 || S > 128 || nhead <= 0 || hd <= 0 || hd > 64) return hulc_fail(-2, "hulc_mha_masked_fwd: needs S <= 128 and head dim <= 64");
-    const size_t lds = (size_t)(2 * S * (hd + 1) + S) * sizeof(float);
+    const size_t lds = mha_smem(S, hd);
+    // 67,072 B at S = 128, hd = 64 (every hd = 64 with S >= 126, and hd = 63 at S = 128): above the default dynamic-LDS limit of 64 KiB
+    if (lds > 65536 && mha_lds_ok()) return hulc_fail(-8, "hulc_mha_masked_fwd: could not raise the dynamic LDS limit");
     mha_masked_kernel<<<B * nhead, 128, lds, (hipStream_t)stream>>>(qkv, mask, S, nhead, hd, out);
     return hulc_check_launch("hulc_mha_masked_fwd");
 }

@@ -83,42 +83,60 @@ __global__ __launch_bounds__(256) void maxpool_nhwc_kernel(const void* __restric
 // the statistics of the batch (biased variance) and keep updating running_mean / running_var (momentum 0.1, unbiased variance).  Three
 // launches per layer behind the (unfolded, bias-free) convolution: partial sums, finalize, apply.
 //
-// partial[p][0][c] = sum z, partial[p][1][c] = sum z^2 over the rows of slice p; rows per slice fixed, lanes walk channels (coalesced), the row
-// lanes of a workgroup are summed in a fixed order: bit-reproducible
-__global__ __launch_bounds__(256) void nhwc_bn_stats_kernel(const void* __restrict__ z, int dtype, long M, int C, long rows_per, float* __restrict__ partial) {
+// the pieces both statistics kernels share.  A lane adds at most 8 rows in fp32 (fs / fq) before the run goes into its double totals: an fp32
+// accumulator walked up to 256 rows in sequence — sqrt(256) roundings, 1e-6 of a mean, ten times what a pairwise float32 sum leaves
+HULC_DEVICE void bn_flush(double (&s)[8], double (&q)[8], float (&fs)[8], float (&fq)[8]) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { s[e] += (double)fs[e]; q[e] += (double)fq[e]; fs[e] = 0.f; fq[e] = 0.f; }
+}
+// v[] of the RL row lanes of a chunk column summed in lane order (fixed: bit-reproducible), in double; the result is in the lanes with rl == 0
+HULC_DEVICE void bn_fanin(double (&v)[8], double (*red)[9], int RL, int C8, int rl, int c80) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) red[threadIdx.x][e] = v[e];
+    __syncthreads();
+    if (rl == 0) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = 0.0;
+        for (int k = 0; k < RL; ++k)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] += red[k * C8 + c80][e];
+    }
+    __syncthreads();
+}
+
+// partial[p][0][c] = sum (z - k), partial[p][1][c] = sum (z - k)^2 over the rows of slice p, k[c] = z[row 0][c] the channel's pivot: the
+// variance is shift-invariant, and q / M - (s / M)^2 on the SHIFTED sums cancels |mean - k|^2 / var digits (a few, k being a sample of the
+// channel) instead of the mean^2 / var digits of the raw sums — at mean / std = 64 those fp32 slice sums left the variance with a relative
+// error of 4e-4, which no double finalize can undo.  Runs of 8 rows are summed in fp32, the runs of a lane and the fan-in of the row lanes in
+// double, and so are the slice totals in the workspace (the pivot is one sample: q / M can be a dozen times the variance, and an fp32 total
+// would hand that factor to its rounding).  Rows per slice fixed, lanes walk channels (coalesced), the row lanes of a
+// workgroup are summed in a fixed order: bit-reproducible
+__global__ __launch_bounds__(256) void nhwc_bn_stats_kernel(const void* __restrict__ z, int dtype, long M, int C, long rows_per, double* __restrict__ partial) {
     // (round 5: 8-channel chunks per thread — 16-byte / 2 x 16-byte loads — instead of one channel with scalar loads; same slices, the row
     //  lanes of a chunk summed through LDS in lane order: bit-reproducible)
-    __shared__ float red[256][17];
+    __shared__ double red[256][9];
     const int C8 = C / 8;
     const int RL = C8 >= 256 ? 1 : 256 / C8;
     const int rl = threadIdx.x / (C8 >= 256 ? 256 : C8), c80 = threadIdx.x % (C8 >= 256 ? 256 : C8);
     const long r0 = (long)blockIdx.x * rows_per, r1 = r0 + rows_per < M ? r0 + rows_per : M;
     for (int c8 = c80; c8 < C8; c8 += 256) {
-        float s[8], q[8];
+        double s[8], q[8];
+        float fs[8], fq[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) { s[e] = 0.f; q[e] = 0.f; }
+        for (int e = 0; e < 8; ++e) { s[e] = 0.0; q[e] = 0.0; fs[e] = 0.f; fq[e] = 0.f; }
+        Chunk8 kv;
+        chunk_load_contig(kv, z, dtype, (long)c8 * 8);        // the pivots: row 0 of the map
         auto term = [&](long row) {
             Chunk8 v;
             chunk_load_contig(v, z, dtype, row * C + c8 * 8);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) { s[e] += v.v[e]; q[e] += v.v[e] * v.v[e]; }
+            for (int e = 0; e < 8; ++e) { const float d = v.v[e] - kv.v[e]; fs[e] += d; fq[e] += d * d; }
         };
         long r = r0 + rl;
-        for (; r + RL < r1; r += 2 * RL) { term(r); term(r + RL); }
+        for (int n = 0; r + RL < r1; r += 2 * RL) { term(r); term(r + RL); if (++n == 4) { bn_flush(s, q, fs, fq); n = 0; } }
         if (r < r1) term(r);
-        if (RL > 1) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { red[threadIdx.x][e] = s[e]; red[threadIdx.x][8 + e] = q[e]; }
-            __syncthreads();
-            if (rl == 0) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { s[e] = 0.f; q[e] = 0.f; }
-                for (int k = 0; k < RL; ++k)
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) { s[e] += red[k * C8 + c80][e]; q[e] += red[k * C8 + c80][8 + e]; }
-            }
-            __syncthreads();
-        }
+        bn_flush(s, q, fs, fq);
+        if (RL > 1) { bn_fanin(s, red, RL, C8, rl, c80); bn_fanin(q, red, RL, C8, rl, c80); }
         if (rl == 0) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
@@ -129,17 +147,22 @@ __global__ __launch_bounds__(256) void nhwc_bn_stats_kernel(const void* __restri
     }
 }
 
-// per channel: the P partials summed in order (double), scale = gamma * rsqrt(var_biased + eps), shift = beta - mean * scale; running statistics
-// updated like nn.BatchNorm2d in training mode (momentum, unbiased variance); ss[c] = scale, ss[C + c] = shift
-__global__ __launch_bounds__(256) void nhwc_bn_finalize_kernel(const float* __restrict__ partial, int P, long M, int C, const float* __restrict__ gamma,
+// per channel: the P partials (sums of z - k and (z - k)^2, k = z[row 0][c]) summed in order (double), mean = k + s / M, var_biased = q / M -
+// (s / M)^2, scale = gamma * rsqrt(var_biased + eps), shift = beta - mean * scale; running statistics updated like nn.BatchNorm2d in training
+// mode (momentum, unbiased variance; a single row keeps its biased variance 0 where torch's M / (M - 1) gives NaN); ss[c] = scale, ss[C + c] = shift
+__global__ __launch_bounds__(256) void nhwc_bn_finalize_kernel(const double* __restrict__ partial, int P, long M, int C, const void* __restrict__ z,
+                                                               int z_dtype, const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, float eps, float momentum, float* __restrict__ run_mean,
                                                                float* __restrict__ run_var, float* __restrict__ ss, float* __restrict__ saved) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     double s = 0.0, q = 0.0;
-    for (int p = 0; p < P; ++p) { s += (double)partial[((long)p * 2) * C + c]; q += (double)partial[((long)p * 2 + 1) * C + c]; }
-    const double mean = s / (double)M;
-    double var = q / (double)M - mean * mean;
+    for (int p = 0; p < P; ++p) { s += partial[((long)p * 2) * C + c]; q += partial[((long)p * 2 + 1) * C + c]; }
+    const double ds = s / (double)M;
+    Chunk8 kv;
+    chunk_load_contig(kv, z, z_dtype, (long)(c & ~7));       // the pivot as the statistics kernel read it
+    const double mean = (double)kv.v[c & 7] + ds;
+    double var = q / (double)M - ds * ds;
     if (var < 0.0) var = 0.0;
     const float scale = gamma[c] * (float)(1.0 / sqrt(var + (double)eps));
     ss[c] = scale; ss[C + c] = beta[c] - (float)mean * scale;
@@ -176,19 +199,20 @@ __global__ __launch_bounds__(256) void nhwc_bn_apply_kernel(const void* __restri
 // dz = gamma * rstd * (g - s1 / M - xhat * s2 / M);  dgamma = s2, dbeta = s1.  Same slicing and summation order as the forward statistics.
 __global__ __launch_bounds__(256) void nhwc_bn_bwd_stats_kernel(const void* __restrict__ dy, int dy_dtype, const void* __restrict__ y, int y_dtype,
                                                                 const float* __restrict__ z, long M, int C, long rows_per,
-                                                                const float* __restrict__ saved, float* __restrict__ partial) {
+                                                                const float* __restrict__ saved, double* __restrict__ partial) {
     // a thread owns an 8-channel chunk (16-byte loads of the bf16 maps, two of the fp32 z) and every RL-th row of the slice, two rows in flight;
     // the row lanes of a chunk are summed through LDS in lane order (fixed: bit-reproducible).  (The first version walked one channel per
     // thread with scalar loads: 250 us per layer at 32 images — 15 x the time its bytes take.)
-    __shared__ float red[256][17];
+    __shared__ double red[256][9];
     const int C8 = C / 8;
     const int RL = C8 >= 256 ? 1 : 256 / C8;               // row lanes per chunk column
     const int rl = threadIdx.x / (C8 >= 256 ? 256 : C8), c80 = threadIdx.x % (C8 >= 256 ? 256 : C8);
     const long r0 = (long)blockIdx.x * rows_per, r1 = r0 + rows_per < M ? r0 + rows_per : M;
     for (int c8 = c80; c8 < C8; c8 += 256) {
-        float mean[8], rstd[8], s[8], q[8];
+        float mean[8], rstd[8], fs[8], fq[8];
+        double s[8], q[8];                                     // (runs of 8 rows in fp32, the runs in double: see bn_flush)
 #pragma unroll
-        for (int e = 0; e < 8; ++e) { mean[e] = saved[c8 * 8 + e]; rstd[e] = saved[C + c8 * 8 + e]; s[e] = 0.f; q[e] = 0.f; }
+        for (int e = 0; e < 8; ++e) { mean[e] = saved[c8 * 8 + e]; rstd[e] = saved[C + c8 * 8 + e]; s[e] = 0.0; q[e] = 0.0; fs[e] = 0.f; fq[e] = 0.f; }
         auto term = [&](long row) {
             const long off = row * C + c8 * 8;
             Chunk8 g, yy;
@@ -199,25 +223,14 @@ __global__ __launch_bounds__(256) void nhwc_bn_bwd_stats_kernel(const void* __re
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const float gg = (y && !(yy.v[e] > 0.f)) ? 0.f : g.v[e];
-                s[e] += gg; q[e] += gg * ((zv[e] - mean[e]) * rstd[e]);
+                fs[e] += gg; fq[e] += gg * ((zv[e] - mean[e]) * rstd[e]);
             }
         };
         long r = r0 + rl;
-        for (; r + RL < r1; r += 2 * RL) { term(r); term(r + RL); }
+        for (int n = 0; r + RL < r1; r += 2 * RL) { term(r); term(r + RL); if (++n == 4) { bn_flush(s, q, fs, fq); n = 0; } }
         if (r < r1) term(r);
-        if (RL > 1) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { red[threadIdx.x][e] = s[e]; red[threadIdx.x][8 + e] = q[e]; }
-            __syncthreads();
-            if (rl == 0) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { s[e] = 0.f; q[e] = 0.f; }
-                for (int k = 0; k < RL; ++k)
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) { s[e] += red[k * C8 + c80][e]; q[e] += red[k * C8 + c80][8 + e]; }
-            }
-            __syncthreads();
-        }
+        bn_flush(s, q, fs, fq);
+        if (RL > 1) { bn_fanin(s, red, RL, C8, rl, c80); bn_fanin(q, red, RL, C8, rl, c80); }
         if (rl == 0) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
@@ -228,12 +241,12 @@ __global__ __launch_bounds__(256) void nhwc_bn_bwd_stats_kernel(const void* __re
     }
 }
 
-__global__ __launch_bounds__(256) void nhwc_bn_bwd_finalize_kernel(const float* __restrict__ partial, int P, long M, int C, float* __restrict__ sums,
+__global__ __launch_bounds__(256) void nhwc_bn_bwd_finalize_kernel(const double* __restrict__ partial, int P, long M, int C, float* __restrict__ sums,
                                                                    float* __restrict__ dgamma, float* __restrict__ dbeta, int accumulate) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     double s = 0.0, q = 0.0;
-    for (int p = 0; p < P; ++p) { s += (double)partial[((long)p * 2) * C + c]; q += (double)partial[((long)p * 2 + 1) * C + c]; }
+    for (int p = 0; p < P; ++p) { s += partial[((long)p * 2) * C + c]; q += partial[((long)p * 2 + 1) * C + c]; }
     sums[c] = (float)(s / (double)M); sums[C + c] = (float)(q / (double)M);
     if (dbeta) dbeta[c] = (accumulate ? dbeta[c] : 0.f) + (float)s;
     if (dgamma) dgamma[c] = (accumulate ? dgamma[c] : 0.f) + (float)q;
@@ -348,7 +361,7 @@ __global__ __launch_bounds__(256) void nhwc_scatter_kernel(const void* __restric
 // see include/hulc2_amd.h
 extern "C" long hulc_nhwc_bn_train_workspace(long M, int C) {
     long P = (M + 255) / 256; if (P > 1024) P = 1024; if (P < 1) P = 1;
-    return (P * 2 * C + 2 * C) * (long)sizeof(float);
+    return P * 2 * C * (long)sizeof(double) + 2 * C * (long)sizeof(float);      // the slices' partial sums (double), then scale / shift or the two means
 }
 
 extern "C" int hulc_nhwc_bn_train_fwd(const void* z, int z_dtype, long M, int C, const float* gamma, const float* beta, float eps, float momentum,
@@ -363,14 +376,15 @@ extern "C" int hulc_nhwc_bn_train_fwd_saved(const void* z, int z_dtype, long M, 
     if (!z || !gamma || !beta || !y || !ws) return hulc_fail(-1, "hulc_nhwc_bn_train_fwd: null pointer");
     if (M < 1 || C < 8 || C % 8 || C > 2048 || (C < 256 && 256 % C)) return hulc_fail(-2, "hulc_nhwc_bn_train_fwd: C must be a multiple of 8 (a divisor of 256 below 256)");
     if (((uintptr_t)z | (uintptr_t)y | (uintptr_t)add) % 16) return hulc_fail(-4, "hulc_nhwc_bn_train_fwd: 16-byte aligned rows");
+    if ((uintptr_t)ws % 8) return hulc_fail(-4, "hulc_nhwc_bn_train_fwd: the workspace holds doubles: 8-byte aligned");
     long P = (M + 255) / 256; if (P > 1024) P = 1024; if (P < 1) P = 1;
     const long rows_per = (M + P - 1) / P;
     P = (M + rows_per - 1) / rows_per;
-    float* partial = (float*)ws;
-    float* ss = partial + P * 2 * C;
+    double* partial = (double*)ws;
+    float* ss = (float*)(partial + P * 2 * C);
     hipStream_t s = (hipStream_t)stream;
     nhwc_bn_stats_kernel<<<(unsigned)P, 256, 0, s>>>(z, z_dtype, M, C, rows_per, partial);
-    nhwc_bn_finalize_kernel<<<(unsigned)((C + 255) / 256), 256, 0, s>>>(partial, (int)P, M, C, gamma, beta, eps, momentum, run_mean, run_var, ss, saved);
+    nhwc_bn_finalize_kernel<<<(unsigned)((C + 255) / 256), 256, 0, s>>>(partial, (int)P, M, C, z, z_dtype, gamma, beta, eps, momentum, run_mean, run_var, ss, saved);
     const long total8 = M * (C / 8);
     nhwc_bn_apply_kernel<<<(unsigned)((total8 + 255) / 256), 256, 0, s>>>(z, z_dtype, total8, C / 8, ss, add, add_dtype, relu, y, y_dtype);
     return hulc_check_launch("hulc_nhwc_bn_train_fwd");
@@ -411,11 +425,12 @@ extern "C" int hulc_nhwc_bn_train_bwd(const void* dy, int dy_dtype, const void* 
     if (!dy || !z || !gamma || !saved || !dz || !ws) return hulc_fail(-1, "hulc_nhwc_bn_train_bwd: null pointer");
     if (M < 1 || C < 8 || C % 8 || C > 2048 || (C < 256 && 256 % C)) return hulc_fail(-2, "hulc_nhwc_bn_train_bwd: C must be a multiple of 8 (a divisor of 256 below 256)");
     if (((uintptr_t)dy | (uintptr_t)y | (uintptr_t)z | (uintptr_t)dz | (uintptr_t)g_out) % 16) return hulc_fail(-4, "hulc_nhwc_bn_train_bwd: 16-byte aligned rows");
+    if ((uintptr_t)ws % 8) return hulc_fail(-4, "hulc_nhwc_bn_train_bwd: the workspace holds doubles: 8-byte aligned");
     long P = (M + 255) / 256; if (P > 1024) P = 1024; if (P < 1) P = 1;
     const long rows_per = (M + P - 1) / P;
     P = (M + rows_per - 1) / rows_per;
-    float* partial = (float*)ws;
-    float* sums = partial + P * 2 * C;
+    double* partial = (double*)ws;
+    float* sums = (float*)(partial + P * 2 * C);
     hipStream_t s = (hipStream_t)stream;
     nhwc_bn_bwd_stats_kernel<<<(unsigned)P, 256, 0, s>>>(dy, dy_dtype, y, y_dtype, z, M, C, rows_per, saved, partial);
     nhwc_bn_bwd_finalize_kernel<<<(unsigned)((C + 255) / 256), 256, 0, s>>>(partial, (int)P, M, C, sums, dgamma, dbeta, accumulate_params);

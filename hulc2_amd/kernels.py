@@ -1403,6 +1403,21 @@ def world_to_tcp(act, robot_obs, n, obs_dim, out):
 def embed_ln_fwd(ids, word, pos, type0, gamma, beta, eps, T, S, D, out):
     if ids.dtype != torch.int64 or not ids.is_contiguous():
         raise TypeError("embed_ln_fwd: token ids are a contiguous int64 tensor")
+    # the kernel indexes word[id], pos[t % S] and row t of out without looking at the tables' sizes: every bound is checked here
+    for name, t in (("word", word), ("pos", pos)):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != D or not t.is_contiguous():
+            raise TypeError(f"embed_ln_fwd: {name} is a contiguous fp32 (rows, {D}) table")
+    for name, t, n in (("type0", type0, D), ("gamma", gamma, D), ("beta", beta, D), ("out", out, T * D)):
+        if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous():
+            raise TypeError(f"embed_ln_fwd: {name} is a contiguous fp32 tensor of {n} elements")
+    if ids.numel() != T:
+        raise ValueError(f"embed_ln_fwd: {ids.numel()} token ids for T = {T}")
+    if S > pos.shape[0]:
+        raise ValueError(f"embed_ln_fwd: S = {S} exceeds the position table's {pos.shape[0]} rows")
+    if T > 0 and not (ids.is_cuda and torch.cuda.is_current_stream_capturing()):   # (reading the ids back synchronises: not inside a capture)
+        lo, hi = (int(v) for v in torch.aminmax(ids))
+        if lo < 0 or hi >= word.shape[0]:
+            raise ValueError(f"embed_ln_fwd: token ids span [{lo}, {hi}], the vocabulary has {word.shape[0]} rows")
     _call("hulc_embed_ln_fwd", ids, word, pos, type0, gamma, beta, eps, T, S, D, out)
     return out
 

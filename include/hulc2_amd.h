@@ -367,7 +367,8 @@ int hulc_maxpool_nhwc(const void* x, int dtype, int N, int H, int W, int C, int 
  * sqrt(var_biased + eps) + beta + add); run_mean / run_var (optional) are updated with `momentum` and the unbiased variance.  The affordance
  * model's trunk as the reference runs it (hulc2/affordance/models/visual_lang_encoders/r3m_rn18.py:27-43 freezes the PARAMETERS of
  * layer1..4 only; pixel_aff_lang_detector.py:51-53 leaves train mode on, so the trunk's BatchNorms use batch statistics).  z / add / y: fp32
- * or bf16; C a multiple of 8 (a divisor of 256 below 256); ws: hulc_nhwc_bn_train_workspace(M, C) bytes.  Fixed summation order. */
+ * or bf16; C a multiple of 8 (a divisor of 256 below 256); ws: hulc_nhwc_bn_train_workspace(M, C) bytes, 8-byte aligned (the slices' partial
+ * sums are doubles).  Fixed summation order. */
 long hulc_nhwc_bn_train_workspace(long M, int C);
 int hulc_nhwc_bn_train_fwd(const void* z, int z_dtype, long M, int C, const float* gamma, const float* beta, float eps, float momentum,
                            float* run_mean, float* run_var, const void* add, int add_dtype, int relu, void* y, int y_dtype, void* ws, void* stream);
