@@ -7,6 +7,7 @@
 // normalisation and the stem's max pool.  The global average pool is hulc_strided_seq_sum over the (H*W) axis.
 #include "hulc_common.h"
 #include "hulc_abi_internal.h"
+#include "u8_frames.h"
 
 namespace {
 
@@ -42,6 +43,77 @@ __global__ __launch_bounds__(256) void r3m_normalize_packed_kernel(const float* 
         o = make_uint2(pack_bf16x2((px[0] / 255.f - m0) * s0, (px[HW] / 255.f - m1) * s1), pack_bf16x2((px[2 * HW] / 255.f - m2) * s2, 0.f));
     }
     y[i] = o;
+}
+
+// The stem's input straight from the uint8 NHWC episode store (hulc_r3m_stage_u8): batch frame n is store frame fidx[n] (null: n), shifted as
+// conv1 shifts it (output pixel (y, x) = source pixel (clamp(y + sy - pad), clamp(x + sx - pad))), every byte looked up in lut[c][byte] — the
+// transform chain and the normalisation, tabulated by the fp32 kernels above, so the values are theirs bit for bit.  PACKED: the layout of
+// r3m_normalize_packed_kernel (border 3, WP = the packed width, 8 bytes a pixel, zero border written here); else NHWC-8 (WP = W, T = bf16 bits
+// or float, channels 3..7 zero).  Block = 4 waves on STAGE_ROWS output rows of one frame; a lane takes 4 consecutive output columns: their 12
+// source bytes are one window of u8_frames.h (3-4 aligned dword loads), and it stores 32 (packed) / 64 / 128 contiguous bytes.
+constexpr int STAGE_ROWS = 16;
+
+template <typename T, bool PACKED>
+__global__ __launch_bounds__(256) void r3m_stage_u8_kernel(const unsigned char* __restrict__ frames, long n_store, int H, int W, int WP,
+                                                           const int* __restrict__ fidx, const int* __restrict__ shift, int pad,
+                                                           const T* __restrict__ lut, char* __restrict__ y) {
+    __shared__ T slut[3 * 256];
+    for (int i = threadIdx.y * 64 + threadIdx.x; i < 3 * 256; i += 256) slut[i] = lut[i];
+    __syncthreads();
+    constexpr int B = PACKED ? 3 : 0, PIX = PACKED ? 8 : 8 * (int)sizeof(T);        // border; bytes of an output pixel
+    const int n = blockIdx.x, HP = H + 2 * B;
+    long fi = fidx ? fidx[n] : n;
+    fi = fi < 0 ? 0 : (fi > n_store - 1 ? n_store - 1 : fi);                        // a bad frame number must not leave the store
+    int dx = 0, dy = 0;
+    if (shift) {                                                                    // (clamped: any draw keeps the index arithmetic in range)
+        dx = shift[2 * n] - pad; dy = shift[2 * n + 1] - pad;
+        dx = dx < -W ? -W : (dx > W ? W : dx); dy = dy < -H ? -H : (dy > H ? H : dy);
+    }
+    const unsigned char* img = frames + fi * ((long)H * W * 3);
+    const int groups = (WP + 3) / 4;
+    const int yp_end = min(HP, ((int)blockIdx.y + 1) * STAGE_ROWS);
+    for (int yp = blockIdx.y * STAGE_ROWS + threadIdx.y; yp < yp_end; yp += 4) {
+        const int yo = yp - B;
+        const bool row_in = yo >= 0 && yo < H;
+        int yy = yo + dy;
+        yy = yy < 0 ? 0 : (yy > H - 1 ? H - 1 : yy);
+        char* orow = y + ((long)n * HP + yp) * WP * PIX;
+        for (int j = threadIdx.x; j < groups; j += 64) {
+            const int x0 = 4 * j - B;                                               // output column of element 0
+            const bool live = row_in && x0 + 3 >= 0 && x0 < W;
+            uint32_t e0, e1, e2, ch[3];
+            const int d = u8_window_raw(img, W, yy, x0 + dx, live, e0, e1, e2);
+            u8_window_bytes(e0, e1, e2, d, ch);
+            T v[4][3];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const bool in = live && x0 + i >= 0 && x0 + i < W;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) v[i][c] = in ? slut[c * 256 + ((ch[c] >> (8 * i)) & 0xffu)] : (T)0;
+            }
+            if constexpr (sizeof(T) == 2) {
+                uint2 p[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) p[i] = make_uint2((uint32_t)v[i][0] | ((uint32_t)v[i][1] << 16), (uint32_t)v[i][2]);
+                if constexpr (PACKED) {                                             // WP is even: a pair of pixels is whole or absent
+                    uint4* o = (uint4*)(orow + (long)j * 32);
+                    o[0] = make_uint4(p[0].x, p[0].y, p[1].x, p[1].y);
+                    if (4 * j + 2 < WP) o[1] = make_uint4(p[2].x, p[2].y, p[3].x, p[3].y);
+                } else {
+                    uint4* o = (uint4*)(orow + (long)j * 64);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) o[i] = make_uint4(p[i].x, p[i].y, 0u, 0u);
+                }
+            } else {
+                float4* o = (float4*)(orow + (long)j * 128);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    o[2 * i] = make_float4(v[i][0], v[i][1], v[i][2], 0.f);
+                    o[2 * i + 1] = make_float4(0.f, 0.f, 0.f, 0.f);
+                }
+            }
+        }
+    }
 }
 
 // max pool k x k, stride s, padding p (padded positions never win: nn.MaxPool2d pads with -inf), NHWC, 8 channels per thread
@@ -407,6 +479,28 @@ extern "C" int hulc_r3m_normalize_packed(const float* x, int N, int H, int W, co
     r3m_normalize_packed_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(x, H, W, Wp, total, mean3[0], mean3[1], mean3[2],
                                                                                                   1.f / std3[0], 1.f / std3[1], 1.f / std3[2], (uint2*)xp);
     return hulc_check_launch("hulc_r3m_normalize_packed");
+}
+
+extern "C" int hulc_r3m_stage_u8(const unsigned char* frames, long n_store, int N, int H, int W, const int* frame_index, const int* shift, int pad,
+                                 const void* lut, void* y, int y_dtype, int packed, void* stream) {
+    if (!frames || !lut || !y) return hulc_fail(-1, "hulc_r3m_stage_u8: null pointer");
+    if (W < 4 || W % 4) return hulc_fail(-2, "hulc_r3m_stage_u8: W must be a multiple of 4 (the byte windows are aligned dwords)");
+    if (N <= 0 || H <= 0 || n_store <= 0 || pad < 0 || (long)H * W * 3 >= (1L << 31) || (H + 6 + STAGE_ROWS - 1) / STAGE_ROWS > 65535)
+        return hulc_fail(-2, "hulc_r3m_stage_u8: bad shape");
+    if (!frame_index && N > n_store) return hulc_fail(-2, "hulc_r3m_stage_u8: more frames than the store holds and no frame_index");
+    if (packed ? y_dtype != HULC_BF16 : (y_dtype != HULC_BF16 && y_dtype != HULC_F32))
+        return hulc_fail(-3, "hulc_r3m_stage_u8: the packed stem input is bf16, NHWC-8 is bf16 or fp32");
+    if ((uintptr_t)frames % 4 || (uintptr_t)y % 16) return hulc_fail(-4, "hulc_r3m_stage_u8: frames 4-byte aligned, y 16-byte aligned");
+    const int HP = packed ? H + 6 : H, WP = packed ? hulc_r3m_packed_width(W) : W;
+    const dim3 grid((unsigned)N, (unsigned)((HP + STAGE_ROWS - 1) / STAGE_ROWS)), block(64, 4);
+    hipStream_t s = (hipStream_t)stream;
+    if (packed)
+        r3m_stage_u8_kernel<uint16_t, true><<<grid, block, 0, s>>>(frames, n_store, H, W, WP, frame_index, shift, pad, (const uint16_t*)lut, (char*)y);
+    else if (y_dtype == HULC_BF16)
+        r3m_stage_u8_kernel<uint16_t, false><<<grid, block, 0, s>>>(frames, n_store, H, W, WP, frame_index, shift, pad, (const uint16_t*)lut, (char*)y);
+    else
+        r3m_stage_u8_kernel<float, false><<<grid, block, 0, s>>>(frames, n_store, H, W, WP, frame_index, shift, pad, (const float*)lut, (char*)y);
+    return hulc_check_launch("hulc_r3m_stage_u8");
 }
 
 extern "C" int hulc_maxpool_nhwc(const void* x, int dtype, int N, int H, int W, int C, int k, int stride, int pad, void* y, void* stream) {

@@ -18,14 +18,19 @@
 // (element i <- window pixel clamp(i + d, 0, 3); the selector is a byte window of 00 00 00 00 | 00 01 02 03 | 03 03 03 03 at 4 + d, d == 0
 // being the identity, so there is no divergent path).  Conversion is v_cvt_f32_ubyteN + a packed fma + v_cvt_pk_bf16: ~55 VALU per half
 // where per-element float selects cost ~120 (the staging of uint8 frames is VALU-bound: tools/conv1_u8_probe.py).
-HULC_DEVICE void u8_window_planes(uint32_t e0, uint32_t e1, uint32_t e2, int d, bool live, uint32_t (&o)[3][2]) {
+HULC_DEVICE void u8_window_bytes(uint32_t e0, uint32_t e1, uint32_t e2, int d, uint32_t (&ch)[3]) {
     const int k = (d < -3 ? -3 : (d > 3 ? 3 : d)) + 4;             // |d| >= 3: every element is the border pixel
     const uint32_t lo = k < 4 ? 0u : 0x03020100u, hi = k < 4 ? 0x03020100u : 0x03030303u;
     const uint32_t rep = __builtin_amdgcn_alignbyte(hi, lo, (uint32_t)k & 3u);
-    const uint32_t ch[3] = {
-        __builtin_amdgcn_perm(0u, __builtin_amdgcn_perm(e2, __builtin_amdgcn_perm(e1, e0, 0x00060300u), 0x05020100u), rep),
-        __builtin_amdgcn_perm(0u, __builtin_amdgcn_perm(e2, __builtin_amdgcn_perm(e1, e0, 0x00070401u), 0x06020100u), rep),
-        __builtin_amdgcn_perm(0u, __builtin_amdgcn_perm(e2, __builtin_amdgcn_perm(e1, e0, 0x00000502u), 0x07040100u), rep)};
+    ch[0] = __builtin_amdgcn_perm(0u, __builtin_amdgcn_perm(e2, __builtin_amdgcn_perm(e1, e0, 0x00060300u), 0x05020100u), rep);
+    ch[1] = __builtin_amdgcn_perm(0u, __builtin_amdgcn_perm(e2, __builtin_amdgcn_perm(e1, e0, 0x00070401u), 0x06020100u), rep);
+    ch[2] = __builtin_amdgcn_perm(0u, __builtin_amdgcn_perm(e2, __builtin_amdgcn_perm(e1, e0, 0x00000502u), 0x07040100u), rep);
+}
+
+// ... and their conversion (the comment above): the bf16 plane data of the three channels, zero when not live
+HULC_DEVICE void u8_window_planes(uint32_t e0, uint32_t e1, uint32_t e2, int d, bool live, uint32_t (&o)[3][2]) {
+    uint32_t ch[3];
+    u8_window_bytes(e0, e1, e2, d, ch);                            // byte i of ch[c]: channel c of element i
     const f32x2_t k2 = {2.0f / 255.0f, 2.0f / 255.0f}, m2 = {-1.f, -1.f};
     const uint32_t lm = live ? 0xffffffffu : 0u;
 #pragma unroll
@@ -37,19 +42,26 @@ HULC_DEVICE void u8_window_planes(uint32_t e0, uint32_t e1, uint32_t e2, int d, 
     }
 }
 
-HULC_DEVICE void u8_half4(const unsigned char* img, int H, int W, int row, int x, int dx, int dy, bool live, uint32_t (&o)[3][2]) {
-    int yy = row + dy;
-    yy = yy < 0 ? 0 : (yy > H - 1 ? H - 1 : yy);
-    const int xx0 = x + dx;
+// the raw window of the 4 elements whose first source column is xx0 (any value; the row yy is already clamped): the 12 bytes of source pixels
+// pw .. pw + 3, pw = clamp(xx0, 0, W - 4), realigned to e0 e1 e2; returns d = xx0 - pw for u8_window_bytes.  Every load lies inside the frame:
+// the window ends at most at the frame's last byte, a multiple of 4 from `img` (W % 4 == 0), so the dword holding its tail ends there too.
+HULC_DEVICE int u8_window_raw(const unsigned char* img, int W, int yy, int xx0, bool live, uint32_t& e0, uint32_t& e1, uint32_t& e2) {
     const int pw = xx0 < 0 ? 0 : (xx0 > W - 4 ? W - 4 : xx0);        // first pixel of the 4-pixel source window
-    const int d = xx0 - pw;                                           // != 0: some of the 4 elements are replicated border pixels
     const int b0 = (yy * W + pw) * 3;                                 // < 2^31 for any camera frame
     const int sh = b0 & 3;
     const uint32_t* q = (const uint32_t*)(img + (b0 - sh));
     uint32_t w0 = 0, w1 = 0, w2 = 0, w3 = 0;
     if (live) { w0 = q[0]; w1 = q[1]; w2 = q[2]; if (sh) w3 = q[3]; }  // the fourth dword is only needed (and only in bounds) when sh > 0
-    const uint32_t e0 = __builtin_amdgcn_alignbyte(w1, w0, sh), e1 = __builtin_amdgcn_alignbyte(w2, w1, sh),
-                   e2 = __builtin_amdgcn_alignbyte(w3, w2, sh);       // R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3
+    e0 = __builtin_amdgcn_alignbyte(w1, w0, sh); e1 = __builtin_amdgcn_alignbyte(w2, w1, sh);
+    e2 = __builtin_amdgcn_alignbyte(w3, w2, sh);                      // R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3
+    return xx0 - pw;                                                  // != 0: some of the 4 elements are replicated border pixels
+}
+
+HULC_DEVICE void u8_half4(const unsigned char* img, int H, int W, int row, int x, int dx, int dy, bool live, uint32_t (&o)[3][2]) {
+    int yy = row + dy;
+    yy = yy < 0 ? 0 : (yy > H - 1 ? H - 1 : yy);
+    uint32_t e0, e1, e2;
+    const int d = u8_window_raw(img, W, yy, x + dx, live, e0, e1, e2);
     u8_window_planes(e0, e1, e2, d, live, o);
 }
 

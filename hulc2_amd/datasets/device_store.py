@@ -46,11 +46,13 @@ class DeviceEpisodeStore:
     def __init__(self, rgb: Dict[str, torch.Tensor], rel_actions: torch.Tensor, robot_obs: torch.Tensor, ep_start_end_ids,
                  min_window_size: int = 20, max_window_size: int = 32, pad: bool = True, validation: bool = False,
                  scene_obs: Optional[torch.Tensor] = None, lang_emb: Optional[torch.Tensor] = None,
-                 lang_lookup: Optional[Sequence[int]] = None, device=None, seed: int = 0, aux_lang_loss_window: int = 1):
+                 lang_lookup: Optional[Sequence[int]] = None, device=None, seed: int = 0, aux_lang_loss_window: int = 1,
+                 aug_pad: Optional[Dict[str, int]] = None):
         """rgb: {"rgb_static": (n, 200, 200, 3) uint8, "rgb_gripper": (n, 84, 84, 3) uint8} — the frames of all episodes back to
         back; rel_actions (n, 7), robot_obs (n, 15) [, scene_obs (n, 24)] fp32; ep_start_end_ids (E, 2): first / last store frame of
         each episode (inclusive, as ep_start_end_ids.npy).  lang_emb (n_ann, 384) + lang_lookup (one annotation per window start)
-        make it the language dataset."""
+        make it the language dataset.  aug_pad: RandomShiftsAug's pad per camera, overriding AUG_PAD; a camera with pad 0 has no shift
+        augmentation (the real-world static camera, conf/datamodule/transforms/real_world_r3m.yaml): no draws, no `_shift` entry."""
         if min_window_size > max_window_size:
             raise ValueError(f"min_window_size {min_window_size} > max_window_size {max_window_size}")   # base_dataset.py:103-105
         if not pad and min_window_size != max_window_size:
@@ -81,6 +83,9 @@ class DeviceEpisodeStore:
         if self.lang_lookup is not None and len(self.lang_lookup) != len(self.episode_lookup):
             raise ValueError("lang_lookup holds one annotation number per window start")
         self.aux_lang_loss_window = aux_lang_loss_window
+        self.aug_pad = {k: int({**self.AUG_PAD, **(aug_pad or {})}.get(k, 0)) for k in self.rgb}
+        if min(self.aug_pad.values(), default=0) < 0:
+            raise ValueError(f"aug_pad {self.aug_pad}: a pad is >= 0")
         self.np_rng = np.random.RandomState(seed)
         self.generator = torch.Generator().manual_seed(seed)
         self._buf: Dict[int, Dict] = {}
@@ -152,7 +157,7 @@ class DeviceEpisodeStore:
             S, dev = self.max_window_size, self.device
             keys = sorted(self.rgb)
             off, n = {}, 0
-            for name, cnt in [("idx64", 2 * B), ("starts", B), ("sizes", B), ("ann", B), ("use", B)] + [(k + "_shift", B * S * 2) for k in keys]:
+            for name, cnt in [("idx64", 2 * B), ("starts", B), ("sizes", B), ("ann", B), ("use", B)] + [(k + "_shift", B * S * 2) for k in keys if self.aug_pad[k]]:
                 off[name] = (n, cnt); n += cnt
             blk = torch.zeros(n, dtype=torch.int32, device=dev)
             view = lambda t, name: t[off[name][0]:off[name][0] + off[name][1]]
@@ -164,7 +169,8 @@ class DeviceEpisodeStore:
                  "actions": torch.zeros(B, S, self.rel_actions.shape[1], device=dev),
                  "robot_obs": torch.zeros(B, S, self.robot_obs.shape[1], device=dev)}
             for k in keys:
-                b[k + "_shift"] = view(blk, k + "_shift").view(B, S, 2)
+                if self.aug_pad[k]:
+                    b[k + "_shift"] = view(blk, k + "_shift").view(B, S, 2)
             if self.scene_obs is not None:
                 b["scene_obs"] = torch.zeros(B, S, self.scene_obs.shape[1], device=dev)
             if self.lang_emb is not None:
@@ -193,7 +199,9 @@ class DeviceEpisodeStore:
         with_shift = shifts is not None or not self.validation         # the validation transforms carry no RandomShiftsAug
         if with_shift:
             for k in self.rgb:
-                pad = self.AUG_PAD.get(k, 0)
+                pad = self.aug_pad[k]
+                if not pad:
+                    continue
                 if shifts is not None:
                     hv(k + "_shift").copy_(shifts[k].reshape(-1).to(torch.int32))
                 else:
@@ -215,7 +223,7 @@ class DeviceEpisodeStore:
         for k, store in self.rgb.items():
             rgb_obs[k] = store
             rgb_obs[k + "_index"] = buf["index"]
-            if with_shift:
+            if with_shift and self.aug_pad[k]:
                 rgb_obs[k + "_shift"] = buf[k + "_shift"]
         out = {"rgb_obs": rgb_obs, "depth_obs": {}, "robot_obs": buf["robot_obs"], "actions": buf["actions"], "state_info": state_info,
                "idx": buf["idx"], "window_sizes": buf["sizes"]}

@@ -491,6 +491,34 @@ def r3m_normalize_packed(x, xp, mean3, std3):
     return xp
 
 
+def r3m_stage_u8(frames, y, lut, frame_index=None, aug_shift=None, aug_pad=0):
+    """uint8 NHWC frames (n, H, W, 3) — the batch itself, or the whole episode store with frame_index (N,) int32 — -> the trunk's input y:
+    bf16 (N, H+6, r3m_packed_width(W), 4) (the packed stem input, zero border written) or (N, H, W, 8) bf16 / fp32 (channels 3..7 zero).
+    Value = lut[c][byte], lut (3, 256) of y's dtype; aug_shift (N, 2) int32 {sx, sy} + aug_pad: conv1's shift semantics."""
+    _require_cuda(frames, y, lut, frame_index, aug_shift)
+    _require_contiguous(frames=frames, y=y, lut=lut)
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise TypeError("r3m_stage_u8: frames are uint8 (n, H, W, 3)")
+    n_store, h, w, _ = frames.shape
+    if w % 4:
+        raise ValueError(f"r3m_stage_u8: frame width {w} is not a multiple of 4 (the bytes are fetched as aligned dword windows)")
+    n = y.shape[0]
+    if frame_index is not None and (frame_index.dtype != torch.int32 or not frame_index.is_contiguous() or frame_index.numel() != n):
+        raise TypeError("frame_index must be a contiguous int32 tensor with one store frame number per batch frame")
+    if frame_index is None and n != n_store:
+        raise TypeError(f"r3m_stage_u8: y holds {n} frames, frames {n_store}, and there is no frame_index")
+    if aug_shift is not None and (aug_shift.dtype != torch.int32 or not aug_shift.is_contiguous() or aug_shift.numel() != 2 * n):
+        raise TypeError("aug_shift must be a contiguous int32 (N, 2) tensor of {sx, sy}")
+    packed = y.dtype == torch.bfloat16 and tuple(y.shape) == (n, h + 6, r3m_packed_width(w), 4)
+    if not packed and (tuple(y.shape) != (n, h, w, 8) or y.dtype not in (torch.bfloat16, torch.float32)):
+        raise TypeError("r3m_stage_u8: y is bf16 (N, H+6, packed width, 4) or bf16 / fp32 (N, H, W, 8)")
+    if lut.dtype != y.dtype or tuple(lut.shape) != (3, 256):
+        raise TypeError("r3m_stage_u8: lut is (3, 256) of y's dtype")
+    _call("hulc_r3m_stage_u8", frames, n_store, n, h, w, frame_index, aug_shift, int(aug_pad), lut, y, _dt(y), int(packed),
+          key=("r3m_stage_u8", n, h, w, int(packed)), nbytes=float(n) * h * w * 3 + _nbytes(y))
+    return y
+
+
 def r3m_stem_fwd(xp, w, bias, y, N, H, W, Cout, relu=True):
     """the 7x7 stride-2 stem on the packed input: w bf16 (Cout, 7*8*4) = [o][kh][kw][c] with zeros at kw = 7 and c = 3; y NHWC."""
     _require_contiguous(xp=xp, w=w, y=y)

@@ -54,7 +54,7 @@ class ConcatEncoders(nn.Module):
         """-> (frames flattened over (B, S), shifts flattened or None, store frame numbers or None, B, S).  fp32 (B,S,3,H,W) in [-1,1]
         as the reference's transforms deliver them, or uint8 (B,S,H,W,3) as stored (+ optional imgs[key + "_shift"] (B,S,2) int32
         {sx, sy}), or the whole uint8 episode store (n_frames,H,W,3) with imgs[key + "_index"] (B,S) int32 naming the window frames
-        (hulc2_amd.datasets.DeviceEpisodeStore: nothing is gathered, conv1 reads the store in place)."""
+        (hulc2_amd.datasets.DeviceEpisodeStore: nothing is gathered, conv1 — or VisionR3M's staging kernel — reads the store in place)."""
         x = imgs[key]
         ix = imgs.get(key + "_index")
         if ix is not None:

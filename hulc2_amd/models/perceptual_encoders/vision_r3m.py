@@ -14,6 +14,9 @@ The trunk is frozen: BatchNorm uses its running statistics, folded into the conv
 parameter version, so a layer is one `hulc_conv2d_padded_fwd` launch with ReLU and the residual add in its epilogue.  (The reference leaves
 the trunk's mode to Lightning's `.train()` call, which would make BatchNorm normalise with batch statistics during training — a side
 effect of not calling `.eval()`, not something a frozen backbone is meant to do; this module keeps the frozen semantics in both modes.)
+
+Frames also arrive as stored: uint8 NHWC, or the whole HBM episode store with a row of frame numbers (hulc2_amd.datasets.DeviceEpisodeStore).
+The camera's transforms are then a 256-entry table per channel (`input_chain`, `_byte_lut`) that hulc_r3m_stage_u8 applies while it gathers.
 """
 import os
 from typing import List, Optional, Sequence, Union
@@ -28,6 +31,52 @@ from hulc2_amd import shadow
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
 _STAGES = {"resnet18": (2, 2, 2, 2), "resnet34": (3, 4, 6, 3)}
+
+
+# ---- uint8 frames: what the camera's transforms do to a stored byte --------------------------------------------------------------------
+# Everything between the stored uint8 frame and the trunk's first convolution is pointwise (the integer shift of RandomShiftsAug only moves
+# pixels), so a transform chain is its 256 values — evaluated with the very torch ops of hulc2/utils/transforms.py, then normalised by the same
+# kernel that normalises fp32 frames (_byte_lut).  hulc_r3m_stage_u8 looks the bytes up: bit-identical to the fp32 path by construction.
+def _scale_upscale(x: torch.Tensor) -> torch.Tensor:
+    """conf/datamodule/transforms/real_world_r3m.yaml:2-13: ScaleImageTensor (transforms.py:19), UpScaleImageTensor (transforms.py:33); the
+    identity on all 256 byte values"""
+    return x.float().div(255).float().mul(255)
+
+
+def _scale_normalize(x: torch.Tensor) -> torch.Tensor:
+    """conf/datamodule/transforms/rand_shift.yaml / play_basic.yaml: ScaleImageTensor, torchvision Normalize(mean 0.5, std 0.5)"""
+    return x.float().div(255).sub(0.5).div(0.5)
+
+
+BYTE_CHAINS = {"real_world_r3m": _scale_upscale, "rand_shift": _scale_normalize, "play_basic": _scale_normalize}
+
+
+def byte_chain_values(chain) -> torch.Tensor:
+    """(256,) fp32: what `chain` — a name of BYTE_CHAINS, or a pointwise callable on an fp32 tensor — makes of the byte values 0..255"""
+    if not callable(chain):
+        if chain not in BYTE_CHAINS:
+            raise ValueError(f"unknown input chain {chain!r}: one of {sorted(BYTE_CHAINS)} or a pointwise callable on an fp32 tensor")
+        chain = BYTE_CHAINS[chain]
+    v = chain(torch.arange(256, dtype=torch.float32))
+    if not torch.is_tensor(v) or v.dtype != torch.float32 or tuple(v.shape) != (256,):
+        raise ValueError("an input chain maps an fp32 tensor to an fp32 tensor of the same shape, value by value")
+    return v
+
+
+_byte_luts = {}
+
+
+def _byte_lut(chain, mean, std, dtype: torch.dtype, device) -> torch.Tensor:
+    """(3, 256) `dtype`: lut[c][b] = what hulc_r3m_normalize writes for channel c of a pixel whose chained value is that of byte b"""
+    key = (chain, tuple(float(m) for m in mean), tuple(float(s) for s in std), dtype, device)
+    lut = _byte_luts.get(key)
+    if lut is None:
+        x = byte_chain_values(chain).view(1, 1, 1, 256).expand(1, 3, 1, 256).contiguous().to(device)
+        y = kn.r3m_normalize(x, torch.empty((1, 1, 256, 8), dtype=dtype, device=device), mean, std)
+        lut = y[0, 0, :, :3].t().contiguous()
+        if not torch.cuda.is_current_stream_capturing():     # (memory of a graph's pool must not outlive the graph in the cache)
+            _byte_luts[key] = lut
+    return lut
 
 
 class BasicBlock(nn.Module):
@@ -92,6 +141,10 @@ def _fold(conv: nn.Conv2d, bn: nn.BatchNorm2d, cin_pad: int, wdtype: torch.dtype
 
 
 class VisionR3M(nn.Module):
+    # what the camera's transforms make of a stored byte when uint8 frames are read in place: a name of BYTE_CHAINS or a pointwise callable
+    # on an fp32 tensor (not a constructor argument: the reference's constructor has none, and instantiate() passes its kwargs only)
+    input_chain = "real_world_r3m"
+
     def __init__(self, device: Union[str, torch.device, None], visual_features: int, resnet_model: str = "resnet18",
                  freeze_backbone: bool = True):
         super().__init__()
@@ -210,12 +263,27 @@ class VisionR3M(nn.Module):
 
     # ---- forward -------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def trunk_features(self, x: torch.Tensor, want_maps: bool = False, mean=None, std=None, batch_stats: bool = False):
+    def trunk_features(self, x: torch.Tensor, want_maps: bool = False, mean=None, std=None, batch_stats: bool = False, aug_shift=None,
+                       aug_pad: int = 0, frame_index=None):
         """x (N, 3, H, W) fp32 in [0, 255] -> (N, 512) fp32: normalise, stem, max pool, the residual stages, global average pool.
         want_maps: return the NHWC maps after the stem (+ max pool) and after each of the four stages instead (the skips of the affordance
-        model's U-Net, hulc2/affordance/models/visual_lang_encoders/r3m_rn18.py:71-76); mean / std override the input normalisation."""
-        if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3:
-            raise TypeError("VisionR3M expects fp32 (N, 3, H, W) frames in [0, 255] (conf/datamodule/transforms/real_world_r3m.yaml)")
+        model's U-Net, hulc2/affordance/models/visual_lang_encoders/r3m_rn18.py:71-76); mean / std override the input normalisation.
+        x uint8 (N, H, W, 3) as stored — or the whole episode store (n, H, W, 3) with frame_index (N,) int32 — is read in place: aug_shift
+        (N, 2) int32 {sx, sy} + aug_pad shift a frame as conv1 does (RandomShiftsAug), `input_chain` is what the camera's transforms make of a
+        byte (hulc_r3m_stage_u8); the features are those of the fp32 frames the transforms would have produced, bit for bit."""
+        u8 = x.dtype == torch.uint8
+        if u8:
+            if x.dim() != 4 or x.shape[3] != 3:
+                raise TypeError("VisionR3M reads uint8 frames as stored: (N, H, W, 3)")
+            if batch_stats:
+                raise NotImplementedError("the affordance model's trunk (batch statistics) takes fp32 frames")
+            aug_shift = None if aug_shift is None else aug_shift.reshape(-1, 2).to(torch.int32).contiguous()
+            frame_index = None if frame_index is None else frame_index.reshape(-1).to(torch.int32).contiguous()
+        elif x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3:
+            raise TypeError("VisionR3M expects fp32 (N, 3, H, W) frames in [0, 255] (conf/datamodule/transforms/real_world_r3m.yaml) or "
+                            "uint8 (N, H, W, 3) frames as stored")
+        elif aug_shift is not None or frame_index is not None:
+            raise TypeError("aug_shift / frame_index address uint8 frames; fp32 frames arrive shifted and gathered")
         mean = IMAGENET_MEAN if mean is None else mean
         std = IMAGENET_STD if std is None else std
         if batch_stats:
@@ -225,7 +293,10 @@ class VisionR3M(nn.Module):
             return self._trunk_maps_batch_stats(x, mean, std)
         f = self._fold_trunk()
         adt = torch.bfloat16 if kn.get_compute() == "bf16" else torch.float32
-        n, _, h, w = x.shape
+        if u8:
+            n, h, w = (x.shape[0] if frame_index is None else frame_index.numel()), x.shape[1], x.shape[2]
+        else:
+            n, _, h, w = x.shape
         dev = x.device
 
         def conv(a, wb, hh, ww, cin, k, stride, pad, relu, add=None):
@@ -235,13 +306,19 @@ class VisionR3M(nn.Module):
             kn.conv2d_padded_fwd(a, wb[0], wb[1], y, n, hh, ww, cin, cout, k, k, stride, pad, relu=relu, add=add)
             return y, oh, ow
 
+        def stage(y):
+            """the trunk's input in the layout of y: normalised fp32 frames, or the stored bytes through their table"""
+            if u8:
+                return kn.r3m_stage_u8(x.contiguous(), y, _byte_lut(self.input_chain, mean, std, adt, dev), frame_index, aug_shift, aug_pad)
+            return (kn.r3m_normalize_packed if y.shape[3] == 4 else kn.r3m_normalize)(x.contiguous(), y, mean, std)
+
         if "stem_packed" in f:
-            xp = kn.r3m_normalize_packed(x.contiguous(), torch.empty((n, h + 6, kn.r3m_packed_width(w), 4), dtype=adt, device=dev), mean, std)
+            xp = stage(torch.empty((n, h + 6, kn.r3m_packed_width(w), 4), dtype=adt, device=dev))
             oh, ow = (h - 1) // 2 + 1, (w - 1) // 2 + 1
             a = kn.r3m_stem_fwd(xp, f["stem_packed"][0], f["stem_packed"][1], torch.empty((n, oh, ow, 64), dtype=adt, device=dev), n, h, w, 64)
             h, w = oh, ow
         else:
-            a = kn.r3m_normalize(x.contiguous(), torch.empty((n, h, w, 8), dtype=adt, device=dev), mean, std)
+            a = stage(torch.empty((n, h, w, 8), dtype=adt, device=dev))
             a, h, w = conv(a, f["stem"], h, w, 8, 7, 2, 3, True)
         ph, pw = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
         a = kn.maxpool_nhwc(a, torch.empty((n, ph, pw, 64), dtype=adt, device=dev), n, h, w, 64, 3, 2, 1)
@@ -280,14 +357,13 @@ class VisionR3M(nn.Module):
         return feat
 
     def forward(self, x: Union[torch.Tensor, Sequence[torch.Tensor]], aug_shift=None, aug_pad: int = 0, frame_index=None) -> torch.Tensor:
-        """x: (N, 3, H, W) fp32 in [0, 255], or one such tensor per modality of a step (rows of the result modality-major).  The real-world
-        transforms apply no shift augmentation to this camera, and the uint8 episode-store path belongs to the from-scratch CNN."""
+        """x: (N, 3, H, W) fp32 in [0, 255], or uint8 (N, H, W, 3) frames as stored (+ aug_shift (N, 2) int32, aug_pad), or the whole uint8
+        episode store with frame_index (N,) int32 (hulc2_amd.datasets.DeviceEpisodeStore: nothing is gathered) — or one of each per modality
+        of a step (rows of the result modality-major): the calling convention of ConcatEncoders.  uint8 bytes go through `input_chain`."""
         xs = list(x) if isinstance(x, (list, tuple)) else [x]
-        for opt in (aug_shift, frame_index):
-            if opt is not None and any(o is not None for o in (opt if isinstance(opt, (list, tuple)) else [opt])):
-                raise NotImplementedError("VisionR3M takes fp32 frames in [0, 255]; shift augmentation / episode-store indices are not part "
-                                          "of the real-world static-camera transforms (conf/datamodule/transforms/real_world_r3m.yaml:2-13)")
-        feat = [self.trunk_features(t) for t in xs]
+        sh = list(aug_shift) if isinstance(aug_shift, (list, tuple)) else [aug_shift] * len(xs)
+        ix = list(frame_index) if isinstance(frame_index, (list, tuple)) else [frame_index] * len(xs)
+        feat = [self.trunk_features(t, aug_shift=s, aug_pad=aug_pad, frame_index=i) for t, s, i in zip(xs, sh, ix)]
         feat = feat[0] if len(feat) == 1 else torch.cat(feat, dim=0)
         return HF.mlp(feat, [(self.fc1.weight, self.fc1.bias, True), (self.fc2.weight, self.fc2.bias, False)])
 

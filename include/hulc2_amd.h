@@ -398,6 +398,14 @@ int hulc_nhwc_scatter(const void* x, int dtype, int N, int H, int W, int C, int 
 int hulc_r3m_packed_width(int W);
 int hulc_r3m_normalize_packed(const float* x, int N, int H, int W, const float* mean3, const float* std3, void* xp, void* stream);
 int hulc_r3m_stem_fwd(const void* xp, const void* w, const float* bias, void* y, int y_dtype, int N, int H, int W, int Cout, int relu, void* stream);
+/* The trunk's input straight from the uint8 NHWC episode store frames [n_store][H][W][3] (hulc2_amd.datasets.DeviceEpisodeStore): batch frame
+ * n is store frame frame_index[n] (NULL: frame n), output pixel (y, x) = source pixel (clamp(y + sy - pad, 0, H - 1), clamp(x + sx - pad, 0,
+ * W - 1)) with shift [N][2] = {sx, sy} (NULL: no shift) — conv1's RandomShiftsAug semantics — and every value is lut[c][byte], lut [3][256]
+ * of y_dtype: the camera's pointwise transforms and the normalisation tabulated per byte, which makes the result bit-identical to
+ * hulc_r3m_normalize[_packed] on the fp32 frames.  packed != 0: y = the packed stem input (bf16, [N][H+6][hulc_r3m_packed_width(W)][4], zero
+ * border written); else y NHWC [N][H][W][8] bf16 or fp32, channels 3..7 zero.  W a multiple of 4; no load leaves the store. */
+int hulc_r3m_stage_u8(const unsigned char* frames, long n_store, int N, int H, int W, const int* frame_index, const int* shift, int pad,
+                      const void* lut, void* y, int y_dtype, int packed, void* stream);
 
 /* ---- transformer feed-forward block, fused (bf16 compute) ----------------------------------------------- */
 /* f = relu(x W1^T + b1) [dropout] W2^T + b2 of nn.TransformerEncoderLayer (plan_recognition_net.py:108-117), d_model 128,
