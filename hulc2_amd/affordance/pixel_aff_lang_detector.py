@@ -16,13 +16,12 @@ STEM trains: the reference's freeze leaves `conv1.weight`, `bn1.weight`, `bn1.bi
 through the whole frozen ResNet (affordance/trunk.py: one autograd node, hulc_nhwc_bn_train_bwd / zero-inserted data-gradient convolutions /
 hulc_maxpool_nhwc_bwd / a 7 x 7 weight gradient).  "frozen" stays what it says: no trunk parameter receives a gradient.  Third-party arithmetic (r3m weights, sentence-transformers) is absent: parity of
 the trunk and of SBERT is unpinned; everything behind them is pinned on the reference's own modules."""
-import os
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 import torch.nn as nn
 
-from .. import functional as HF, kernels as kn
+from .. import functional as HF, kernels as kn, switches
 from ..models.language_encoders.sbert_lang_encoder import SBertLang
 from ..models.perceptual_encoders.vision_r3m import R3M
 from .functional import DECODER_CHANNELS, AffDecoderLossFn, DepthNllFn, block_channels
@@ -123,7 +122,7 @@ class PixelAffLangDetector(nn.Module):
         r3m = self.model.aff_stream.r3m
         net = r3m.convnet
         if (self.trunk_mode == "reference" and self.training and torch.is_grad_enabled() and net.conv1.weight.requires_grad
-                and not os.environ.get("HULC_AFF_FROZEN_STEM")):
+                and not switches.on("AFF_FROZEN_STEM")):
             from .trunk import TrunkStemFn
             return list(TrunkStemFn.apply(img, net.conv1.weight, net.bn1.weight, net.bn1.bias, _trunk_of(r3m)))
         with torch.no_grad():

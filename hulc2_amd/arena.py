@@ -10,7 +10,6 @@ Two halves:
 from types import SimpleNamespace
 from typing import List, Optional, Tuple
 
-import os
 import weakref
 
 import numpy as np
@@ -19,6 +18,7 @@ import torch
 from . import gradsink
 from . import kernels as kn
 from . import shadow
+from . import switches
 
 MAX_KERNEL_RANGES = 8              # element ranges an optimizer kernel takes (remainder ranges, skip ranges)
 
@@ -350,7 +350,7 @@ class WeightKeeper:
     def _zero_arena(self) -> None:
         """what a backward pass needs of the gradient arena before it starts: everything zeroed (first pass: sinks accumulate) or only the slices
         autograd accumulates into (later passes: the first sink writer of a slice overwrites it)"""
-        if self._zero_ranges is None or os.environ.get("HULC_FULL_ZERO_GRAD"):
+        if self._zero_ranges is None or switches.on("FULL_ZERO_GRAD"):
             self.flat_g.zero_()
             gradsink.begin_step(False)
         else:
@@ -360,7 +360,7 @@ class WeightKeeper:
 
     def _settle_sinks(self) -> None:
         """bookkeeping behind a finished backward pass: the first (fully zeroed) pass makes the zeroing plan; later passes clean up after it"""
-        if self._zero_ranges is None and gradsink._sinks and not os.environ.get("HULC_FULL_ZERO_GRAD"):
+        if self._zero_ranges is None and gradsink._sinks and not switches.on("FULL_ZERO_GRAD"):
             self._plan_partial_zero()                              # the backward that just finished ran on a fully zeroed arena
         elif self._zero_ranges is not None:
             # a sink the plan expects to be overwritten was not written by this backward (a branch of the model did not run): its slice

@@ -8,12 +8,12 @@ reference's nn.Linear / nn.Conv2d / nn.RNN layouts so state_dicts interchange.
 """
 from typing import List, Optional, Sequence, Tuple
 
-import os
 
 import torch
 
 from . import gradsink
 from . import kernels as kn
+from . import switches
 from .shadow import weight_operand
 
 
@@ -384,7 +384,7 @@ def _conv1_pair_ok(xs, u8, bits, cout, shifts=None, indices=None) -> bool:
     slices are one contiguous tensor"""
     if len(xs) != 2 or xs[0].dtype != xs[1].dtype or xs[0].shape[1:] != xs[1].shape[1:] or not (xs[0].is_contiguous() and xs[1].is_contiguous()):
         return False
-    if cout != 32 or kn.base_mode() == "fp32" or kn.get_compute() != "bf16" or os.environ.get("HULC_CONV1_PER_INPUT"):
+    if cout != 32 or kn.base_mode() == "fp32" or kn.get_compute() != "bf16" or switches.on("CONV1_PER_INPUT"):
         return False
     if u8:
         H, W = xs[0].shape[1], xs[0].shape[2]
@@ -1053,12 +1053,12 @@ class TxlLayerFn(torch.autograd.Function):
 
 def _txl_fused_ok(x, p: dict, S: int, nhead: int) -> bool:
     return (kn.get_compute() == "bf16" and x.shape[-1] == 128 and nhead == 8 and 1 <= S <= 32 and p["linear1.weight"].shape[0] % 128 == 0
-            and x.dtype == torch.float32 and not os.environ.get("HULC_NO_FUSED_TXL") and not os.environ.get("HULC_NO_FUSED_FFN"))
+            and x.dtype == torch.float32 and not switches.on("NO_FUSED_TXL") and not switches.on("NO_FUSED_FFN"))
 
 
 def _ffn_fused_ok(x, W1) -> bool:
     return (kn.get_compute() == "bf16" and x.shape[-1] == 128 and W1.shape[0] % 128 == 0 and x.dtype == torch.float32
-            and not os.environ.get("HULC_NO_FUSED_FFN"))
+            and not switches.on("NO_FUSED_FFN"))
 
 
 def transformer_encoder_layer(x, p: dict, B: int, S: int, nhead: int, drop_p: float, seed: int):
@@ -1191,7 +1191,7 @@ def txl_block_ok(emb, layer_params, S: int, nhead: int) -> bool:
     return (emb.is_cuda and kn.get_compute() == "bf16" and kn.base_mode() == "bf16"
             and emb.shape[-1] == 128 and nhead == 8 and 1 <= S <= 32 and 1 <= len(layer_params) <= 4 and emb.dtype == torch.float32
             and p0["linear1.weight"].shape[0] % 128 == 0 and all(p["linear1.weight"].shape == p0["linear1.weight"].shape for p in layer_params)
-            and not os.environ.get("HULC_NO_TXL_BLOCK") and not os.environ.get("HULC_NO_FUSED_TXL") and not os.environ.get("HULC_NO_FUSED_FFN"))
+            and not switches.on("NO_TXL_BLOCK") and not switches.on("NO_FUSED_TXL") and not switches.on("NO_FUSED_FFN"))
 
 
 def transformer_trunk_pooled(emb, pos, pos_ids, layer_params, nhead: int, drop_p: float, seed: int):
@@ -1211,7 +1211,7 @@ def _rnn_persistent(B: int, Hd: int, device) -> bool:
     return (kn.get_compute() == "bf16" and Hd == 2048 and B <= 64
             and kn.device_cu_count(device) >= 256
             and not kn.concurrent_streams()          # its device-wide barrier needs the GPU to itself (kernels.set_concurrent_streams)
-            and not os.environ.get("HULC_NO_RNN_WAVEFRONT"))
+            and not switches.on("NO_RNN_WAVEFRONT"))
 
 
 def _decoder_rnn_forward(plan, emb, goal, lo: int, hi: int, w_ih0, w_hh0, b_ih0, b_hh0, w_ih1, w_hh1, b_ih1, b_hh1, h0, emb_tm: bool = False):
@@ -1258,7 +1258,7 @@ def _decoder_rnn_forward(plan, emb, goal, lo: int, hi: int, w_ih0, w_hh0, b_ih0,
         # both layers, all S steps: one persistent kernel with register-resident weights (csrc/rnn_wavefront.hip)
         z16 = kn.rnn_wavefront(zbuf[0], B * 2 * Hd, S, B, Hd, whh0, weight_operand(w_ih1), weight_operand(w_hh1), False,
                                add1=pre0, add1_step=B * Hd, ld_add1=Hd, bias1=(b_hh0, None), bias2=(b_ih1, b_hh1), relu=True,
-                               mirror_t=bool(os.environ.get("HULC_RNN_WGRAD_TMIRROR")), add1c=c, zero_edges=True)
+                               mirror_t=switches.on("RNN_WGRAD_TMIRROR"), add1c=c, zero_edges=True)
         return zbuf, plan, emb_t, goal, z16, meta
     w1cat = weight_operand(torch.cat([w_ih1.detach(), w_hh1.detach()], dim=1))   # (H, 2H) = [W_ih1 | W_hh1]
     for t in range(S):
@@ -1328,7 +1328,7 @@ class DecoderRNNFn(torch.autograd.Function):
                                    add1=dH1_t[S - 1], add1_step=-B * Hd, ld_add1=Hd,
                                    mask1=zbuf[S + 1][:, Hd:], mask1_step=-B * 2 * Hd, ld_mask1=2 * Hd,
                                    mask2=zbuf[S + 1][:, :Hd], mask2_step=-B * 2 * Hd, ld_mask2=2 * Hd,
-                                   mirror_t=bool(os.environ.get("HULC_RNN_WGRAD_TMIRROR")), zero_edges=True)
+                                   mirror_t=switches.on("RNN_WGRAD_TMIRROR"), zero_edges=True)
         else:
             whh1_t = weight_operand(w_hh1, "t")
             wb0 = weight_operand(torch.cat([w_ih1.detach().t(), w_hh0.detach().t()], dim=1))   # (H, 2H) = [W_ih1^T | W_hh0^T]

@@ -8,6 +8,7 @@ import ctypes
 import torch
 
 from . import lib as _L
+from . import switches
 
 F32, BF16, F16 = (_L.DEFINES["HULC_" + n] for n in ("F32", "BF16", "F16"))      # the header's dtype codes
 _COMPUTE = {"bf16": BF16, "fp32": F32, "f32": F32}
@@ -86,8 +87,7 @@ def fp32_sites() -> frozenset:
     softmax: + 0.01-0.03 ms per step, the embeddings' maximum error does not move);
     `head,goal,encfc`: 13 % / 8.0 % for +0.09 ms; `head` alone: 23 % / 13 % at no cost; `head,goal,encfc,txl,conv1,a3`: median
     0.84 % (worst 10 %: the conv stacks' own parameters) for +0.45 ms."""
-    import os
-    v = os.environ.get("HULC_FP32_SITES", "head,goal,encfc,txl")
+    v = switches.value("FP32_SITES")
     sites = frozenset(x for x in v.replace(" ", "").split(",") if x and x != "none")
     unknown = sites - _KNOWN_SITES
     if unknown:
@@ -105,8 +105,7 @@ def site_scope(site: str):
         if site in fp32_sites() or _base_mode == "mixed":
             # forward only: rounding in the BACKWARD products moves no gradient of this model by more than 1 % (tools/study/bf16_emulation.py,
             # `only_bwd`), and the backward then stays on the grouped / chained bf16 launches.  HULC_FP32_SITES_BWD=1: both directions.
-            import os
-            return compute_scope("fp32", fwd_only=not os.environ.get("HULC_FP32_SITES_BWD"))
+            return compute_scope("fp32", fwd_only=not switches.on("FP32_SITES_BWD"))
     return compute_scope(get_compute(), fwd_only=_bwd_mode is not None)
 
 
@@ -778,8 +777,7 @@ class no_gc:
 
 def fork_branches() -> bool:
     """run the prior and the posterior branch of a step on two streams (HULC_FORK=0: one after the other, as until round 5)"""
-    import os
-    return os.environ.get("HULC_FORK", "1") != "0" and not concurrent_streams() and _timing is None
+    return switches.on("FORK") and not concurrent_streams() and _timing is None
 
 
 _wgrad_branch = False
@@ -798,8 +796,7 @@ class wgrad_branch_scope:
 
 
 def wgrad_branch_ok() -> bool:
-    import os
-    return _wgrad_branch and os.environ.get("HULC_WGRAD_FORK", "0") not in ("", "0")
+    return _wgrad_branch and switches.on("WGRAD_FORK")
 
 
 def branch_stream(device, which: int = 0):
@@ -858,8 +855,7 @@ def gemm_fuses_rowsum(M: int, a_kmajor: bool) -> bool:
 def mlp_chain_ok(M: int, K0: int, widths, device, share=None) -> bool:
     """shapes hulc_mlp_chain takes (include/hulc2_amd.h) on a whole MI355X with nothing else sharing the GPU — or, under a coop share of n, on
     1 / n of it: a layer of N columns needs N / 16 workgroups"""
-    import os
-    if os.environ.get("HULC_NO_MLP_CHAIN") or _compute_mode != BF16 or concurrent_streams() or device_cu_count(device) < 256:
+    if switches.on("NO_MLP_CHAIN") or _compute_mode != BF16 or concurrent_streams() or device_cu_count(device) < 256:
         return False
     if not (1 <= M <= 64) or not (1 <= len(widths) <= 8):
         return False
@@ -1153,10 +1149,9 @@ def exact_site_in_bf16_step() -> bool:
 
 def mlp2_rows_ok(x, W1, W2) -> bool:
     """shapes hulc_mlp2_rows_* take (include/hulc2_amd.h): the camera encoders' fc1 -> ReLU -> fc2 head"""
-    import os
     H, K = W1.shape
     OUT = W2.shape[0]
-    return ((_compute_mode == BF16 or exact_site_in_bf16_step()) and not os.environ.get("HULC_NO_MLP2_ROWS") and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32
+    return ((_compute_mode == BF16 or exact_site_in_bf16_step()) and not switches.on("NO_MLP2_ROWS") and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32
             and x.is_contiguous() and K == 128 and x.shape[1] == 128 and H % 128 == 0 and OUT % 32 == 0 and 32 <= OUT <= 128 and W2.shape[1] == H
             and x.data_ptr() % 16 == 0)
 
@@ -1187,8 +1182,7 @@ def txl_block_desc(emb, pos, pos_ids, B, S, H, FF, drop_p, seed_pos, eps, layers
     d.emb, d.pos, d.pos_ids = emb.data_ptr(), pos.data_ptr(), pos_ids.data_ptr()
     d.pooled, d.dpooled, d.demb = [t.data_ptr() if t is not None else None for t in (pooled, dpooled, demb)]
     # sequences shared between workgroups (csrc/txl_block.hip) only on a whole MI355X with the stream to itself, like the chain kernels
-    import os
-    d.exclusive = int(not concurrent_streams() and not os.environ.get("HULC_TXL_NO_SHARE"))
+    d.exclusive = int(not concurrent_streams() and not switches.on("TXL_NO_SHARE"))
     d.coop_share = int(_coop_share if share is None else share)
     if d.exclusive:
         need = _L.load().hulc_txl_block_workspace(B, len(layers))
@@ -1258,8 +1252,8 @@ def rnn_wavefront(z0, z_step, S, B, H, wA, wB1, wB2, transposed, add1=None, add1
                   mask1=None, mask1_step=0, ld_mask1=0, mask2=None, mask2_step=0, ld_mask2=0, relu=False, mirror_t=False, add1c=None, zero_edges=False):
     """Both RNN layers of one direction as one persistent kernel (csrc/rnn_wavefront.hip).  z0: view of the (zero) state row
     wave step 0 reads; rows advance by z_step elements.  Weights are bf16 (H, H) matrices, `transposed` applies to all three
-    (or is a 3-tuple, one flag for each of wA, wB1, wB2).  HULC_RNN_DBG with bit 4 set (tests of the fault path, through a child process's
-    environment): the launch ends as if a barrier had timed out (hulc_rnn_wave_desc.inject_timeout)."""
+    (or is a 3-tuple, one flag for each of wA, wB1, wB2).  HULC_RNN_DBG with bit 4 set (tests of the fault path, also handed to a child
+    process): the launch ends as if a barrier had timed out (hulc_rnn_wave_desc.inject_timeout)."""
     for w in (wA, wB1, wB2):
         if w.dtype != torch.bfloat16:
             raise _L.HulcKernelError("rnn_wavefront: weights must be bf16 shadows (bf16 compute mode)")
@@ -1282,9 +1276,7 @@ def rnn_wavefront(z0, z_step, S, B, H, wA, wB1, wB2, transposed, add1=None, add1
     d.err_sticky = fault_word(z0.device).data_ptr()
     d.add1c, d.ld_add1c = (add1c.data_ptr(), add1c.stride(0)) if add1c is not None else (None, 0)
     d.zero_edges = int(bool(zero_edges))
-    import os
-    dbg = os.environ.get("HULC_RNN_DBG", "")
-    d.inject_timeout = int(dbg) & 4 if dbg.isdigit() else 0
+    d.inject_timeout = switches.value("RNN_DBG") & 4
     lib = _L.load()
     ws = _ws(lib.hulc_rnn_wavefront_workspace(S, B, H), z0.device)
     # algorithmic work: S wave steps of a (B x 2H) x (2H x 2H) product with one H x H block structurally zero; bytes: the

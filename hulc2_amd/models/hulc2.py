@@ -18,13 +18,13 @@ import logging
 from typing import Dict, Optional, Tuple
 
 import numpy as np
-import os
 
 import torch
 import torch.nn as nn
 
 from hulc2_amd import functional as HF
 from hulc2_amd import kernels as kn
+from hulc2_amd import switches
 from hulc2_amd.arena import WeightKeeper
 from hulc2_amd.compat import LightningModule, instantiate
 from hulc2_amd.models.plan_encoders.plan_recognition_net import trunk_site
@@ -112,7 +112,7 @@ class Hulc2(LightningModule):
         cfg = self.optimizer_config
         tgt = cfg.get("_target_") if hasattr(cfg, "get") else None
         drop_in = {"torch.optim.Adam": "Adam", "torch.optim.AdamW": "AdamW", "torch.optim.SGD": "SGD"}
-        if tgt in drop_in and not os.environ.get("HULC_TORCH_ADAM"):
+        if tgt in drop_in and not switches.on("TORCH_ADAM"):
             # round 6: the unchanged conf/model/optimizer/adam.yaml gets the drop-in SUBCLASS (hulc2_amd/optim.py): same update rule, same
             # hyper-parameters, same state_dict layout (checkpoints interchange), isinstance(opt, torch.optim.Adam) holds; its step is one
             # launch of the arena kernel on the step node's gradient arena and takes a GradScaler's device scalars without a host
@@ -192,7 +192,7 @@ class Hulc2(LightningModule):
         launches whenever the optimizer has stepped.  bf16 arithmetic modes only; HULC_NO_AUTO_SHADOWS=1 keeps the lazy per-parameter path.
         Round 5: the keeper also owns the gradient arena of the step node (hulc2_amd/stepnode.py; HULC_NO_STEP_NODE=1: weight copies only).
         Returns the keeper when it is this model's (else None: a full ArenaTrainer drives the step, or the lazy path is selected)."""
-        if kn.base_mode() == "fp32" or os.environ.get("HULC_NO_AUTO_SHADOWS"):
+        if kn.base_mode() == "fp32" or switches.on("NO_AUTO_SHADOWS"):
             return None
         ref = self.__dict__.get("_hulc_arena_trainer")
         tr = ref() if ref is not None else None
@@ -200,7 +200,7 @@ class Hulc2(LightningModule):
             tr = None
         if tr is None:
             # the model owns its keeper (a deepcopy of the model gets None here and builds its own)
-            tr = self.__dict__["_hulc_shadow_keeper"] = WeightKeeper(self, step_node=not os.environ.get("HULC_NO_STEP_NODE"))
+            tr = self.__dict__["_hulc_shadow_keeper"] = WeightKeeper(self, step_node=not switches.on("NO_STEP_NODE"))
         if not isinstance(tr, ArenaTrainer):
             tr.refresh_if_stale()
             return tr
@@ -422,8 +422,7 @@ class Hulc2(LightningModule):
     @staticmethod
     def _batchable(mods) -> bool:
         """all modalities carry the same cameras and tensor shapes (the CALVIN vis/lang batches do)"""
-        import os
-        if len(mods) < 2 or os.environ.get("HULC_NO_MODALITY_BATCHING"):
+        if len(mods) < 2 or switches.on("NO_MODALITY_BATCHING"):
             return False
         ref = mods[0][1]
         for _, db in mods[1:]:

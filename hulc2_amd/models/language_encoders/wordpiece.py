@@ -25,6 +25,8 @@ from typing import Dict, Iterable, List, Optional, Sequence
 
 import torch
 
+from hulc2_amd import switches
+
 _SPECIALS = ("[PAD]", "[UNK]", "[CLS]", "[SEP]", "[MASK]")
 # Unicode White_Space beyond \t \n \r and " " (what Rust's char::is_whitespace accepts)
 _WS = {0x0B, 0x0C, 0x85, 0xA0, 0x1680, 0x2028, 0x2029, 0x202F, 0x205F, 0x3000, *range(0x2000, 0x200B)}
@@ -184,7 +186,7 @@ class WordPieceTokenizer:
 def find_checkpoint_dir(nlp_model: str) -> Optional[str]:
     """where the sentence encoder's files live: `nlp_model` itself when it is a directory, $HULC2_SBERT_DIR, or the sentence-transformers /
     huggingface cache entries of that model name — never a download"""
-    cands = [nlp_model, os.environ.get("HULC2_SBERT_DIR", "")]
+    cands = [nlp_model, switches.value("SBERT_DIR")]
     home = os.path.expanduser("~")
     cands += [os.path.join(home, ".cache", "torch", "sentence_transformers", f"sentence-transformers_{nlp_model}")]
     hub = os.path.join(os.environ.get("HF_HOME", os.path.join(home, ".cache", "huggingface")), "hub",

@@ -5,11 +5,11 @@ for the configured cameras: rgb_static + rgb_gripper, proprio/depth/tactile: non
 """
 from typing import Dict, Optional
 
-import os
 
 import torch
 import torch.nn as nn
 
+from hulc2_amd import switches
 from hulc2_amd.compat import instantiate
 
 
@@ -102,7 +102,7 @@ class ConcatEncoders(nn.Module):
         # workgroups) and leave most of the chip idle.  On a second stream they fill the tails of the static camera's launches — forward here,
         # and backward too (autograd runs a node on the stream of its forward).  The streams join before the embedding is used, so the
         # device-wide-barrier kernels further down (recurrent sweep, MLP chains) still have the GPU to themselves.  HULC_ENC_STREAMS=0: one stream.
-        two = has_gripper and fr[0][0].is_cuda and os.environ.get("HULC_ENC_STREAMS", "1") != "0"
+        two = has_gripper and fr[0][0].is_cuda and switches.on("ENC_STREAMS")
         if two:
             cur = torch.cuda.current_stream(fr[0][0].device)
             side = _encoder_side_stream(fr[0][0].device)

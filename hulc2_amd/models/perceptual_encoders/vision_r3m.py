@@ -8,7 +8,7 @@ What the trunk computes comes from `r3m`, an un-vendored submodule with download
 its public definition: obs / 255 -> Normalize(ImageNet mean, std) -> torchvision resnet18 (or 34) with fc = Identity, i.e. a (N, 512)
 feature; `self.r3m(x)` is called with the default obs_shape, so there is no resize / centre crop.  Without network access the constructor
 cannot download the weights: the trunk starts from torchvision's initialisation and takes its values from a checkpoint
-(`load_state_dict`) or from an r3m `model.pt` (`load_r3m_checkpoint`, or the HULC2_R3M_WEIGHTS environment variable).
+(`load_state_dict`) or from an r3m `model.pt` (`load_r3m_checkpoint`, or the path in $HULC2_R3M_WEIGHTS).
 
 The trunk is frozen: BatchNorm uses its running statistics, folded into the convolution weights (scale) and bias (shift) once per
 parameter version, so a layer is one `hulc_conv2d_padded_fwd` launch with ReLU and the residual add in its epilogue.  (The reference leaves
@@ -18,7 +18,6 @@ effect of not calling `.eval()`, not something a frozen backbone is meant to do;
 Frames also arrive as stored: uint8 NHWC, or the whole HBM episode store with a row of frame numbers (hulc2_amd.datasets.DeviceEpisodeStore).
 The camera's transforms are then a 256-entry table per channel (`input_chain`, `_byte_lut`) that hulc_r3m_stage_u8 applies while it gathers.
 """
-import os
 from typing import List, Optional, Sequence, Union
 
 import torch
@@ -27,6 +26,7 @@ import torch.nn as nn
 from hulc2_amd import functional as HF
 from hulc2_amd import kernels as kn
 from hulc2_amd import shadow
+from hulc2_amd import switches
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -160,7 +160,7 @@ class VisionR3M(nn.Module):
         self.fc2 = nn.Linear(256, visual_features)
         self._folded = None
         self._folded_key = None
-        path = os.environ.get("HULC2_R3M_WEIGHTS")
+        path = switches.value("R3M_WEIGHTS")
         if path:
             self.load_r3m_checkpoint(path)
 
@@ -328,7 +328,7 @@ class VisionR3M(nn.Module):
         # a stage's first block (stride 2 + 1 x 1 shortcut) stays on the gather kernel and its outputs are put on the grid.  OFF by default —
         # measured twice: the gather kernel is the faster one at the trunk's channel counts (1024 frames of 150 x 200: 64 -> 64 at 38 x 50
         # 287 TFLOP/s on the grid against ~450 gathered, whole step 19.4 vs 12.9 ms; 32 images of 224 x 224: 5.03 vs 4.99 ms).
-        on_grid = adt == torch.bfloat16 and os.environ.get("HULC_TRUNK_GRID", "0") == "1"
+        on_grid = adt == torch.bfloat16 and switches.on("TRUNK_GRID")
         ag = kn.grid_from_nhwc(a) if on_grid else None
         for bi, (c1, c2, ds, stride) in enumerate(f["blocks"]):
             if on_grid:

@@ -25,7 +25,6 @@ Gradients still attached when backward runs (accumulation over several calls, `z
 graphs and come out as old + new (_take_live_grads); the capturing call puts back the gradient arena its warm-up overwrote (_capture).
 HULC_NO_STEP_NODE=1 keeps round 4's loop, HULC_NO_STEP_GRAPH=1 the eager node.
 """
-import os
 import warnings
 from typing import List, Optional, Tuple
 
@@ -34,6 +33,7 @@ import torch
 from . import gradsink
 from . import kernels as kn
 from . import shadow
+from . import switches
 
 
 def _rebuild(obj, it):
@@ -125,7 +125,7 @@ class StepNode:
         self.static_outs: List[Optional[torch.Tensor]] = []
         self.static_leaves: List[torch.Tensor] = []
         self.static_logs = []
-        self.disabled: Optional[str] = "HULC_NO_STEP_GRAPH" if os.environ.get("HULC_NO_STEP_GRAPH") else None
+        self.disabled: Optional[str] = switches.entry("NO_STEP_GRAPH").name if switches.on("NO_STEP_GRAPH") else None
         self.replays = self.eager_steps = self.captures = self.input_copies = self.accum_steps = self.zeroed_steps = self.evictions = 0      # (tests / bench read these)
         self._seen = {}                        # signature -> eager-node steps taken (a loop that alternates layouts still reaches its captures)
         # frame slots (hulc_conv_desc.x_slot): the big frame tensors are read by conv1's captured launches through device pointer slots
@@ -184,7 +184,7 @@ class StepNode:
         # set_kl_beta costs at most one recapture, later ones none
         kl_beta = "device" if getattr(m, "kl_beta_on_device", False) else float(m.kl_beta)
         return (tuple((path, tuple(t.shape), t.dtype, t.device) for path, t in leaves), kn.base_mode(), kn.get_compute(),
-                os.environ.get("HULC_FP32_SITES"), kn.concurrent_streams(), kn.fork_branches(), kl_beta, float(m.kl_balancing_mix),
+                switches.graph_key(), kn.concurrent_streams(), kn.fork_branches(), kl_beta, float(m.kl_balancing_mix),
                 float(m.clip_auxiliary_loss_beta), bool(m.use_clip_auxiliary_loss))
 
     def usable(self) -> bool:
@@ -451,7 +451,7 @@ class StepNode:
         words = kn.step_state(dev).clone()
         one = torch.ones((), dtype=torch.float32, device=dev)
         # frame slots: which of the batch's tensors would conv1's band launches read through device pointer slots?  (recorded by the warm-up)
-        want_slots = kn.base_mode() == "bf16" and not os.environ.get("HULC_NO_FRAME_SLOTS")
+        want_slots = kn.base_mode() == "bf16" and not switches.on("NO_FRAME_SLOTS")
         cand = {t.data_ptr(): i for i, t in enumerate(leaves)
                 if want_slots and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() >= 4 and t.numel() >= (1 << 18)
                 and t.data_ptr() % 16 == 0}

@@ -19,7 +19,6 @@ from typing import Dict, List, Optional
 import contextlib
 import copy
 import ctypes
-import os
 
 import torch
 import torch.distributed as dist
@@ -27,6 +26,7 @@ import torch.distributed as dist
 from . import gradsink
 from . import kernels as kn
 from . import shadow
+from . import switches
 from .arena import MAX_KERNEL_RANGES, WeightKeeper, plan_arena, span_ranges
 
 
@@ -58,8 +58,8 @@ class GradComm:
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.active = self.world > 1 or (force and dist.is_initialized())
-        self.algo = algo or os.environ.get("HULC_ALLREDUCE", "auto")
-        self.payload = payload or os.environ.get("HULC_GRAD_PAYLOAD") or self.default_payload(self.world)
+        self.algo = algo or switches.value("ALLREDUCE") or "auto"
+        self.payload = payload or switches.value("GRAD_PAYLOAD") or self.default_payload(self.world)
         if self.algo not in ("ring", "direct", "auto") or self.payload not in ("fp32", "bf16"):
             raise ValueError(f"gradient all-reduce: algo {self.algo!r} (ring | direct | auto), payload {self.payload!r} (fp32 | bf16)")
         self.flat_grad = flat_grad
@@ -361,6 +361,7 @@ class ArenaTrainer(WeightKeeper):
             self._acc_hooks = [p.register_post_accumulate_grad_hook(self._saw_autograd_grad) for p in self.params]
         self._clip_out = torch.zeros(2, dtype=torch.float32, device=dev)      # {gradient norm, clip coefficient} of the last norm pass
         self.step_count = 0
+        self._fault_every = switches.value("FAULT_CHECK_EVERY")
         if dev.type == "cuda":
             kn.step_state(dev)[1] = 0               # the device-resident Adam step count starts with this trainer (the RNG word keeps walking)
         self.graph_fb = self.graph_enc = self.graph_opt = None
@@ -465,7 +466,7 @@ class ArenaTrainer(WeightKeeper):
                           momentum=hp.get("momentum", self.momentum), dampening=hp.get("dampening", self.dampening),
                           nesterov=hp.get("nesterov", self.nesterov))
         algo = (sd.get("comm") or {}).get("algo")
-        if algo in ("ring", "direct") and self.comm is not None and self.comm.active and not os.environ.get("HULC_ALLREDUCE"):
+        if algo in ("ring", "direct") and self.comm is not None and self.comm.active and not switches.value("ALLREDUCE"):
             self.comm.pin(algo)                                   # a resumed run keeps the summation order it started with
         if self.dev.type == "cuda":
             kn.reset_step_state(self.dev, seed=int(sd["rng_word"]), step=int(sd.get("device_step", sd["step"])))
@@ -828,7 +829,6 @@ class ArenaTrainer(WeightKeeper):
             self._poll_faults()
         return loss
 
-    _fault_every = int(os.environ.get("HULC_FAULT_CHECK_EVERY", "64"))
     _since_check = 0
 
     def _poll_faults(self) -> None:
@@ -865,10 +865,10 @@ class ArenaTrainer(WeightKeeper):
         torch.cuda.synchronize()
         self.graph_fb = torch.cuda.CUDAGraph()
         # world > 1: the process group's watchdog thread may touch the runtime while this thread captures; only this thread's calls are policed
-        mode = {"capture_error_mode": os.environ.get("HULC_CAPTURE_MODE", "thread_local")} if self.multi else {}
+        mode = {"capture_error_mode": switches.value("CAPTURE_MODE")} if self.multi else {}
         self.graph_opt = torch.cuda.CUDAGraph()
         with kn.no_gc():                             # (no garbage collection inside a capture: see kernels.no_gc)
-            if self.multi and self.enc_hi > self.enc_lo and not os.environ.get("HULC_NO_SPLIT_GRAPH"):
+            if self.multi and self.enc_hi > self.enc_lo and not switches.on("NO_SPLIT_GRAPH"):
                 # two graphs around the split point; replay() launches the big all-reduce between them on the comm stream
                 with torch.cuda.graph(self.graph_fb, stream=side, **mode):
                     self.static_loss = self._forward_backward_head(batch, 0)

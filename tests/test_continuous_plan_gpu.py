@@ -7,7 +7,6 @@ The oracle does not know this mode: the float64 restatements below are built on 
 The cases that capture graphs run in a child process each (`_in_child`, as in tests/test_lr_schedule_gpu.py): graph launches of this HIP
 runtime have died depending on how many captures the process had made before, and the step-node tests that follow in the suite's process
 should see the same number of earlier captures with or without this file."""
-import os
 import subprocess
 import sys
 from pathlib import Path
@@ -23,7 +22,7 @@ sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tools"))
 pytestmark = pytest.mark.gpu
 
-from hulc2_amd import kernels as kn, synthetic as syn  # noqa: E402
+from hulc2_amd import kernels as kn, switches, synthetic as syn  # noqa: E402
 from hulc2_amd.compat import instantiate  # noqa: E402
 from hulc2_amd.config import default_model_config  # noqa: E402
 from tests.kcheck import EPS32, compare  # noqa: E402
@@ -138,26 +137,6 @@ def test_built_step_equals_the_float64_stand_in(dev, monkeypatch):
     assert not bad, f"{len(bad)} tensors beyond {MARGIN:g} * max(e_ref, 2^-23): {bad[:6]}"
 
 
-class _env:
-    def __init__(self, **kv):
-        self.kv = kv
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.kv}
-        for k, v in self.kv.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-    def __exit__(self, *exc):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
 def _same(a, b, what):
     assert a.keys() == b.keys()
     bad = []
@@ -180,7 +159,7 @@ def _case_same_bits(dev):
     kn.set_compute("bf16")
 
     def run(calls, **env):
-        with _env(HULC_NO_STEP_NODE=None, **env):
+        with switches.scope(HULC_NO_STEP_NODE=None, **env):
             kn.reset_step_state(dev)
             m = _model(dev, 31)
             batch = _batch(dev, 31)

@@ -6,7 +6,6 @@ same perceptual embedding and do not depend on each other; the contrastive head 
 goals only.  What must hold: the forked step computes what the one-chain step computes (the transformer trunk shares a sequence between 2 instead
 of 4 workgroups: a different summation order of its partial tiles, fp32 rounding), cooperative launches on their share of the device give the
 bits of the whole-device launches, and a scope of 0 keeps every cooperative launch out."""
-import os
 import sys
 from pathlib import Path
 
@@ -17,36 +16,16 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 pytestmark = pytest.mark.gpu
 
-from hulc2_amd import functional as HF, kernels as kn, synthetic as syn  # noqa: E402
+from hulc2_amd import functional as HF, kernels as kn, switches, synthetic as syn  # noqa: E402
 from hulc2_amd.compat import instantiate  # noqa: E402
 from hulc2_amd.config import default_model_config  # noqa: E402
 from hulc2_amd.trainer import ArenaTrainer  # noqa: E402
 
 
-class _env:
-    def __init__(self, **kv):
-        self.kv = kv
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.kv}
-        for k, v in self.kv.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-    def __exit__(self, *exc):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
 def _steps(dev, fork, graph, n=4, B=4, S=16):
     kn.reset_step_state(dev)
     kn.set_compute("bf16")
-    with _env(HULC_FORK=fork):
+    with switches.scope(HULC_FORK=fork):
         m = instantiate(default_model_config(gripper_control=True, dropout_p=0.1)).to(dev)
         syn.fill_state_dict_(m.state_dict(), 3)
         m.train()

@@ -10,7 +10,6 @@ the GPU:
 Dropout is off, plan indices / noise are injected, seeds are fixed.  The cases that capture graphs run in a child process each, as in
 tests/test_lr_schedule_gpu.py (the suite's later step-node tests see the same number of earlier captures with or without this file)."""
 import ctypes
-import os
 import subprocess
 import sys
 from pathlib import Path
@@ -22,7 +21,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 pytestmark = pytest.mark.gpu
 
-from hulc2_amd import functional as HF, kernels as kn, lib, synthetic as syn  # noqa: E402
+from hulc2_amd import functional as HF, kernels as kn, lib, switches, synthetic as syn  # noqa: E402
 from hulc2_amd.compat import instantiate  # noqa: E402
 from hulc2_amd.config import default_model_config  # noqa: E402
 from hulc2_amd.lib import HulcKernelError  # noqa: E402
@@ -320,20 +319,6 @@ def _case_captured_node(dev):
 
 
 # ---- 6. the step node ---------------------------------------------------------------------------------------------------------------------------
-class _env:
-    def __init__(self, **kv):
-        self.kv = kv
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.kv}
-        for k, v in self.kv.items():
-            os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
-
-    def __exit__(self, *exc):
-        for k, v in self.old.items():
-            os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
-
-
 def test_step_node_replays_through_an_annealing_sequence(dev):
     _in_child("step_node")
 
@@ -368,10 +353,10 @@ def _case_step_node(dev):
     captures ONCE at the third call and replays the other six calls: the captures never increase after that one (with beta in the signature
     every epoch was a new layout: nothing was ever captured, or — with longer epochs — every epoch captured again).  Loss and every parameter
     gradient of every step are bit-equal to the same loop on the eager node (HULC_NO_STEP_GRAPH=1)."""
-    with _env(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH="1"):
+    with switches.scope(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH="1"):
         ne, le, ge, ce = _anneal_loop(dev)
     assert ce == [0, 0, 0, 0] and ne.eager_steps == 8
-    with _env(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH=None):
+    with switches.scope(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH=None):
         ng, lg, gg, cg = _anneal_loop(dev)
     assert ng.disabled is None, ng.disabled
     print(f"[step node] captures after each epoch {cg}; eager {ng.eager_steps}, replays {ng.replays}, evictions {ng.evictions}")

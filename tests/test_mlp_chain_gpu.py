@@ -2,7 +2,6 @@
 per-layer GEMM path of the same Function (HULC_NO_MLP_CHAIN=1) — forward values, input gradient, every weight / bias gradient — on the
 shapes the policy uses: the prior (160 -> 4 x 2048 -> 1024, 64 rows), the goal encoders (128 / 384 -> 2048 -> 2048 -> 32, 32 rows), the
 contrastive projections (4096 -> 128 -> 32, 32 -> 128 -> 32) and ragged row counts."""
-import os
 import sys
 from pathlib import Path
 
@@ -13,7 +12,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 pytestmark = pytest.mark.gpu
 
-from hulc2_amd import functional as HF, kernels as kn  # noqa: E402
+from hulc2_amd import functional as HF, kernels as kn, switches  # noqa: E402
 
 SHAPES = [(64, (160, 2048, 2048, 2048, 2048, 1024)), (32, (128, 2048, 2048, 32)), (32, (384, 2048, 2048, 32)), (32, (4096, 128, 32)),
           (32, (32, 128, 32)), (5, (160, 2048, 1024)), (2, (128, 2048, 2048, 32)), (17, (384, 64, 48))]
@@ -27,15 +26,9 @@ def _run(M, dims, seed, chain, need_x=True):
     import copy
     wsd = [copy.deepcopy(l).to(dev) for l in ws]
     xd = x.to(dev).requires_grad_(need_x)
-    if chain:
-        os.environ.pop("HULC_NO_MLP_CHAIN", None)
-    else:
-        os.environ["HULC_NO_MLP_CHAIN"] = "1"
-    try:
+    with switches.scope(HULC_NO_MLP_CHAIN=None if chain else "1"):
         y = HF.mlp(xd, [(l.weight, l.bias, i < len(wsd) - 1) for i, l in enumerate(wsd)])
         (y * r.to(dev)).sum().backward()
-    finally:
-        os.environ.pop("HULC_NO_MLP_CHAIN", None)
     torch.cuda.synchronize()
     return y.detach(), (xd.grad if need_x else None), [l.weight.grad for l in wsd], [l.bias.grad for l in wsd], (ws, x, r)
 

@@ -23,7 +23,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 pytestmark = pytest.mark.gpu
 
-from hulc2_amd import kernels as kn  # noqa: E402
+from hulc2_amd import kernels as kn, switches  # noqa: E402
 from hulc2_amd import synthetic as syn  # noqa: E402
 from hulc2_amd.compat import instantiate  # noqa: E402
 from hulc2_amd.config import real_world_model_config  # noqa: E402
@@ -244,20 +244,17 @@ def _in_child(case: str) -> None:
 
 
 def _store_loop(dev, graphs: bool):
-    if graphs:
-        os.environ.pop("HULC_NO_STEP_GRAPH", None)
-    else:
-        os.environ["HULC_NO_STEP_GRAPH"] = "1"               # (read when the model's step node is made)
     kn.reset_step_state(dev)
     m = _rw_model(dev, 23)
     stores = _stores(dev)
     losses = []
-    for i, d in enumerate(DRAWS):
-        for p in m.parameters():
-            p.grad = None
-        loss = m.training_step({mod: st.batch(d[mod]) for mod, st in stores.items()}, i)
-        loss.backward()
-        losses.append(float(loss.detach()))
+    with switches.scope(HULC_NO_STEP_GRAPH=None if graphs else "1"):      # (read when the model's step node is made)
+        for i, d in enumerate(DRAWS):
+            for p in m.parameters():
+                p.grad = None
+            loss = m.training_step({mod: st.batch(d[mod]) for mod, st in stores.items()}, i)
+            loss.backward()
+            losses.append(float(loss.detach()))
     torch.cuda.synchronize()
     kn.check_faults(dev)
     return losses, m.__dict__["_hulc_step_node"]

@@ -3,8 +3,6 @@
 Both run bf16 MFMA with fp32 accumulation on the same bf16-rounded operands; they differ only in summation order and in
 rounding the recurrent state to bf16 once (wavefront) instead of at every operand load (per-step) — the same values.
 """
-import os
-
 import pytest
 import torch
 
@@ -19,7 +17,7 @@ def dev():
 
 
 def _run(dev, B, S, persistent, seed=0):
-    from hulc2_amd import functional as HF, kernels as kn
+    from hulc2_amd import functional as HF, kernels as kn, switches
 
     kn.set_compute("bf16")
     H, P, E, G = 2048, 64, 40, 32
@@ -29,17 +27,11 @@ def _run(dev, B, S, persistent, seed=0):
     k0, k1 = (P + E + G) ** -0.5, H ** -0.5
     params = [r(H, P + E + G, k=k0), r(H, H, k=k1), r(H, k=k1), r(H, k=k1), r(H, H, k=k1), r(H, H, k=k1), r(H, k=k1), r(H, k=k1)]
     leaves = [t.requires_grad_(True) for t in (plan, emb, goal, *params)]
-    if persistent:
-        os.environ.pop("HULC_NO_RNN_WAVEFRONT", None)
-    else:
-        os.environ["HULC_NO_RNN_WAVEFRONT"] = "1"
-    try:
+    with switches.scope(HULC_NO_RNN_WAVEFRONT=None if persistent else "1"):
         h1 = HF.DecoderRNNFn.apply(leaves[0], leaves[1], leaves[2], 4, 4 + E, *leaves[3:])
         w = r(B, S, H)
         (h1 * w).sum().backward()
         torch.cuda.synchronize()
-    finally:
-        os.environ.pop("HULC_NO_RNN_WAVEFRONT", None)
     return h1.detach(), [t.grad for t in leaves]
 
 

@@ -5,7 +5,6 @@ torch.autocast + GradScaler).  The node must be invisible to that loop: same los
 (HULC_NO_STEP_NODE=1 = round 4's loop of ~160 autograd Functions), eager or as two replayed hipGraphs; a batch at new addresses is copied
 into the graphs' input buffers; no_grad calls and validation take the plain path; gradients still attached at backward time are added back; hulc2_amd.optim.Adam reads the
 gradient arena in place and applies a GradScaler's device scalars without a host synchronisation."""
-import os
 import sys
 from pathlib import Path
 
@@ -16,7 +15,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 pytestmark = pytest.mark.gpu
 
-from hulc2_amd import kernels as kn, synthetic as syn  # noqa: E402
+from hulc2_amd import kernels as kn, switches, synthetic as syn  # noqa: E402
 from hulc2_amd.compat import instantiate  # noqa: E402
 from hulc2_amd.config import default_model_config  # noqa: E402
 
@@ -36,35 +35,21 @@ def _batch(dev, seed, B=2, S=8):
     return b
 
 
-class _env:
-    def __init__(self, **kv):
-        self.kv = kv
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.kv}
-        for k, v in self.kv.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-    def __exit__(self, *exc):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def _amp_loop(dev, steps, opt_cls=torch.optim.Adam, seed=31, B=2, S=8, fresh_batches=False, keep=()):
-    """the Lightning precision-16 loop; -> (model, losses, {step: {name: scaled gradient}} for the steps in `keep`, parameters at the end)"""
+def _amp_fresh(dev, opt_cls=torch.optim.Adam, seed=31, B=2, S=8):
+    """-> [model, batch, optimizer, scaler, next step]: what `_amp_loop` runs on"""
     kn.reset_step_state(dev)
     m = _model(dev, seed)
-    batch = _batch(dev, seed, B, S)
     opt = opt_cls([p for p in m.parameters() if p.requires_grad], lr=2e-4)
-    scaler = torch.amp.GradScaler("cuda", init_scale=65536.0)
+    return [m, _batch(dev, seed, B, S), opt, torch.amp.GradScaler("cuda", init_scale=65536.0), 0]
+
+
+def _amp_loop(dev, steps, opt_cls=torch.optim.Adam, seed=31, B=2, S=8, fresh_batches=False, keep=(), resume=None):
+    """the Lightning precision-16 loop; -> (model, losses, {step: {name: scaled gradient}} for the steps in `keep`, parameters at the end,
+    optimizer).  resume: an `_amp_fresh` list of the caller's, whose step count moves on — a second call with it continues the first"""
+    st = resume if resume is not None else _amp_fresh(dev, opt_cls, seed, B, S)
+    m, batch, opt, scaler, first = st
     losses, grads = [], {}
-    for i in range(steps):
+    for i in range(first, first + steps):
         if fresh_batches:            # the same values at new addresses, as a data loader delivers them
             batch = {k: {kk: ({k3: v3.clone() for k3, v3 in vv.items()} if isinstance(vv, dict) else (vv.clone() if torch.is_tensor(vv) else vv))
                          for kk, vv in db.items()} for k, db in batch.items()}
@@ -79,6 +64,7 @@ def _amp_loop(dev, steps, opt_cls=torch.optim.Adam, seed=31, B=2, S=8, fresh_bat
         losses.append(float(loss))
     torch.cuda.synchronize()
     kn.check_faults(dev)
+    st[4] = first + steps
     return m, losses, grads, {n: p.detach().clone() for n, p in m.named_parameters()}, opt
 
 
@@ -97,11 +83,11 @@ def _same(a, b, what):
 def test_graphed_node_equals_eager_node_bitwise(dev):
     """two replayed hipGraphs against the same node run eagerly (HULC_NO_STEP_GRAPH=1): losses of five steps, the scaled gradients of the
     first and second replayed step, and the parameters after five optimizer steps — bit for bit.  The node captures once and replays after it."""
-    with _env(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH="1"):
+    with switches.scope(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH="1"):
         m_e, l_e, g_e, p_e, _ = _amp_loop(dev, 5, keep=(2, 3))
     node_e = m_e.__dict__["_hulc_step_node"]
     assert node_e.captures == 0 and node_e.eager_steps == 5
-    with _env(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH=None):
+    with switches.scope(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH=None):
         m_g, l_g, g_g, p_g, _ = _amp_loop(dev, 5, keep=(2, 3))
     node = m_g.__dict__["_hulc_step_node"]
     assert node.disabled is None, node.disabled
@@ -112,16 +98,40 @@ def test_graphed_node_equals_eager_node_bitwise(dev):
     _same(p_g, p_e, "parameters after five steps")
 
 
+def test_node_recaptures_when_a_graph_switch_flips(dev):
+    """a switch that chooses the launches of a step (switches.graph_key) flips on a live model: the node may not replay the graph it
+    recorded under the other setting.  Four steps by default, then four more of the same model and optimizer under HULC_NO_MLP_CHAIN=1: the
+    node takes its two eager steps again and captures a second time, and all eight losses are, bit for bit, those of the eager node
+    (HULC_NO_STEP_GRAPH=1), which picks its launches anew at every step."""
+    def flip(**env):
+        with switches.scope(HULC_NO_STEP_NODE=None, HULC_NO_MLP_CHAIN=None, **env):
+            st = _amp_fresh(dev)
+            m, first, _, _, _ = _amp_loop(dev, 4, resume=st)
+            node = m.__dict__["_hulc_step_node"]
+            captures = node.captures
+            with switches.scope(HULC_NO_MLP_CHAIN="1"):
+                second = _amp_loop(dev, 4, resume=st)[1]
+        return node, captures, first + second
+
+    node_e, _, l_e = flip(HULC_NO_STEP_GRAPH="1")
+    assert node_e.captures == 0 and node_e.eager_steps == 8
+    node, captures, l_g = flip(HULC_NO_STEP_GRAPH=None)
+    assert node.disabled is None, node.disabled
+    assert captures == 1
+    assert node.captures == 2
+    assert l_g == l_e, (l_g, l_e)
+
+
 def test_step_node_equals_the_plain_loop(dev):
     """the node (gradient sinks, grouped weight-gradient launch, arena views handed to autograd) against round 4's loop of per-Function autograd
     (HULC_NO_STEP_NODE=1) under autocast(fp16) + GradScaler: the forward is the same launches — the loss of the first step bit for bit — and so is
     the backward except where a gradient sink selects another kernel for the same sum: the bias gradient of the gripper encoder's flatten-linear is
     a row sum inside the grouped weight-gradient launch instead of one inside the tiled GEMM (two summation orders: 2e-7 relative).  Every other
     gradient of the first step is identical bit for bit; over four optimizer steps losses and parameters stay within fp32 rounding of each other."""
-    with _env(HULC_NO_STEP_NODE="1"):
+    with switches.scope(HULC_NO_STEP_NODE="1"):
         m_p, l_p, g_p, p_p, _ = _amp_loop(dev, 4, keep=(0,))
     assert "_hulc_step_node" not in m_p.__dict__
-    with _env(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH=None):
+    with switches.scope(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH=None):
         m_n, l_n, g_n, p_n, _ = _amp_loop(dev, 4, keep=(0,))
     assert m_n.__dict__["_hulc_step_node"].replays == 2
     assert l_n[0] == l_p[0], (l_n, l_p)
@@ -143,9 +153,9 @@ def test_step_node_equals_the_plain_loop(dev):
 
 
 def test_batches_at_new_addresses_are_copied_into_the_graph_inputs(dev):
-    with _env(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH="1"):
+    with switches.scope(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH="1"):
         _, l_e, _, p_e, _ = _amp_loop(dev, 5, fresh_batches=True)
-    with _env(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH=None):
+    with switches.scope(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH=None):
         m, l_g, _, p_g, _ = _amp_loop(dev, 5, fresh_batches=True)
     node = m.__dict__["_hulc_step_node"]
     assert node.replays == 3 and node.input_copies >= 2            # (the small tensors of a batch are copied into the graphs' input buffers)
@@ -154,7 +164,7 @@ def test_batches_at_new_addresses_are_copied_into_the_graph_inputs(dev):
     assert node.slots_ok and len(node.slot_idx) == 4 and node.slot_updates >= 3, (node.slots_ok, node.slot_idx, node.slot_updates)
     assert l_g == l_e
     _same(p_g, p_e, "parameters")
-    with _env(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH=None, HULC_NO_FRAME_SLOTS="1"):
+    with switches.scope(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH=None, HULC_NO_FRAME_SLOTS="1"):
         m2, l_c, _, p_c, _ = _amp_loop(dev, 5, fresh_batches=True)
     assert not m2.__dict__["_hulc_step_node"].slots_ok and l_c == l_e
     _same(p_c, p_e, "parameters (frames copied)")
@@ -204,7 +214,7 @@ def test_accumulation_validation_and_layout_changes_leave_the_graphs(dev):
     from hulc2_amd.models.hulc2 import Hulc2
     Hulc2._plan_calls = 0                                           # (validation samples its plans from a per-call counter stream)
     got = m.validation_step(syn.make_batch(8, 2, 4, device=dev), 0)
-    with _env(HULC_NO_AUTO_SHADOWS="1"):
+    with switches.scope(HULC_NO_AUTO_SHADOWS="1"):
         m2 = _model(dev, 1, dropout_p=0.0)
         m2.load_state_dict({k: v.clone() for k, v in m.state_dict().items()})
         m2.eval()
@@ -242,7 +252,7 @@ def test_lightning_closure_order_stays_on_the_graphs(dev, set_to_none):
         torch.cuda.synchronize()
         kn.check_faults(dev)
         return m, losses, {n: p.detach().clone() for n, p in m.named_parameters()}
-    with _env(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH=None):
+    with switches.scope(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH=None):
         m_a, l_a, p_a = loop(False)
         m_b, l_b, p_b = loop(True)
     na, nb = m_a.__dict__["_hulc_step_node"], m_b.__dict__["_hulc_step_node"]
@@ -288,7 +298,7 @@ def test_arena_zero_grad_in_place_needs_no_add_back(dev):
         kn.check_faults(dev)
         assert opt.fused_launches == 6
         return m, losses, {n: p.detach().clone() for n, p in m.named_parameters()}
-    with _env(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH=None, HULC_TORCH_ADAM=None):
+    with switches.scope(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH=None, HULC_TORCH_ADAM=None):
         m_a, l_a, p_a = loop(False)
         m_b, l_b, p_b = loop(True)
         m_c, l_c, p_c = loop(True, poke=True)
@@ -326,7 +336,7 @@ def test_drop_in_adam_reads_the_gradient_arena_and_takes_the_scaler_on_device(de
     gradient is skipped on the device and does not count."""
     from hulc2_amd.optim import Adam
     lr = 2e-4
-    with _env(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH=None):
+    with switches.scope(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH=None):
         kn.reset_step_state(dev)
         m = _model(dev, 31)
         batch = _batch(dev, 31)
@@ -374,7 +384,7 @@ def test_drop_in_adam_late_first_gradient_and_fused_flag_take_torchs_path(dev):
     """a parameter whose FIRST gradient arrives after the others have stepped starts at step 1 in torch (its own bias correction):
     the drop-in takes torch's per-tensor path for it, the state_dict says step 1; `fused=True` is never the arena launch"""
     from hulc2_amd.optim import Adam
-    with _env(HULC_NO_STEP_NODE=None):
+    with switches.scope(HULC_NO_STEP_NODE=None):
         kn.reset_step_state(dev)
         m = _model(dev, 3, dropout_p=0.0)
         batch = syn.make_batch(3, 2, 8, device=dev)
@@ -554,13 +564,13 @@ def _grad_loop(dev, plan, opt_kind, amp, seed=43, running_sum=False):
 
 
 def _eager_and_graphed(dev, plan, opt_kind, amp, **env):
-    with _env(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH="1", HULC_TORCH_ADAM=None, **env):
+    with switches.scope(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH="1", HULC_TORCH_ADAM=None, **env):
         eager = _grad_loop(dev, plan, opt_kind, amp)
     assert eager[0].captures == 0 and eager[0].eager_steps == len(plan)
     # every comparison includes logit_scale: the 0-dim parameter at arena offset 0 whose `.grad` AccumulateGrad clones out of the arena —
     # its slice is never zeroed, where a slightly wrong restore or add-back of the whole arena shows first
     assert all(g["logit_scale"] is not None for g in eager[2])
-    with _env(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH=None, HULC_TORCH_ADAM=None, **env):
+    with switches.scope(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH=None, HULC_TORCH_ADAM=None, **env):
         graphed = _grad_loop(dev, plan, opt_kind, amp)
     return eager, graphed
 
@@ -614,7 +624,7 @@ def test_accumulation_from_the_first_call_across_the_capture(dev, k, amp):
     plan = [("big", j == 0, j == k - 1) for _ in range(2) for j in range(k)]
     opt_kind = "adam" if amp else "sgd"
     (ne, le, ge, pe), (ng, lg, gg, pg) = _eager_and_graphed(dev, plan, opt_kind, amp)
-    with _env(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH="1"):
+    with switches.scope(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH="1"):
         nr, lr_, gr, pr = _grad_loop(dev, plan, opt_kind, amp, running_sum=True)
     assert ng.disabled is None, ng.disabled
     assert (ng.captures, ng.eager_steps, ng.replays) == (1, 2, 2 * k - 2), (ng.captures, ng.eager_steps, ng.replays)
@@ -654,11 +664,11 @@ def test_a_failed_capture_keeps_the_accumulated_gradients(dev, monkeypatch):
         def __init__(self, *a, **kw):
             raise RuntimeError("graph objects unavailable")
     plan = [("big", False, i == 4) for i in range(5)]
-    with _env(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH="1"):
+    with switches.scope(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH="1"):
         ne, le, ge, pe = _grad_loop(dev, plan, "sgd", False)
     assert ne.eager_steps == 5 and all(g["logit_scale"] is not None for g in ge)
     monkeypatch.setattr(stepnode.torch.cuda, "CUDAGraph", _NoGraph)
-    with _env(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH=None), pytest.warns(UserWarning, match="capture failed"):
+    with switches.scope(HULC_NO_STEP_NODE=None, HULC_NO_STEP_GRAPH=None), pytest.warns(UserWarning, match="capture failed"):
         ng, lg, gg, pg = _grad_loop(dev, plan, "sgd", False)
     assert ng.disabled is not None and "graph objects unavailable" in ng.disabled, ng.disabled
     assert (ng.captures, ng.replays, ng.eager_steps) == (0, 0, 5), (ng.captures, ng.replays, ng.eager_steps)

@@ -14,7 +14,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 pytestmark = pytest.mark.gpu
 
-from hulc2_amd import kernels as kn, synthetic as syn  # noqa: E402
+from hulc2_amd import kernels as kn, switches, synthetic as syn  # noqa: E402
 from hulc2_amd.compat import instantiate  # noqa: E402
 from hulc2_amd.config import default_model_config  # noqa: E402
 from hulc2_amd.lib import HulcKernelError  # noqa: E402
@@ -123,11 +123,8 @@ def test_barrier_timeout_raises_and_adam_skips(dev):
     tr.step(batch, 0)
     kn.check_faults(dev)
     before = tr.flat_p.clone()
-    os.environ["HULC_RNN_DBG"] = "4"
-    try:
+    with switches.scope(HULC_RNN_DBG="4"):
         tr.step(batch, 1)
-    finally:
-        del os.environ["HULC_RNN_DBG"]
     torch.cuda.synchronize()
     assert torch.equal(tr.flat_p, before), "Adam must not consume the gradients of a faulted step"
     with pytest.raises(HulcKernelError, match="barrier timed out"):
@@ -233,14 +230,9 @@ def test_external_optimizer_loop_keeps_weight_copies_fresh_with_a_weight_keeper(
     when the optimizer has stepped.  The loop's losses must be the bits of the lazy per-parameter path (HULC_NO_AUTO_SHADOWS=1), a nudge of
     ONE parameter must be seen, and copy.deepcopy(model) must not drag the keeper along."""
     import copy
-    import os
 
     def run(auto):
-        if auto:
-            os.environ.pop("HULC_NO_AUTO_SHADOWS", None)
-        else:
-            os.environ["HULC_NO_AUTO_SHADOWS"] = "1"
-        try:
+        with switches.scope(HULC_NO_AUTO_SHADOWS=None if auto else "1"):
             kn.reset_step_state(dev)
             m = _model(dev, 9)
             batch = _batch(dev, 9, B=2, S=8)
@@ -253,8 +245,6 @@ def test_external_optimizer_loop_keeps_weight_copies_fresh_with_a_weight_keeper(
                 opt.step()
                 losses.append(float(loss))
             return m, batch, losses
-        finally:
-            os.environ.pop("HULC_NO_AUTO_SHADOWS", None)
 
     m_lazy, _, want = run(False)
     assert "_hulc_shadow_keeper" not in m_lazy.__dict__

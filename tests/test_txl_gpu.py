@@ -3,7 +3,6 @@ feed-forward slice sums folded into the neighbouring kernels) against
   (a) a plain PyTorch fp32 nn.TransformerEncoderLayer — the reference's own layer class (plan_recognition_net.py:115-117) — dropout off,
   (b) the unfused HIP kernel chain on the same counter-RNG streams, dropout on (identical masks by construction).
 Tolerances are bf16's (the fused kernel rounds q, k, v, P and ctx to bf16 as MFMA operands): stated per assertion."""
-import os
 import sys
 from pathlib import Path
 
@@ -14,7 +13,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 pytestmark = pytest.mark.gpu
 
-from hulc2_amd import functional as HF, kernels as kn  # noqa: E402
+from hulc2_amd import functional as HF, kernels as kn, switches  # noqa: E402
 
 
 def _layer(dev, seed, p_drop):
@@ -38,14 +37,8 @@ def _run(m, x, r, B, S, p_drop, seed, fused):
     for q in m.parameters():
         q.grad = None
     x = x.clone().requires_grad_(True)
-    if fused:
-        os.environ.pop("HULC_NO_FUSED_TXL", None)
-    else:
-        os.environ["HULC_NO_FUSED_TXL"] = "1"
-    try:
+    with switches.scope(HULC_NO_FUSED_TXL=None if fused else "1"):
         y = HF.transformer_encoder_layer(x.reshape(B * S, 128), _params(m), B, S, 8, p_drop, seed)
-    finally:
-        os.environ.pop("HULC_NO_FUSED_TXL", None)
     (y * r.reshape(B * S, 128)).sum().backward()
     return y.detach().reshape(B, S, 128), x.grad.detach(), {k: v.grad.detach().clone() for k, v in _params(m).items()}
 
