@@ -360,6 +360,7 @@ class WeightKeeper:
 
     def _settle_sinks(self) -> None:
         """bookkeeping behind a finished backward pass: the first (fully zeroed) pass makes the zeroing plan; later passes clean up after it"""
+        self._settle_zeroed = []                                   # the slices this call cleared (a captured loop repeats them per replay)
         if self._zero_ranges is None and gradsink._sinks and not switches.on("FULL_ZERO_GRAD"):
             self._plan_partial_zero()                              # the backward that just finished ran on a fully zeroed arena
         elif self._zero_ranges is not None:
@@ -369,6 +370,7 @@ class WeightKeeper:
             for k in self._planned_written - now:
                 a, b = self._sink_slices[k]
                 self.flat_g[a:b].zero_()
+                self._settle_zeroed.append((a, b))
             # a sink written for the first time AFTER the plan was made (untouched in the planning step, so neither zeroed per step nor
             # expected to be overwritten): from now on it is "expected" — a later step that does not write it gets the clean-up above
             # instead of Adam applying the stale slice (second case)

@@ -304,6 +304,43 @@ __global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __r
     out[1] = c > 1.f ? 1.f : c;
 }
 
+// ---- gradient accumulation (hulc_grad_accumulate) -------------------------------------------------------------------------------------------
+// One streaming pass per micro-batch of a window: acc is touched once per micro-batch, milliseconds apart, and the gradients it reads were
+// written by a whole backward pass — non-temporal loads of both and non-temporal stores of acc (adam_kernel<7>'s policy for p / m / v).  The g
+// that ACC_FINISH writes is read by the norm pass or the optimizer step straight afterwards: plain stores.  ACC_FINISH is two ROUNDED
+// operations, the add first: pinned() keeps the sum an opaque value, so no pass of the compiler can re-associate it with the multiply.
+#ifndef HULC_GRAD_ACCUM_NT
+#define HULC_GRAD_ACCUM_NT 1       // load policy of acc and g, store policy of acc: 1 non-temporal, 0 default (NOTES.md "Gradient accumulation": the A/B)
+#endif
+enum { ACC_STORE = 0, ACC_ADD = 1, ACC_FINISH = 2 };
+template <int MODE> HULC_DEVICE float acc_value(float a, float g, float scale) {
+    if (MODE == ACC_STORE) return g;
+    const float s = pinned(__fadd_rn(a, g));
+    return MODE == ACC_ADD ? s : __fmul_rn(s, scale);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void grad_accum_kernel(float* __restrict__ acc, float* __restrict__ g, long n, float scale) {
+    constexpr bool NT = HULC_GRAD_ACCUM_NT != 0;
+    const long stride = (long)gridDim.x * blockDim.x * 4;
+    for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {
+        if (i + 3 < n) {
+            const float4 gv = ld4<NT>(g + i);
+            float4 av = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (MODE != ACC_STORE) av = ld4<NT>(acc + i);
+            const float x = acc_value<MODE>(av.x, gv.x, scale), y = acc_value<MODE>(av.y, gv.y, scale);
+            const float z = acc_value<MODE>(av.z, gv.z, scale), w = acc_value<MODE>(av.w, gv.w, scale);
+            if (MODE == ACC_FINISH) st4<false>(g + i, x, y, z, w);
+            else st4<NT>(acc + i, x, y, z, w);
+        } else {
+            for (long k = i; k < n; ++k) {
+                const float r = acc_value<MODE>(MODE == ACC_STORE ? 0.f : acc[k], g[k], scale);
+                if (MODE == ACC_FINISH) g[k] = r; else acc[k] = r;
+            }
+        }
+    }
+}
+
 __global__ void step_count_advance_if_kernel(unsigned long long* state, const float* found_inf) {
     if (!found_inf || *found_inf == 0.f) state[1] += 1ull;      // (torch's fused Adam takes a skipped step's increment back the same way)
 }
@@ -622,6 +659,23 @@ extern "C" int hulc_grad_norm_clip(const float* g, long n, float grad_scale, con
     if (int rc = hulc_check_launch("hulc_grad_norm_clip")) return rc;
     grad_norm_finish_kernel<<<1, 256, 0, (hipStream_t)stream>>>((const double*)ws, (int)blocks, grad_scale, loss_scale, max_norm, out);
     return hulc_check_launch("hulc_grad_norm_clip");
+}
+
+// see include/hulc2_amd.h
+extern "C" int hulc_grad_accumulate(float* acc, float* g, long n, int mode, float scale, void* stream) {
+    if (n < 0 || mode < ACC_STORE || mode > ACC_FINISH) return hulc_fail(-2, "hulc_grad_accumulate: n >= 0, mode 0 (store), 1 (add) or 2 (finish)");
+    if (n == 0) return 0;
+    if (!acc || !g) return hulc_fail(-1, "hulc_grad_accumulate: null pointer");
+    const uintptr_t a0 = (uintptr_t)acc, g0 = (uintptr_t)g, bytes = (uintptr_t)n * sizeof(float);
+    if (a0 < g0 + bytes && g0 < a0 + bytes) return hulc_fail(-2, "hulc_grad_accumulate: the accumulator and the gradient ranges overlap");
+    if ((a0 | g0) % 16) return hulc_fail(-4, "hulc_grad_accumulate: both ranges must be 16-byte aligned");
+    // grid as adam_launch's (8192 workgroups of 256 lanes: its sweep on the same arenas)
+    constexpr long cap = 8192;
+    long blocks = (n / 4 + 255) / 256; if (blocks > cap) blocks = cap; if (blocks < 1) blocks = 1;
+    if (mode == ACC_STORE) grad_accum_kernel<ACC_STORE><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(acc, g, n, scale);
+    else if (mode == ACC_ADD) grad_accum_kernel<ACC_ADD><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(acc, g, n, scale);
+    else grad_accum_kernel<ACC_FINISH><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(acc, g, n, scale);
+    return hulc_check_launch("hulc_grad_accumulate");
 }
 
 // ---- hulc_adamw_step / hulc_sgd_step: see include/hulc2_amd.h -----------------------------------------------------------------------------

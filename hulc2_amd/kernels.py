@@ -1593,6 +1593,30 @@ def grad_norm_clip(g, n, grad_scale, loss_scale_dev, max_norm, out):
     _call("hulc_grad_norm_clip", g, int(n), float(grad_scale), loss_scale_dev, float(max_norm), out, ws, nbytes=4.0 * n)
 
 
+_ACC_MODES = {"store": (0, 8.0), "add": (1, 12.0), "finish": (2, 12.0)}      # mode -> (ABI number, algorithmic bytes per element)
+
+
+def grad_accumulate(acc, g, n, mode, scale=1.0):
+    """One micro-batch of a gradient-accumulation window over the first n elements (hulc_grad_accumulate; one launch, capturable):
+    "store" acc = g, "add" acc = acc + g, "finish" g = (acc + g) * scale — one rounded fp32 add, then one rounded fp32 multiply.  store and
+    add leave g untouched, finish leaves acc untouched; scale is ignored outside "finish".  acc, g: contiguous fp32 tensors of at least n
+    elements on the same GPU that do not overlap inside [0, n)."""
+    if not isinstance(mode, str) or mode not in _ACC_MODES:
+        raise _L.HulcKernelError(f"grad_accumulate: mode {mode!r} is not 'store', 'add' or 'finish'")
+    for name, t in (("acc", acc), ("g", g)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous():
+            raise _L.HulcKernelError(f"grad_accumulate: {name} is a contiguous fp32 tensor")
+    _require_cuda(acc, g)
+    n = int(n)
+    if acc.device != g.device or n < 0 or acc.numel() < n or g.numel() < n:
+        raise _L.HulcKernelError("grad_accumulate: acc and g hold at least n >= 0 elements each, on one device")
+    a0, g0 = acc.data_ptr(), g.data_ptr()
+    if n and a0 < g0 + 4 * n and g0 < a0 + 4 * n:
+        raise _L.HulcKernelError("grad_accumulate: acc[:n] and g[:n] overlap")
+    number, per_element = _ACC_MODES[mode]
+    _call("hulc_grad_accumulate", acc, g, n, number, float(scale), nbytes=per_element * n)
+
+
 def step_count_advance_if(state, found_inf_dev=None) -> None:
     """state[1] += 1 unless the GradScaler's found_inf (device float) is set — the device-resident step count of hulc2_amd.optim.Adam"""
     _call("hulc_step_count_advance_if", state, found_inf_dev)

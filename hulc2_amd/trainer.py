@@ -315,7 +315,8 @@ class ArenaTrainer(WeightKeeper):
     def __init__(self, model: torch.nn.Module, lr: float = 2e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                  bucket_mb: int = 32, group=None, overlap: bool = True, comm_algo: Optional[str] = None, grad_payload: Optional[str] = None,
                  force_comm: bool = False, optimizer: str = "adam", momentum: float = 0.0, dampening: float = 0.0, nesterov: bool = False,
-                 skip_params=(), gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm"):
+                 skip_params=(), gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: str = "norm",
+                 accumulate_grad_batches: int = 1):
         """optimizer: the update rule of optimizer_step() — "adam" (torch.optim.Adam, L2 weight decay), "adamw" (torch.optim.AdamW, decoupled
         decay) or "sgd" (torch.optim.SGD with momentum / dampening / nesterov, L2 weight decay): conf/model/optimizer/{adam,adamw,sgd}.yaml;
         hulc2_amd.optim.trainer_kwargs_from_config maps such a config to these arguments.
@@ -326,6 +327,17 @@ class ArenaTrainer(WeightKeeper):
         step multiplies every gradient by min(1, gradient_clip_val / (norm + 1e-6)) in registers, as torch.nn.utils.clip_grad_norm_ would
         have in memory; "value": the step clamps every gradient to [-gradient_clip_val, gradient_clip_val] (clip_grad_value_).  Every rank
         reads the same arena with the same kernel, so all ranks apply the same bits; set_gradient_clip changes the threshold later.
+        accumulate_grad_batches: Lightning's trainer flag of the same name, k >= 1.  Every step() / replay() is one micro-batch and returns its
+        detached loss; calls are grouped into windows of k and the optimizer runs once per window, on G = ((g_1 + g_2) + ... + g_k) * s with
+        s = fp32(1 / k) (the quotient formed in double, then rounded), summed left to right in fp32 by hulc_grad_accumulate into a second
+        gradient arena (flat_acc).  That is Lightning's mean over the window up to rounding: Lightning divides each LOSS by k, here the SUM is
+        scaled once.  A micro-batch that does not close its window runs forward, backward and one accumulate launch, nothing else: no
+        exchange, lr write, norm pass, optimizer launch or derive_after_step.  The closing one runs today's tail on G — the gradient
+        exchange (ONCE per window: under data parallelism the collectives drop k-fold, which is the point of accumulating there), the lr
+        schedule, clipping (grad_norm is the norm of G), the optimizer, the derived copies.  The optimizer step count (host and device) and
+        the lr schedule advance once per window, the RNG word once per micro-batch (fresh dropout masks and plan samples).  With several
+        ranks k > 1 needs overlap=False: the bucket hooks would reduce every micro-batch's partial gradient.  k == 1 allocates no
+        accumulator and runs exactly the launches it always ran.
         force_comm: run the multi-rank control flow (split graphs, comm stream, collectives) even with a single rank in the process
         group — how the RCCL path is exercised on a one-GPU box."""
         if optimizer not in ("adam", "adamw", "sgd"):
@@ -339,6 +351,7 @@ class ArenaTrainer(WeightKeeper):
         self.step_node = False                             # (the step node is the keeper's, under an external optimizer)
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.multi = self.world > 1 or (force_comm and dist.is_initialized())
+        self.accumulate_grad_batches = self._check_accumulate(accumulate_grad_batches, self.multi and overlap)
         # fused views receive their gradient through a sink only, so they exist only when sinks do (not with per-parameter all-reduce hooks)
         use_sinks = next(p for p in model.parameters() if p.requires_grad).is_cuda and (not self.multi or not overlap)
         plan = plan_arena(model, use_sinks)
@@ -360,6 +373,8 @@ class ArenaTrainer(WeightKeeper):
             self._register_sinks(None)
             self._acc_hooks = [p.register_post_accumulate_grad_hook(self._saw_autograd_grad) for p in self.params]
         self._clip_out = torch.zeros(2, dtype=torch.float32, device=dev)      # {gradient norm, clip coefficient} of the last norm pass
+        self.micro_batch = 0                               # position inside the current accumulation window, 0 .. k - 1
+        self.flat_acc = self._new_accumulator()            # the running sum of a window's gradients (None with k == 1)
         self.step_count = 0
         self._fault_every = switches.value("FAULT_CHECK_EVERY")
         if dev.type == "cuda":
@@ -424,9 +439,14 @@ class ArenaTrainer(WeightKeeper):
             st[names[id(p)]] = {"exp_avg": self.exp_avg[off:off + n].view(p.shape).clone(),
                                 "exp_avg_sq": self.exp_avg_sq[off:off + n].view(p.shape).clone()}
         words = kn.step_state(self.dev).tolist() if self.dev.type == "cuda" else [0, self.step_count]
+        # the accumulation window: its length and the position inside it; an open window (position > 0) carries its running sum the way the
+        # moments travel, per parameter and by name.  (The device step count of an open window already counts the step that will close it.)
+        acc = {"k": int(self.accumulate_grad_batches), "position": int(self.micro_batch)}
+        if self.micro_batch > 0:
+            acc["sum"] = {names[id(p)]: self.flat_acc[off:off + p.numel()].view(p.shape).clone() for p, off in zip(self.params, self.offsets)}
         # (the schedule's function is not state, as with torch's LambdaLR: the resumed run attaches the same one, before or after loading)
         return {"lr_schedule": {"base_lr": float(self.base_lr), "position": int(self._opt_steps), "device_lr": self._lr_dev is not None},
-                "state": st, "step": int(self.step_count), "rng_word": int(words[0]), "device_step": int(words[1]),
+                "state": st, "accumulate": acc, "step": int(self.step_count), "rng_word": int(words[0]), "device_step": int(words[1]),
                 "comm": ({"algo": self.comm.algo, "payload": self.comm.payload, "chosen_by": self.comm.chosen_by} if self.comm is not None else None),
                 "hparams": {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd, "optimizer": self.optimizer,
                             "momentum": self.momentum, "dampening": self.dampening, "nesterov": self.nesterov}}
@@ -436,11 +456,29 @@ class ArenaTrainer(WeightKeeper):
         if kind != self.optimizer:
             raise ValueError(f"ArenaTrainer.load_state_dict: the state is of optimizer {kind!r}, this trainer was built with "
                              f"optimizer={self.optimizer!r}; build the trainer with the optimizer the state was saved under")
+        acc = sd.get("accumulate") or {"k": self.accumulate_grad_batches, "position": 0}      # (states written before there were windows)
+        if int(acc["k"]) != self.accumulate_grad_batches:
+            raise ValueError(f"ArenaTrainer.load_state_dict: the state was saved with accumulate_grad_batches={int(acc['k'])}, this trainer "
+                             f"was built with {self.accumulate_grad_batches}; build the trainer with the window length of the state")
         names = {n: p for n, p in self.model.named_parameters()}
         index = {id(p): off for p, off in zip(self.params, self.offsets)}
         missing = [n for n, p in names.items() if id(p) in index and n not in sd["state"]]
         if missing:
             raise KeyError(f"ArenaTrainer.load_state_dict: no optimizer state for {missing[:4]}{'...' if len(missing) > 4 else ''}")
+        position = int(acc["position"])
+        if not 0 <= position < self.accumulate_grad_batches:
+            raise ValueError(f"ArenaTrainer.load_state_dict: window position {position} outside 0 .. {self.accumulate_grad_batches - 1}")
+        if position > 0:
+            lost = [n for n, p in names.items() if id(p) in index and n not in acc.get("sum", {})]
+            if lost:
+                raise KeyError(f"ArenaTrainer.load_state_dict: no accumulated gradient for {lost[:4]}{'...' if len(lost) > 4 else ''}")
+            with torch.no_grad():
+                self.flat_acc.zero_()
+                for n, t in acc["sum"].items():
+                    p = names.get(n)
+                    if p is not None and id(p) in index:
+                        self.flat_acc[index[id(p)]:index[id(p)] + p.numel()].copy_(t.reshape(-1))
+        self.micro_batch = position
         with torch.no_grad():
             for n, rec in sd["state"].items():
                 p = names.get(n)
@@ -669,6 +707,49 @@ class ArenaTrainer(WeightKeeper):
         kn.grad_norm_clip(self.flat_g, self.total, 1.0 / self.world, None, self.clip_val, self._clip_out)
         return {"clip_coef_dev": self._clip_out[1:2]}
 
+    # ---- gradient accumulation (Lightning: trainer.accumulate_grad_batches) ----------------------------------------------------------------
+    _replay_settle = ()            # arena slices the settle clean-up cleared behind the captured backward: replay() clears them again (k > 1)
+
+    @staticmethod
+    def _check_accumulate(k, hooks: bool = False) -> int:
+        """hooks: the trainer reduces gradient buckets from per-parameter hooks (several ranks, overlap=True)"""
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+            raise ValueError(f"ArenaTrainer: accumulate_grad_batches must be an int >= 1, got {k!r}")
+        if k > 1 and hooks:
+            raise ValueError("ArenaTrainer: accumulate_grad_batches > 1 with several ranks needs overlap=False (the bucket hooks of "
+                             "overlap=True would all-reduce every micro-batch's partial gradient)")
+        return k
+
+    def _new_accumulator(self) -> Optional[torch.Tensor]:
+        if self.accumulate_grad_batches == 1:
+            return None
+        return torch.zeros(self.total, dtype=torch.float32, device=self.dev)
+
+    def set_accumulate_grad_batches(self, k: int) -> None:
+        """The window length of the following micro-batches; only at a window boundary (micro_batch == 0).  The captured graphs are built
+        for one k (which launches they hold, who bumps the step count), so a change drops them, as set_gradient_clip does."""
+        k = self._check_accumulate(k, self.multi and self.buckets.overlap)
+        if self.micro_batch != 0:
+            raise RuntimeError(f"ArenaTrainer.set_accumulate_grad_batches: micro-batch {self.micro_batch} of {self.accumulate_grad_batches} "
+                               "is open; change the window length at a window boundary")
+        if k == self.accumulate_grad_batches:
+            return
+        if getattr(self, "graph_opt", None) is not None:
+            self.graph_fb = self.graph_enc = self.graph_opt = None
+        self.accumulate_grad_batches = k
+        self.flat_acc = self._new_accumulator()
+
+    def _accumulate(self) -> bool:
+        """behind the backward pass (and the settle clean-up) of a micro-batch, k > 1: the arena into the running sum — store, add, or finish
+        back into flat_g.  True when this micro-batch closed its window (flat_g then holds G)."""
+        j, k = self.micro_batch, self.accumulate_grad_batches
+        if j == k - 1:
+            kn.grad_accumulate(self.flat_acc, self.flat_g, self.total, "finish", ctypes.c_float(1.0 / k).value)
+        else:
+            kn.grad_accumulate(self.flat_acc, self.flat_g, self.total, "store" if j == 0 else "add")
+        self.micro_batch = (j + 1) % k
+        return j == k - 1
+
     # ---- KL annealing: the KL weight as a device scalar the captured KL launches read (Hulc2.set_kl_beta) --------------------------------
     _kl_captured = None            # the by-value KL weight baked into the captured graphs; None: no graphs, or they read the model's device word
     _kl_schedule = None            # the attached annealing rule (set_kl_schedule)
@@ -721,10 +802,10 @@ class ArenaTrainer(WeightKeeper):
 
     _split_active = False
 
-    def _forward_backward_head(self, batch, batch_idx: int) -> torch.Tensor:
+    def _forward_backward_head(self, batch, batch_idx: int, count: bool = True) -> torch.Tensor:
         """forward + backward down to the encoder output: every gradient outside the camera encoders is final afterwards"""
         shadow.bump_epoch()
-        kn.advance_step_state(self.dev)
+        kn.advance_step_state(self.dev, True, count)
         kn.wgrad_reset(self.dev)
         self.zero_grad()
         self._split_active = True
@@ -754,6 +835,10 @@ class ArenaTrainer(WeightKeeper):
 
     def optimizer_step(self):
         self._settle_sinks()
+        self._optimizer_launch()
+
+    def _optimizer_launch(self):
+        """the optimizer pass over the finished gradient arena and the derived copies behind it (the settle clean-up has run)"""
         self.step_count += 1
         common = dict(grad_scale=1.0 / self.world,
                       step_state_dev=kn.step_state(self.dev),      # step count lives on the device (graph replay)
@@ -771,9 +856,11 @@ class ArenaTrainer(WeightKeeper):
                         self.momentum, self.dampening, self.nesterov, self.wd, self.step_count, skip_ranges=self.skip_ranges, **common)
         self.derive_after_step()                                   # (the other derived copies: two launches behind the optimizer's)
 
-    def _forward_backward(self, batch, batch_idx: int) -> torch.Tensor:
+    def _forward_backward(self, batch, batch_idx: int, count: bool = True) -> torch.Tensor:
+        """count: this pass also bumps the device optimizer step count (not the later micro-batches of an accumulation window, and not the
+        captured pass of one: replay() bumps the count when a window opens)"""
         shadow.bump_epoch()                    # every repack/shadow is re-made inside this step (and inside a capture)
-        kn.advance_step_state(self.dev)        # fresh dropout / plan-sample stream, step count + 1
+        kn.advance_step_state(self.dev, True, count)       # fresh dropout / plan-sample stream; step count + 1 with `count`
         kn.wgrad_reset(self.dev)
         self.zero_grad()
         loss = self.model.training_step(batch, batch_idx)
@@ -816,7 +903,16 @@ class ArenaTrainer(WeightKeeper):
         return sum(a.elapsed_time(b) for a, b in evs) / len(evs)
 
     def step(self, batch, batch_idx: int = 0) -> torch.Tensor:
-        """zero grads -> training_step -> backward (+ overlapped all-reduce) -> fused Adam.  Returns the detached loss."""
+        """zero grads -> training_step -> backward (+ overlapped all-reduce) -> fused Adam.  Returns the detached loss.
+        accumulate_grad_batches > 1: one micro-batch; the exchange and the optimizer follow only the one that closes its window."""
+        if self.accumulate_grad_batches > 1:
+            with self.gpu_section():
+                loss = self._forward_backward(batch, batch_idx, count=self.micro_batch == 0)
+                self._settle_sinks()                 # its clean-up fills slices of flat_g: the accumulator reads the arena behind it
+                closing = self._accumulate()
+            if closing:
+                self._window_tail(self._optimizer_launch)
+            return loss
         with (self.gpu_section() if not (self.multi and self.buckets.overlap) else contextlib.nullcontext()):
             loss = self._forward_backward(batch, batch_idx)
         ev = self._comm_wait_begin()
@@ -828,6 +924,18 @@ class ArenaTrainer(WeightKeeper):
             self._opt_steps += 1
             self._poll_faults()
         return loss
+
+    def _window_tail(self, optimizer) -> None:
+        """behind the micro-batch that closed a window (flat_g holds G): the one gradient exchange of the window, the lr write, then
+        `optimizer` — the launches themselves or the captured graph's replay"""
+        ev = self._comm_wait_begin()
+        self.buckets.finish()
+        self._comm_wait_end(ev)
+        with self.gpu_section():
+            self._apply_lr_schedule()
+            optimizer()
+            self._opt_steps += 1
+            self._poll_faults()
 
     _since_check = 0
 
@@ -849,8 +957,18 @@ class ArenaTrainer(WeightKeeper):
     def capture(self, batch) -> None:
         """Capture forward+backward and the optimizer as two HIP graphs over the (static, device-resident) batch.
         Between them the gradient arena is all-reduced eagerly when world > 1 (construct with overlap=False).
-        Call after a few eager warm-up steps (allocator pools, lazy scratch buffers and kernels are then live)."""
+        Call after a few eager warm-up steps (allocator pools, lazy scratch buffers and kernels are then live).
+        accumulate_grad_batches = k > 1: only at a window boundary (RuntimeError otherwise); the warm-up is two whole WINDOWS and leaves the
+        trainer at a boundary.  ONE forward/backward graph serves every micro-batch — it advances the RNG word only, replay() bumps the
+        step count when a window opens — and replay() launches the settle clean-up and the accumulate pass eagerly behind it (static
+        pointers, no host synchronisation); the optimizer graph replays only when the window closes.  Moving through a window never drops
+        or recaptures a graph; a change of k does.  Several ranks: the split replay (graph_enc) does NOT overlap the exchange with the
+        encoder backward when k > 1 — on the closing micro-batch both graphs replay, the whole arena is finished, and then one exchange
+        of the whole arena runs on the comm stream, as GradBuckets.finish() does it: one exchange per window instead of k."""
         assert self.dev.type == "cuda"
+        k = self.accumulate_grad_batches
+        if self.micro_batch != 0:
+            raise RuntimeError(f"ArenaTrainer.capture: micro-batch {self.micro_batch} of {k} is open; capture at a window boundary")
         if self.multi and self.buckets.overlap:
             raise RuntimeError("graph mode needs ArenaTrainer(overlap=False): bucket hooks cannot run inside a replayed graph")
         self.comm.reserve()
@@ -859,7 +977,7 @@ class ArenaTrainer(WeightKeeper):
         side = kn.capture_stream(self.dev)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):                # AccumulateGrad nodes must be born on the capture stream
-            for i in range(2):
+            for i in range(2 * k):
                 self.step(batch, i)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
@@ -871,15 +989,23 @@ class ArenaTrainer(WeightKeeper):
             if self.multi and self.enc_hi > self.enc_lo and not switches.on("NO_SPLIT_GRAPH"):
                 # two graphs around the split point; replay() launches the big all-reduce between them on the comm stream
                 with torch.cuda.graph(self.graph_fb, stream=side, **mode):
-                    self.static_loss = self._forward_backward_head(batch, 0)
+                    self.static_loss = self._forward_backward_head(batch, 0, count=k == 1)
                 self.graph_enc = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(self.graph_enc, pool=self.graph_fb.pool(), stream=side, **mode):
                     self._backward_encoder()
             else:
                 with torch.cuda.graph(self.graph_fb, stream=side, **mode):
-                    self.static_loss = self._forward_backward(batch, 0)
+                    self.static_loss = self._forward_backward(batch, 0, count=k == 1)
+            if k > 1:
+                # the settle clean-up of the captured backward, between the graphs: what it cleared, replay() clears behind every replay
+                with torch.cuda.stream(side):
+                    self._settle_sinks()
+                self._replay_settle = tuple(self._settle_zeroed)
             with torch.cuda.graph(self.graph_opt, pool=self.graph_fb.pool(), stream=side, **mode):
-                self.optimizer_step()
+                if k > 1:
+                    self._optimizer_launch()
+                else:
+                    self.optimizer_step()
         torch.cuda.synchronize()
         # a KL weight taken by value is baked into graph_fb: replay() refuses to run it under another one
         kl = getattr(self.model, "kl_beta", None)
@@ -892,6 +1018,19 @@ class ArenaTrainer(WeightKeeper):
             raise RuntimeError(f"ArenaTrainer.replay: the graphs were captured with kl_beta = {self._kl_captured!r} as a kernel argument and cannot "
                                f"see model.kl_beta = {float(self.model.kl_beta)!r}: set the weight through ArenaTrainer.set_kl_beta (the captured "
                                "launches then read a device scalar) and call capture() again")
+        if self.accumulate_grad_batches > 1:
+            with self.gpu_section():
+                if self.micro_batch == 0:            # a window opens: the optimizer step count of the pass that will close it
+                    kn.step_count_advance_if(kn.step_state(self.dev))
+                self.graph_fb.replay()
+                if self.graph_enc is not None:
+                    self.graph_enc.replay()
+                for a, b in self._replay_settle:
+                    self.flat_g[a:b].zero_()
+                closing = self._accumulate()
+            if closing:
+                self._window_tail(self.graph_opt.replay)
+            return self.static_loss
         with self.gpu_section():
             self.graph_fb.replay()
         if self.graph_enc is not None:

@@ -784,6 +784,21 @@ int hulc_sgd_step_clip(float* p, const float* g, float* buf, void* bf16_shadow, 
                        const int* skip_flag, void* lo_shadow, const long* lo_ranges, int n_ranges, const float* loss_scale,
                        const float* found_inf, const float* lr_dev, const long* skip_ranges, int n_skip, const float* clip_coef,
                        float clip_value, void* stream);
+/* (added under ABI 7 — a new symbol only; every earlier prototype and hulc_abi_version() are unchanged.)  GRADIENT ACCUMULATION over arena
+ * ranges (Lightning's trainer.accumulate_grad_batches in the native loop): acc holds the running sum of a window's micro-batch gradients, g
+ * is the gradient arena a backward pass has just filled.  Per element i of [0, n):
+ *   mode 0 (store)   acc[i] = g[i]
+ *   mode 1 (add)     acc[i] = fl(acc[i] + g[i])
+ *   mode 2 (finish)  g[i]   = fl(fl(acc[i] + g[i]) * scale)
+ * Finish is the add FIRST, rounded to fp32, and THEN the multiply, rounded to fp32: two roundings in that order, never contracted into one
+ * operation and never re-associated (not acc * scale + g * scale), so k - 1 accumulations and one finish give ((g_1 + g_2) + ... + g_k) * scale
+ * summed left to right.  Modes 0 and 1 leave g as it was, mode 2 leaves acc as it was; `scale` is ignored outside mode 2.  There is no
+ * early-out on a value: inf and NaN propagate as IEEE arithmetic gives them.  One streaming launch (float4 body + scalar tail; acc through
+ * non-temporal loads and stores, the g that finish writes through plain stores: the norm pass or the optimizer step reads it next), no host
+ * synchronisation: a launch may be captured into a graph.
+ * Refused: a null pointer with n > 0 (-1); n < 0, a mode outside {0, 1, 2}, ranges [acc, acc + n) and [g, g + n) that overlap (-2); a
+ * pointer that is not 16-byte aligned (-4).  n == 0 is a successful no-op. */
+int hulc_grad_accumulate(float* acc, float* g, long n, int mode, float scale, void* stream);
 /* Device-resident step state {rng word, optimizer step count}: advanced by one kernel per training step so that
  * a captured hipGraph replays with fresh dropout masks / plan samples and the right Adam bias correction.
  * RNG kernels xor state[0] into their site seed (seed_dev = state); hulc_adam_step reads state[1] when
