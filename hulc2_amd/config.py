@@ -15,8 +15,13 @@ DISTRIBUTIONS = {
 }
 
 
-def default_model_config(gripper_control: bool = True, dropout_p: float = 0.1, static_hw=(200, 200), distribution: str = "discrete") -> Config:
-    """distribution: "discrete" (the headline config) or "continuous" (`model/distribution=continuous`)"""
+def default_model_config(gripper_control: bool = True, dropout_p: float = 0.1, static_hw=(200, 200), distribution: str = "discrete",
+                         dropout_vis_fc: float = 0.0, word_dropout_p: float = 0.0, l2_normalize_output: bool = False,
+                         l2_normalize_goal_embeddings: bool = False) -> Config:
+    """distribution: "discrete" (the headline config) or "continuous" (`model/distribution=continuous`).  The encoder regularisers:
+    dropout_vis_fc / l2_normalize_output go to both camera yamls (rgb_static/default.yaml, rgb_gripper/default.yaml),
+    l2_normalize_goal_embeddings to both goal encoders, word_dropout_p to language_goal/default.yaml; per-encoder values: edit the returned
+    config (e.g. cfg["perceptual_encoder"]["rgb_gripper"]["dropout_vis_fc"])."""
     act7 = [1.0] * 7
     return Config.wrap({
         "_target_": "hulc2.models.hulc2.Hulc2",
@@ -26,12 +31,12 @@ def default_model_config(gripper_control: bool = True, dropout_p: float = 0.1, s
             "_recursive_": False,
             "rgb_static": {
                 "_target_": "hulc2.models.perceptual_encoders.vision_network.VisionNetwork",
-                "input_width": static_hw[1], "input_height": static_hw[0], "activation_function": "ReLU", "dropout_vis_fc": 0.0,
-                "l2_normalize_output": False, "visual_features": 64, "num_c": 3, "use_sinusoid": False, "spatial_softmax_temp": 1.0},
+                "input_width": static_hw[1], "input_height": static_hw[0], "activation_function": "ReLU", "dropout_vis_fc": dropout_vis_fc,
+                "l2_normalize_output": l2_normalize_output, "visual_features": 64, "num_c": 3, "use_sinusoid": False, "spatial_softmax_temp": 1.0},
             "rgb_gripper": {
                 "_target_": "hulc2.models.perceptual_encoders.vision_network_gripper.VisionNetwork",
-                "input_width": 84, "input_height": 84, "activation_function": "ReLU", "dropout_vis_fc": 0.0,
-                "l2_normalize_output": False, "visual_features": 64, "conv_encoder": "nature_cnn", "num_c": 3},
+                "input_width": 84, "input_height": 84, "activation_function": "ReLU", "dropout_vis_fc": dropout_vis_fc,
+                "l2_normalize_output": l2_normalize_output, "visual_features": 64, "conv_encoder": "nature_cnn", "num_c": 3},
             "depth_static": None, "depth_gripper": None, "proprio": None, "tactile": None,
         },
         "plan_proposal": {
@@ -45,11 +50,11 @@ def default_model_config(gripper_control: bool = True, dropout_p: float = 0.1, s
         "distribution": dict(DISTRIBUTIONS[distribution]),
         "visual_goal": {
             "_target_": "hulc2.models.encoders.goal_encoders.VisualGoalEncoder", "in_features": None, "hidden_size": 2048,
-            "latent_goal_features": 32, "l2_normalize_goal_embeddings": False, "activation_function": "ReLU"},
+            "latent_goal_features": 32, "l2_normalize_goal_embeddings": l2_normalize_goal_embeddings, "activation_function": "ReLU"},
         "language_encoder": None,
         "language_goal": {
             "_target_": "hulc2.models.encoders.goal_encoders.LanguageGoalEncoder", "in_features": 384, "hidden_size": 2048,
-            "latent_goal_features": 32, "l2_normalize_goal_embeddings": False, "activation_function": "ReLU", "word_dropout_p": 0.0},
+            "latent_goal_features": 32, "l2_normalize_goal_embeddings": l2_normalize_goal_embeddings, "activation_function": "ReLU", "word_dropout_p": word_dropout_p},
         "action_decoder": {
             "_target_": "hulc2.models.decoders.logistic_decoder_rnn.LogisticDecoderRNN",
             "n_mixtures": 10, "hidden_size": 2048, "out_features": 7, "log_scale_min": -7.0, "act_max_bound": act7,
@@ -66,12 +71,15 @@ def default_model_config(gripper_control: bool = True, dropout_p: float = 0.1, s
     })
 
 
-def real_world_model_config(dropout_p: float = 0.1) -> Config:
+def real_world_model_config(dropout_p: float = 0.1, dropout_vis_fc: float = 0.0, word_dropout_p: float = 0.0, l2_normalize_output: bool = False,
+                            l2_normalize_goal_embeddings: bool = False) -> Config:
     """conf/cfg_low_level_rw.yaml -> conf/model/real_world_hulc++.yaml (BASELINE configs[3]): static camera through the frozen R3M trunk
     (conf/model/perceptual_encoder/rgb_static/r3m.yaml), the decoder sees the whole perceptual embedding and predicts world-frame actions
     (conf/model/action_decoder/logistic_decoder_rnn_real_world.yaml:15,19), no CLIP auxiliary loss (real_world_hulc++.yaml:12,20);
     language arrives as precomputed embeddings like the headline config (language_encoder = none)."""
-    cfg = default_model_config(gripper_control=False, dropout_p=dropout_p)
+    # (the R3M static camera has neither switch: dropout_vis_fc / l2_normalize_output reach the gripper camera only)
+    cfg = default_model_config(gripper_control=False, dropout_p=dropout_p, dropout_vis_fc=dropout_vis_fc, word_dropout_p=word_dropout_p,
+                               l2_normalize_output=l2_normalize_output, l2_normalize_goal_embeddings=l2_normalize_goal_embeddings)
     cfg["perceptual_encoder"]["rgb_static"] = Config.wrap({
         "_target_": "hulc2.models.perceptual_encoders.vision_r3m.VisionR3M", "visual_features": 64, "freeze_backbone": True,
         "resnet_model": "resnet18"})

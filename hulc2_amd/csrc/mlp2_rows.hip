@@ -30,6 +30,19 @@ struct Mlp2P {
     float* dx;                      // (T, 128) or null
     uint16_t *h, *dh;               // (T, H) bf16
 };
+// DROP instantiations: inverted dropout on the hidden tile (fc1 = Sequential(Linear, ReLU, Dropout(p)), vision_network.py:49-51).  The
+// arguments ride behind Mlp2P only where DROP is set: the plain kernels' argument block is what it was.
+template <bool DROP> struct Mlp2Arg : Mlp2P {};
+template <> struct Mlp2Arg<true> : Mlp2P {
+    float drop_p;
+    unsigned long long seed;
+    const unsigned long long* seed_dev;
+};
+// keep-scales of the 16 hidden units a lane holds of row `row` in slice j0: element index row * H + hidden, the index the GEMM epilogue
+// (hulc_gemm_desc.drop_p) gives the same (T, H) matrix; j0 and H are multiples of 4, so four draws serve the 16 elements
+HULC_DEVICE void hidden_keep16(const Mlp2Arg<true>& p, unsigned long long seed, long row, int j0, int hf, float (&ks)[16]) {
+    dropout_scale_acc16(seed, (uint64_t)row * (uint64_t)p.H + (uint64_t)j0, hf, p.drop_p, ks);
+}
 
 // sum of the four waves' partial tiles for THIS wave's output tile (fixed order); part: [wave][tile][register][lane]
 template <int NT>
@@ -72,8 +85,8 @@ HULC_DEVICE void exchange4(const f32x16_t (&acc)[4], float* part, int w, int lan
 }
 
 // X3: both products from hi / lo splits of both operands (three bf16 MFMAs each: fp32-class values, the selective-precision site "encfc")
-template <int OT, bool X3>          // OT = OUT / 32 output row tiles
-__global__ __launch_bounds__(256) void mlp2_fwd_kernel(Mlp2P p) {
+template <int OT, bool X3, bool DROP = false>          // OT = OUT / 32 output row tiles
+__global__ __launch_bounds__(256) void mlp2_fwd_kernel(Mlp2Arg<DROP> p) {
     __shared__ float part[4 * OT * 16 * 64];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, hf = lane >> 5;
     const long tok0 = (long)blockIdx.x * 32;
@@ -84,6 +97,8 @@ __global__ __launch_bounds__(256) void mlp2_fwd_kernel(Mlp2P p) {
     f32x16_t acc[OT];
 #pragma unroll
     for (int ot = 0; ot < OT; ++ot) acc[ot] = zero16();
+    unsigned long long seed = 0ull;
+    if constexpr (DROP) seed = p.seed ^ (p.seed_dev ? p.seed_dev[0] : 0ull);
     for (int s = 0; s < p.H / 128; ++s) {
         const int j0 = s * 128 + 32 * w;
         bf16x8_t w1f[8], w2f[OT * 2], w1l[X3 ? 8 : 1], w2l[X3 ? OT * 2 : 1];
@@ -113,6 +128,12 @@ __global__ __launch_bounds__(256) void mlp2_fwd_kernel(Mlp2P p) {
         float hv[16];
 #pragma unroll
         for (int e = 0; e < 16; ++e) hv[e] = fmaxf(zT[e], 0.f);
+        if constexpr (DROP) {
+            float ks[16];
+            hidden_keep16(p, seed, tok0 + r, j0, hf, ks);
+#pragma unroll
+            for (int e = 0; e < 16; ++e) hv[e] *= ks[e];
+        }
         if constexpr (X3) {
             bf16x8_t h0, h0l, h1, h1l;
             pack8f_hl(hv, h0, h0l); pack8f_hl(hv + 8, h1, h1l);
@@ -143,8 +164,8 @@ __global__ __launch_bounds__(256) void mlp2_fwd_kernel(Mlp2P p) {
     }
 }
 
-template <int OT>
-__global__ __launch_bounds__(256) void mlp2_bwd_kernel(Mlp2P p) {
+template <int OT, bool DROP = false>
+__global__ __launch_bounds__(256) void mlp2_bwd_kernel(Mlp2Arg<DROP> p) {
     __shared__ float part[4 * 2 * 16 * 64];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, hf = lane >> 5;
     const long tok0 = (long)blockIdx.x * 32;
@@ -170,6 +191,8 @@ __global__ __launch_bounds__(256) void mlp2_bwd_kernel(Mlp2P p) {
     for (int ot = 0; ot < 4; ++ot) acc[ot] = zero16();
     uint16_t* hrow = p.h + (tok0 + r) * (long)p.H + 4 * hf;
     uint16_t* dhrow = p.dh + (tok0 + r) * (long)p.H + 4 * hf;
+    unsigned long long seed = 0ull;
+    if constexpr (DROP) seed = p.seed ^ (p.seed_dev ? p.seed_dev[0] : 0ull);
     struct Frags { bf16x8_t w1f[8], w2t[OT * 2], w1t[8]; };
     auto load = [&](Frags& f, int s) {
         const int j0 = s * 128 + 32 * w;
@@ -200,6 +223,12 @@ __global__ __launch_bounds__(256) void mlp2_bwd_kernel(Mlp2P p) {
             const bool on = zT[e] > 0.f && live;
             hv[e] = on ? zT[e] : 0.f;
             dv[e] = on ? dT[e] : 0.f;
+        }
+        if constexpr (DROP) {                                       // the forward's mask, recomputed: h is stored post-dropout (the operand of dW2),
+            float ks[16];                                           // dh carries mask * scale inside its gate
+            hidden_keep16(p, seed, tok0 + r, j0, hf, ks);
+#pragma unroll
+            for (int e = 0; e < 16; ++e) { hv[e] *= ks[e]; dv[e] *= ks[e]; }
         }
         if (live) {
 #pragma unroll
@@ -251,7 +280,7 @@ extern "C" int hulc_mlp2_rows_fwd(const float* x, const void* W1, const float* b
     if (int rc = mlp2_check(x, W1, W2, b1, T, K, H, OUT, "hulc_mlp2_rows_fwd: needs K = 128, H a multiple of 128, OUT in {32, 64, 96, 128}, 16-byte aligned operands")) return rc;
     if (!b2 || !y || (uintptr_t)b2 % 16 || (uintptr_t)y % 16) return hulc_fail(-1, "hulc_mlp2_rows_fwd: null or misaligned pointer");
     if ((W1_lo != nullptr) != (W2_lo != nullptr)) return hulc_fail(-3, "hulc_mlp2_rows_fwd: both remainder arrays or none");
-    Mlp2P p = {};
+    Mlp2Arg<false> p = {};
     p.x = x; p.W1 = (const uint16_t*)W1; p.W2 = (const uint16_t*)W2; p.b1 = b1; p.b2 = b2; p.T = T; p.H = H; p.OUT = OUT; p.y = y;
     p.W1lo = (const uint16_t*)W1_lo; p.W2lo = (const uint16_t*)W2_lo;
     const unsigned grid = (unsigned)((T + 31) / 32);
@@ -279,7 +308,7 @@ extern "C" int hulc_mlp2_rows_bwd(const float* x, const float* dy, const void* W
     if (int rc = mlp2_check(x, W1, W2T, b1, T, K, H, OUT, "hulc_mlp2_rows_bwd: needs K = 128, H a multiple of 128, OUT in {32, 64, 96, 128}, 16-byte aligned operands")) return rc;
     if (!dy || !W1T || !h || !dh || (uintptr_t)dy % 16 || (uintptr_t)dx % 16 || (uintptr_t)h % 8 || (uintptr_t)dh % 8)
         return hulc_fail(-1, "hulc_mlp2_rows_bwd: null or misaligned pointer");
-    Mlp2P p = {};
+    Mlp2Arg<false> p = {};
     p.x = x; p.dy = dy; p.W1 = (const uint16_t*)W1; p.W1T = (const uint16_t*)W1T; p.W2T = (const uint16_t*)W2T; p.b1 = b1; p.T = T; p.H = H; p.OUT = OUT;
     p.dx = dx; p.h = (uint16_t*)h; p.dh = (uint16_t*)dh;
     const unsigned grid = (unsigned)((T + 31) / 32);
@@ -291,4 +320,63 @@ extern "C" int hulc_mlp2_rows_bwd(const float* x, const float* dy, const void* W
         default: mlp2_bwd_kernel<4><<<grid, 256, 0, s>>>(p); break;
     }
     return hulc_check_launch("hulc_mlp2_rows_bwd");
+}
+
+// ---- the same head with inverted dropout between the ReLU and fc2 (dropout_vis_fc of the camera yamls) --------------------------------
+namespace {
+int drop_check(float drop_p, const char* who) {
+    if (!(drop_p >= 0.f) || !(drop_p < 1.f)) return hulc_fail(-2, who);
+    return 0;
+}
+template <bool X3>
+void launch_fwd_drop(int ot, unsigned grid, hipStream_t s, const Mlp2Arg<true>& p) {
+    switch (ot) {
+        case 1: mlp2_fwd_kernel<1, X3, true><<<grid, 256, 0, s>>>(p); break;
+        case 2: mlp2_fwd_kernel<2, X3, true><<<grid, 256, 0, s>>>(p); break;
+        case 3: mlp2_fwd_kernel<3, X3, true><<<grid, 256, 0, s>>>(p); break;
+        default: mlp2_fwd_kernel<4, X3, true><<<grid, 256, 0, s>>>(p); break;
+    }
+}
+}  // namespace
+
+// see include/hulc2_amd.h
+extern "C" int hulc_mlp2_rows_fwd_drop(const float* x, const void* W1, const float* b1, const void* W2, const float* b2, const void* W1_lo,
+                                       const void* W2_lo, int T, int K, int H, int OUT, float* y, float drop_p, unsigned long long seed,
+                                       const unsigned long long* seed_dev, void* stream) {
+    if (int rc = drop_check(drop_p, "hulc_mlp2_rows_fwd_drop: drop_p must be in [0, 1)")) return rc;
+    if (drop_p == 0.f) return hulc_mlp2_rows_fwd(x, W1, b1, W2, b2, W1_lo, W2_lo, T, K, H, OUT, y, stream);      // the plain kernels, bit for bit
+    if (int rc = mlp2_check(x, W1, W2, b1, T, K, H, OUT, "hulc_mlp2_rows_fwd_drop: needs K = 128, H a multiple of 128, OUT in {32, 64, 96, 128}, 16-byte aligned operands")) return rc;
+    if (!b2 || !y || (uintptr_t)b2 % 16 || (uintptr_t)y % 16) return hulc_fail(-1, "hulc_mlp2_rows_fwd_drop: null or misaligned pointer");
+    if ((W1_lo != nullptr) != (W2_lo != nullptr)) return hulc_fail(-3, "hulc_mlp2_rows_fwd_drop: both remainder arrays or none");
+    Mlp2Arg<true> p = {};
+    p.x = x; p.W1 = (const uint16_t*)W1; p.W2 = (const uint16_t*)W2; p.b1 = b1; p.b2 = b2; p.T = T; p.H = H; p.OUT = OUT; p.y = y;
+    p.W1lo = (const uint16_t*)W1_lo; p.W2lo = (const uint16_t*)W2_lo;
+    p.drop_p = drop_p; p.seed = seed; p.seed_dev = seed_dev;
+    const unsigned grid = (unsigned)((T + 31) / 32);
+    if (W1_lo) launch_fwd_drop<true>(OUT / 32, grid, (hipStream_t)stream, p);
+    else launch_fwd_drop<false>(OUT / 32, grid, (hipStream_t)stream, p);
+    return hulc_check_launch("hulc_mlp2_rows_fwd_drop");
+}
+
+extern "C" int hulc_mlp2_rows_bwd_drop(const float* x, const float* dy, const void* W1, const float* b1, const void* W1T, const void* W2T, int T, int K,
+                                       int H, int OUT, float* dx, void* h, void* dh, float drop_p, unsigned long long seed,
+                                       const unsigned long long* seed_dev, void* stream) {
+    if (int rc = drop_check(drop_p, "hulc_mlp2_rows_bwd_drop: drop_p must be in [0, 1)")) return rc;
+    if (drop_p == 0.f) return hulc_mlp2_rows_bwd(x, dy, W1, b1, W1T, W2T, T, K, H, OUT, dx, h, dh, stream);
+    if (int rc = mlp2_check(x, W1, W2T, b1, T, K, H, OUT, "hulc_mlp2_rows_bwd_drop: needs K = 128, H a multiple of 128, OUT in {32, 64, 96, 128}, 16-byte aligned operands")) return rc;
+    if (!dy || !W1T || !h || !dh || (uintptr_t)dy % 16 || (uintptr_t)dx % 16 || (uintptr_t)h % 8 || (uintptr_t)dh % 8)
+        return hulc_fail(-1, "hulc_mlp2_rows_bwd_drop: null or misaligned pointer");
+    Mlp2Arg<true> p = {};
+    p.x = x; p.dy = dy; p.W1 = (const uint16_t*)W1; p.W1T = (const uint16_t*)W1T; p.W2T = (const uint16_t*)W2T; p.b1 = b1; p.T = T; p.H = H; p.OUT = OUT;
+    p.dx = dx; p.h = (uint16_t*)h; p.dh = (uint16_t*)dh;
+    p.drop_p = drop_p; p.seed = seed; p.seed_dev = seed_dev;
+    const unsigned grid = (unsigned)((T + 31) / 32);
+    hipStream_t s = (hipStream_t)stream;
+    switch (OUT / 32) {
+        case 1: mlp2_bwd_kernel<1, true><<<grid, 256, 0, s>>>(p); break;
+        case 2: mlp2_bwd_kernel<2, true><<<grid, 256, 0, s>>>(p); break;
+        case 3: mlp2_bwd_kernel<3, true><<<grid, 256, 0, s>>>(p); break;
+        default: mlp2_bwd_kernel<4, true><<<grid, 256, 0, s>>>(p); break;
+    }
+    return hulc_check_launch("hulc_mlp2_rows_bwd_drop");
 }

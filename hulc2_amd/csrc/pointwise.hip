@@ -353,6 +353,106 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
 }
 
 // ------------------------------------------------------------------------------------------------
+// y = LayerNorm(u), u = x / max(||x||_2, 1e-12): F.normalize(x, p=2, dim=1) in front of the encoders' final LayerNorm
+// (vision_network.py:62-64, goal_encoders.py:31-33,68-70).  One wave per row like layernorm_fwd_kernel; the row's three sums each
+// go through wave_sum's fixed butterfly, so a row's bits do not depend on the launch.  Saves 1 / max(||x||, 1e-12), mean, rstd.
+// ------------------------------------------------------------------------------------------------
+#define HULC_L2_EPS 1e-12f
+// u = x * inv as ONE rounded value, the same in the forward and the backward: under -ffp-contract=fast (which disregards contraction pragmas)
+// the compiler forms u - mean as fma(x, inv, -mean) from the unrounded product, an ulp away from the u that went into the mean — times
+// rstd = 316 where the variance is 0 (D = 1, constant rows).  The empty asm makes the product opaque: nothing is fused through it.
+HULC_DEVICE float rounded_product(float a, float b) {
+    float v = a * b;
+    asm volatile("" : "+v"(v));
+    return v;
+}
+__global__ __launch_bounds__(256) void l2norm_layernorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                                   const float* __restrict__ beta, float eps, int R, int D,
+                                                                   float* __restrict__ y, long ld_y, float* __restrict__ inv_out,
+                                                                   float* __restrict__ mean_out, float* __restrict__ rstd_out) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= R) return;
+    float v[4], n2 = 0.f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int c = lane + q * 64;
+        v[q] = c < D ? x[(long)r * D + c] : 0.f;
+        n2 += v[q] * v[q];
+    }
+    const float inv = 1.0f / fmaxf(sqrtf(wave_sum(n2)), HULC_L2_EPS);
+    float s = 0.f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { v[q] = rounded_product(v[q], inv); s += v[q]; }        // (columns past D hold 0)
+    const float mean = wave_sum(s) / D;
+    float ss = 0.f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int c = lane + q * 64;
+        if (c < D) { const float dlt = v[q] - mean; ss += dlt * dlt; }
+    }
+    const float rstd = rsqrtf(wave_sum(ss) / D + eps);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int c = lane + q * 64;
+        if (c < D) y[(long)r * ld_y + c] = (v[q] - mean) * rstd * gamma[c] + beta[c];
+    }
+    if (lane == 0) { inv_out[r] = inv; mean_out[r] = mean; rstd_out[r] = rstd; }
+}
+
+// du = rstd * (g - mean(g) - uhat * mean(g * uhat)), g = dy * gamma (the LayerNorm);  dx = (du - u (u . du)) * inv_norm (the normalisation:
+// where the clamp held, ||x|| < 1e-12, u . du is ~0 and dx = du * 1e12, the gradient of x / 1e-12);  partial dgamma / dbeta per block.
+__global__ __launch_bounds__(256) void l2norm_layernorm_bwd_kernel(const float* __restrict__ dy, long ld_dy, const float* __restrict__ x,
+                                                                   const float* __restrict__ inv_in, const float* __restrict__ mean_in,
+                                                                   const float* __restrict__ rstd_in, const float* __restrict__ gamma, int R,
+                                                                   int D, int rows_per_block, float* __restrict__ dx,
+                                                                   float* __restrict__ partial) {
+    __shared__ float red[4][2][256];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float dg[4] = {0.f, 0.f, 0.f, 0.f}, db[4] = {0.f, 0.f, 0.f, 0.f};
+    const int r0 = blockIdx.x * rows_per_block;
+    for (int r = r0 + wave; r < r0 + rows_per_block && r < R; r += 4) {
+        const float inv = inv_in[r], mean = mean_in[r], rstd = rstd_in[r];
+        float g[4], u[4], xh[4], s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int c = lane + q * 64;
+            g[q] = 0.f; u[q] = 0.f; xh[q] = 0.f;
+            if (c < D) {
+                const float d = dy[(long)r * ld_dy + c];
+                u[q] = rounded_product(x[(long)r * D + c], inv);
+                xh[q] = (u[q] - mean) * rstd;
+                g[q] = d * gamma[c];
+                dg[q] += d * xh[q]; db[q] += d;
+                s1 += g[q]; s2 += g[q] * xh[q];
+            }
+        }
+        s1 = wave_sum(s1) / D; s2 = wave_sum(s2) / D;
+        float du[4], dot = 0.f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            du[q] = (lane + q * 64 < D) ? rstd * (g[q] - s1 - xh[q] * s2) : 0.f;
+            dot += u[q] * du[q];
+        }
+        dot = wave_sum(dot);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int c = lane + q * 64;
+            if (c < D) dx[(long)r * D + c] = (du[q] - u[q] * dot) * inv;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { red[wave][0][lane + q * 64] = dg[q]; red[wave][1][lane + q * 64] = db[q]; }
+    __syncthreads();
+    for (int c = threadIdx.x; c < D; c += 256) {
+        float a = 0.f, b = 0.f;
+        for (int w = 0; w < 4; ++w) { a += red[w][0][c]; b += red[w][1][c]; }
+        partial[(long)blockIdx.x * 2 * D + c] = a;
+        partial[(long)blockIdx.x * 2 * D + D + c] = b;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // column sums: out[n] = sum_m x[m][n]   (bias gradients).  HBM-bound: M*N*sizeof(x) bytes read once.
 // Workgroup = 4 waves; a lane owns 4 adjacent columns (one 16-byte / 8-byte load per row), the waves interleave rows,
 // 4 rows are in flight per lane.  Row blocks are sized so that >= ~1024 workgroups exist; partials are summed in a
@@ -764,6 +864,28 @@ extern "C" int hulc_layernorm_bwd_ld(const float* dy, long ld_dy, const float* p
     return hulc_check_launch("hulc_layernorm_bwd_ld");
 }
 
+// LayerNorm(x / max(||x||_2, 1e-12)) in the _ld form (see include/hulc2_amd.h); workspace: hulc_layernorm_bwd_workspace(R, D)
+extern "C" int hulc_l2norm_layernorm_fwd_ld(const float* x, const float* gamma, const float* beta, float eps, int R, int D, float* y, long ld_y,
+                                            float* inv_norm, float* mean, float* rstd, void* stream) {
+    if (!x || !gamma || !beta || !y || !inv_norm || !mean || !rstd) return hulc_fail(-1, "hulc_l2norm_layernorm_fwd_ld: null pointer");
+    if (D > 256 || D <= 0 || ld_y < D || R < 1) return hulc_fail(-2, "hulc_l2norm_layernorm_fwd_ld: D must be in 1..256, ld_y >= D");
+    l2norm_layernorm_fwd_kernel<<<(R + 3) / 4, 256, 0, (hipStream_t)stream>>>(x, gamma, beta, eps, R, D, y, ld_y, inv_norm, mean, rstd);
+    return hulc_check_launch("hulc_l2norm_layernorm_fwd_ld");
+}
+
+extern "C" int hulc_l2norm_layernorm_bwd_ld(const float* dy, long ld_dy, const float* x, const float* inv_norm, const float* mean, const float* rstd,
+                                            const float* gamma, int R, int D, float* dx, float* dgamma, float* dbeta, int accumulate_params,
+                                            void* ws, void* stream) {
+    if (!dy || !x || !inv_norm || !mean || !rstd || !gamma || !dx || !dgamma || !dbeta || !ws)
+        return hulc_fail(-1, "hulc_l2norm_layernorm_bwd_ld: null pointer");
+    if (D > 256 || D <= 0 || ld_dy < D || R < 1) return hulc_fail(-2, "hulc_l2norm_layernorm_bwd_ld: D must be in 1..256, ld_dy >= D");
+    const int rpb = ln_bwd_rows_per_block(R), nb = (R + rpb - 1) / rpb;
+    hipStream_t s = (hipStream_t)stream;
+    l2norm_layernorm_bwd_kernel<<<nb, 256, 0, s>>>(dy, ld_dy, x, inv_norm, mean, rstd, gamma, R, D, rpb, dx, (float*)ws);
+    reduce_rows_wide_kernel<<<dim3((D + 63) / 64, 2), 1024, 0, s>>>((const float*)ws, dgamma, nb, D, 2 * D, accumulate_params, (long)D, dbeta);
+    return hulc_check_launch("hulc_l2norm_layernorm_bwd_ld");
+}
+
 // ------------------------------------------------------------------------------------------------
 // fan-out of the perceptual embedding emb (N, S, D) to its four consumers in Hulc2.training_step (hulc2.py:380-387 / :228-231): the
 // prior sees emb[:, 0], the visual goal encoder emb[:n_last, -1], the posterior all of it, the action decoder the column slice [lo, hi)
@@ -921,6 +1043,16 @@ extern "C" int hulc_dropout_bwd(const float* dy, float* dx, long n, float drop_p
     if (!dy || !dx) return hulc_fail(-1, "hulc_dropout_bwd: null pointer");
     dropout_bwd_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(dy, dx, n, drop_p, seed, seed_dev);
     return hulc_check_launch("hulc_dropout_bwd");
+}
+// y = x * keep-scale(seed ^ seed_dev[0], i, p): word dropout on the sentence embedding (goal_encoders.py:52-54) — the body of hulc_dropout_bwd
+// under a forward name (the mask applies to data here, to a gradient there)
+extern "C" int hulc_dropout_fwd(const float* x, float* y, long n, float drop_p, unsigned long long seed, const unsigned long long* seed_dev,
+                                void* stream) {
+    if (n == 0) return 0;
+    if (!x || !y) return hulc_fail(-1, "hulc_dropout_fwd: null pointer");
+    if (n < 0 || !(drop_p >= 0.f) || !(drop_p < 1.f)) return hulc_fail(-2, "hulc_dropout_fwd: n >= 0 and drop_p in [0, 1)");
+    dropout_bwd_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(x, y, n, drop_p, seed, seed_dev);
+    return hulc_check_launch("hulc_dropout_fwd");
 }
 
 extern "C" int hulc_relu_bwd(const float* dy, const void* y, int y_dtype, float* dx, long n, float scale, void* stream) {

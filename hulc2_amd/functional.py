@@ -324,12 +324,15 @@ class Mlp2RowsFn(torch.autograd.Function):
     two weight-gradient products for the pass's grouped launch."""
 
     @staticmethod
-    def forward(ctx, x, W1, b1, W2, b2, x3: bool = False):
+    def forward(ctx, x, W1, b1, W2, b2, x3: bool = False, drop_p: float = 0.0, seed: int = 0):
+        """drop_p > 0: inverted dropout between the ReLU and fc2 (fc1's nn.Dropout), mask of element row * H + hidden under `seed` and the
+        device step word — recomputed by the backward launch, nothing is stored"""
         y = _f32(x.shape[0], W2.shape[0], like=x)
         with kn.compute_scope("bf16", fwd_only=True):       # (x3: called inside an exact-forward scope — the operands are the bf16 shadows + remainders)
             lo = (weight_operand(W1, "lo"), weight_operand(W2, "lo")) if x3 else (None, None)
-            kn.mlp2_rows_fwd(x, weight_operand(W1), b1, weight_operand(W2), b2, y, *lo)
+            kn.mlp2_rows_fwd(x, weight_operand(W1), b1, weight_operand(W2), b2, y, *lo, drop_p=drop_p, seed=seed)
         ctx.save_for_backward(x, W1, b1, W2, b2)
+        ctx.drop = (float(drop_p), int(seed))
         return y
 
     @staticmethod
@@ -342,21 +345,56 @@ class Mlp2RowsFn(torch.autograd.Function):
         dx = _f32(T, 128, like=dy) if ctx.needs_input_grad[0] else None
         h = torch.empty(T, H, dtype=torch.bfloat16, device=dy.device)
         dh = torch.empty(T, H, dtype=torch.bfloat16, device=dy.device)
-        kn.mlp2_rows_bwd(x, dy, weight_operand(W1), b1, weight_operand(W1, "t"), weight_operand(W2, "t"), dx, h, dh)
+        kn.mlp2_rows_bwd(x, dy, weight_operand(W1), b1, weight_operand(W1, "t"), weight_operand(W2, "t"), dx, h, dh, drop_p=ctx.drop[0], seed=ctx.drop[1])
         ret = []
         for left, right, W, b, M, N in ((dh, x, W1, b1, H, 128), (dy, h, W2, b2, OUT, H)):
             (dW, a1, rW), (db, a2, rb) = gradsink.dest(W, (M, N), dy), gradsink.dest(b, (M,), dy)
             kn.wgrad(left, right, dW, M, N, T, M, N, N, accumulate=a1, rowsum=db, rowsum_accumulate=a2, defer=rW is None and rb is None)
             ret += [rW, rb]
-        return (dx, *ret, None)
+        return (dx, *ret, None, None, None)
 
 
-def mlp2_rows(x, fc1_w, fc1_b, fc2_w, fc2_b):
-    """fc2(relu(fc1(x))) for x (rows, 128): one launch per direction where hulc_mlp2_rows_* take the shape, else the GEMM chain.  Inside an
-    exact-forward scope of a bf16 step (site "encfc") the launch forms its products from split operands instead of leaving for fp32 GEMMs."""
+def mlp2_rows(x, fc1_w, fc1_b, fc2_w, fc2_b, drop_p: float = 0.0, seed: int = 0):
+    """fc2(dropout(relu(fc1(x)))) for x (rows, 128): one launch per direction where hulc_mlp2_rows_* take the shape, else the GEMM chain.  Inside an
+    exact-forward scope of a bf16 step (site "encfc") the launch forms its products from split operands instead of leaving for fp32 GEMMs.
+    drop_p > 0: both paths drop the same hidden elements for the same seed (index row * H + hidden)."""
     if kn.mlp2_rows_ok(x, fc1_w, fc2_w):
+        if drop_p > 0.0:
+            return Mlp2RowsFn.apply(x, fc1_w, fc1_b, fc2_w, fc2_b, kn.exact_site_in_bf16_step(), float(drop_p), int(seed))
         return Mlp2RowsFn.apply(x, fc1_w, fc1_b, fc2_w, fc2_b, kn.exact_site_in_bf16_step())
+    if drop_p > 0.0:
+        return mlp(x, [(fc1_w, fc1_b, True), (fc2_w, fc2_b, False)], drops=(drop_p, 0.0), seed=seed)
     return mlp(x, [(fc1_w, fc1_b, True), (fc2_w, fc2_b, False)])
+
+
+class WordDropoutFn(torch.autograd.Function):
+    """y = x * keep-scale (hulc_dropout_fwd); the backward is hulc_dropout_bwd under the same seed and device word.  On the configured path
+    the sentence embedding is data (SBERT is frozen, embeddings come precomputed) and no backward ever runs."""
+
+    @staticmethod
+    def forward(ctx, x, p: float, seed: int):
+        x = _c(x)
+        y = torch.empty_like(x)
+        kn.dropout_fwd(x, y, x.numel(), p, seed)
+        ctx.meta = (p, seed)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dy = _c(dy)
+        dx = torch.empty_like(dy)
+        kn.dropout_bwd(dy, dx, dy.numel(), *ctx.meta)
+        return dx, None, None
+
+
+def word_dropout(x, p: float, seed: int):
+    """nn.Dropout(p) on the (B, 384) sentence embedding in front of the language goal MLP (goal_encoders.py:52-54): one pointwise launch on
+    element index row * 384 + column.  p == 0: x itself, nothing is launched."""
+    if p <= 0.0:
+        return x
+    if x.dtype != torch.float32:
+        x = x.float()
+    return WordDropoutFn.apply(x, float(p), int(seed))
 
 
 def dual_mlp(xa, layers_a, xb, layers_b, exact_b: bool = False):
@@ -632,13 +670,23 @@ def spatial_softmax(a, xmap, ymap, temperature):
 @_scoped
 class LayerNormFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, o, gamma, beta, eps: float, drop_p: float, seed: int):
+    def forward(ctx, x, o, gamma, beta, eps: float, drop_p: float, seed: int, l2: bool = False):
+        """l2: LayerNorm(F.normalize(x, p=2, dim=-1)) — the encoders' l2_normalize switches; no residual branch there"""
         D = x.shape[-1]
         x2 = _c(x.reshape(-1, D))
         o2 = _c(o.reshape(-1, D)) if o is not None else None
         R = x2.shape[0]
         y = _f32(R, D, like=x2)
         mean, rstd = _f32(R, like=x2), _f32(R, like=x2)
+        ctx.l2 = bool(l2)
+        if l2:
+            assert o is None, "l2-normalised LayerNorm has no residual branch"
+            inv = _f32(R, like=x2)
+            kn.l2norm_layernorm_fwd_ld(x2, gamma, beta, eps, R, D, y, D, inv, mean, rstd)
+            ctx.save_for_backward(x2, mean, rstd, gamma, inv)
+            ctx.beta = beta
+            ctx.meta = (x.shape, False, 0.0, 0)
+            return y.reshape(x.shape)
         pre = _f32(R, D, like=x2) if o2 is not None else None
         kn.layernorm_fwd(x2, o2, drop_p, seed, gamma, beta, eps, R, D, pre, y, mean, rstd)
         ctx.save_for_backward(pre if pre is not None else x2, mean, rstd, gamma)
@@ -648,11 +696,15 @@ class LayerNormFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        pre, mean, rstd, gamma = ctx.saved_tensors
+        pre, mean, rstd, gamma = ctx.saved_tensors[:4]
         shape, has_o, drop_p, seed = ctx.meta
         R, D = pre.shape
         dy2 = _c(dy.reshape(R, D))
         dpre = _f32(R, D, like=dy2)
+        if ctx.l2:
+            (dg, db), acc, (rg, rb) = gradsink.joint((gamma, ctx.beta), None, dy2)
+            kn.l2norm_layernorm_bwd_ld(dy2, D, pre, ctx.saved_tensors[4], mean, rstd, gamma, R, D, dpre, dg, db, accumulate_params=acc)
+            return dpre.reshape(shape), None, rg, rb, None, None, None, None
         do = _f32(R, D, like=dy2) if (has_o and drop_p > 0) else None
         (dg, db), acc, (rg, rb) = gradsink.joint((gamma, ctx.beta), None, dy2)      # sunk: straight into the gradient arena (no AccumulateGrad adds)
         kn.layernorm_bwd(dy2, pre, mean, rstd, gamma, R, D, dpre, do, drop_p, seed, dg, db, accumulate_params=acc)
@@ -660,10 +712,13 @@ class LayerNormFn(torch.autograd.Function):
         d_o = None
         if has_o:
             d_o = (do if do is not None else dpre).reshape(shape)
-        return dx, d_o, rg, rb, None, None, None
+        return dx, d_o, rg, rb, None, None, None, None
 
 
-def layer_norm(x, gamma, beta, eps=1e-5):
+def layer_norm(x, gamma, beta, eps=1e-5, l2: bool = False):
+    """l2: F.normalize(x, p=2, dim=-1) in front of the LayerNorm, one launch each way (hulc_l2norm_layernorm_*_ld)"""
+    if l2:
+        return LayerNormFn.apply(x, None, gamma, beta, eps, 0.0, 0, True)
     return LayerNormFn.apply(x, None, gamma, beta, eps, 0.0, 0)
 
 
@@ -680,6 +735,11 @@ class LayerNormCatFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, dim: int, eps: float, n: int, *args):
+        """eps: the LayerNorms' eps, or a tuple (eps, l2_0, .., l2_{n-1}) — block i is F.normalize'd (p=2, along its columns) in front of its
+        LayerNorm where l2_i is set (the cameras and the goal encoders each have their own yaml switch)"""
+        l2 = (False,) * n
+        if isinstance(eps, tuple):
+            eps, l2 = float(eps[0]), tuple(bool(f) for f in eps[1:])
         xs = [_c(x.reshape(-1, x.shape[-1])) for x in args[:n]]
         params = args[n:]
         if dim == 0:
@@ -700,22 +760,28 @@ class LayerNormCatFn(torch.autograd.Function):
             ld = D
         y = _f32(R, D, like=xs[0])
         flat = y.view(-1)
-        stats = []
+        stats, invs = [], []
         for i, x in enumerate(xs):
             r, d = x.shape
             mean, rstd = _f32(r, like=x), _f32(r, like=x)
-            kn.layernorm_fwd_ld(x, params[2 * i], params[2 * i + 1], eps, r, d, flat[offs[i]:], ld, mean, rstd)
+            if l2[i]:
+                inv = _f32(r, like=x)
+                kn.l2norm_layernorm_fwd_ld(x, params[2 * i], params[2 * i + 1], eps, r, d, flat[offs[i]:], ld, inv, mean, rstd)
+                invs.append(inv)
+            else:
+                kn.layernorm_fwd_ld(x, params[2 * i], params[2 * i + 1], eps, r, d, flat[offs[i]:], ld, mean, rstd)
             stats += [mean, rstd]
-        ctx.save_for_backward(*xs, *stats, *[params[2 * i] for i in range(n)])
+        ctx.save_for_backward(*xs, *stats, *[params[2 * i] for i in range(n)], *invs)
         ctx.betas = [params[2 * i + 1] for i in range(n)]
         ctx.meta = (n, offs, ld, [tuple(a.shape) for a in args[:n]])
+        ctx.l2 = l2
         return y
 
     @staticmethod
     def backward(ctx, dy):
         n, offs, ld, shapes = ctx.meta
         sv = ctx.saved_tensors
-        xs, stats, gammas = sv[:n], sv[n:3 * n], sv[3 * n:]
+        xs, stats, gammas, invs = sv[:n], sv[n:3 * n], sv[3 * n:4 * n], list(sv[4 * n:])
         dyf = _c(dy).view(-1)
         dxs, dps = [], []
         for i in range(n):
@@ -723,16 +789,24 @@ class LayerNormCatFn(torch.autograd.Function):
             r, d = x.shape
             dx = _f32(r, d, like=dyf)
             (dg, db), acc, rets = gradsink.joint((gamma, beta), None, dyf)
-            kn.layernorm_bwd_ld(dyf[offs[i]:], ld, x, stats[2 * i], stats[2 * i + 1], gamma, r, d, dx, dg, db, accumulate_params=acc)
+            if ctx.l2[i]:
+                kn.l2norm_layernorm_bwd_ld(dyf[offs[i]:], ld, x, invs.pop(0), stats[2 * i], stats[2 * i + 1], gamma, r, d, dx, dg, db, accumulate_params=acc)
+            else:
+                kn.layernorm_bwd_ld(dyf[offs[i]:], ld, x, stats[2 * i], stats[2 * i + 1], gamma, r, d, dx, dg, db, accumulate_params=acc)
             dxs.append(dx.reshape(shapes[i]))
             dps += rets
         return (None, None, None, *dxs, *dps)
 
 
-def layer_norm_cat(xs, norms, dim: int):
-    """cat([F.layer_norm(x_i, ...)], dim) for nn.LayerNorm modules `norms` (2-D results: rows = all leading axes flattened)"""
+def layer_norm_cat(xs, norms, dim: int, l2=None):
+    """cat([F.layer_norm(x_i, ...)], dim) for nn.LayerNorm modules `norms` (2-D results: rows = all leading axes flattened).  l2: one flag per
+    block — that block is F.normalize'd (p=2, last axis) in front of its LayerNorm"""
     params = [t for m in norms for t in (m.weight, m.bias)]
-    return LayerNormCatFn.apply(int(dim), float(norms[0].eps), len(xs), *xs, *params)
+    eps = float(norms[0].eps)
+    if l2 is not None and any(l2):
+        assert len(l2) == len(xs)
+        eps = (eps, *[bool(f) for f in l2])
+    return LayerNormCatFn.apply(int(dim), eps, len(xs), *xs, *params)
 
 
 @_scoped

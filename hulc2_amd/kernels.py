@@ -693,6 +693,11 @@ def dropout_bwd(dy, dx, n, drop_p, seed):
     _call("hulc_dropout_bwd", dy, dx, n, drop_p, seed, _sd(dy, drop_p))
 
 
+def dropout_fwd(x, y, n, drop_p, seed):
+    """y = x * keep-scale(seed ^ the device step word, i, drop_p): word dropout on the sentence embedding"""
+    _call("hulc_dropout_fwd", x, y, n, drop_p, int(seed) & 0xFFFFFFFFFFFFFFFF, _sd(x, drop_p))
+
+
 def relu_bwd(dy, y, dx, n, scale=1.0):
     _call("hulc_relu_bwd", dy, y, _dt(y), dx, n, scale)
 
@@ -1156,16 +1161,27 @@ def mlp2_rows_ok(x, W1, W2) -> bool:
             and x.data_ptr() % 16 == 0)
 
 
-def mlp2_rows_fwd(x, W1, b1, W2, b2, y, W1_lo=None, W2_lo=None):
+def mlp2_rows_fwd(x, W1, b1, W2, b2, y, W1_lo=None, W2_lo=None, drop_p=0.0, seed=0):
+    """drop_p > 0: the launch with inverted dropout on the hidden tile (hulc_mlp2_rows_fwd_drop, element index row * H + hidden); drop_p == 0
+    is the plain launch, name and arguments as ever"""
     T, H, OUT = x.shape[0], W1.shape[0], W2.shape[0]
+    fl, nb = 2.0 * T * H * (128 + OUT) * (3 if W1_lo is not None else 1), _nbytes(x, W1, W2, y)
+    if drop_p > 0.0:
+        _call("hulc_mlp2_rows_fwd_drop", x, W1, b1, W2, b2, W1_lo, W2_lo, T, 128, H, OUT, y, drop_p, int(seed) & 0xFFFFFFFFFFFFFFFF, _sd(x, drop_p),
+              key=("mlp2_rows_fwd_drop", T, H, OUT, W1_lo is not None), flops=fl, nbytes=nb)
+        return
     _call("hulc_mlp2_rows_fwd", x, W1, b1, W2, b2, W1_lo, W2_lo, T, 128, H, OUT, y, key=("mlp2_rows_fwd", T, H, OUT, W1_lo is not None),
-          flops=2.0 * T * H * (128 + OUT) * (3 if W1_lo is not None else 1), nbytes=_nbytes(x, W1, W2, y))
+          flops=fl, nbytes=nb)
 
 
-def mlp2_rows_bwd(x, dy, W1, b1, W1T, W2T, dx, h, dh):
+def mlp2_rows_bwd(x, dy, W1, b1, W1T, W2T, dx, h, dh, drop_p=0.0, seed=0):
     T, H, OUT = x.shape[0], W1.shape[0], W2T.shape[1]
-    _call("hulc_mlp2_rows_bwd", x, dy, W1, b1, W1T, W2T, T, 128, H, OUT, dx, h, dh, key=("mlp2_rows_bwd", T, H, OUT),
-          flops=2.0 * T * H * (2 * 128 + OUT), nbytes=_nbytes(x, dy, W1, W1T, W2T, dx, h, dh))
+    fl, nb = 2.0 * T * H * (2 * 128 + OUT), _nbytes(x, dy, W1, W1T, W2T, dx, h, dh)
+    if drop_p > 0.0:
+        _call("hulc_mlp2_rows_bwd_drop", x, dy, W1, b1, W1T, W2T, T, 128, H, OUT, dx, h, dh, drop_p, int(seed) & 0xFFFFFFFFFFFFFFFF, _sd(x, drop_p),
+              key=("mlp2_rows_bwd_drop", T, H, OUT), flops=fl, nbytes=nb)
+        return
+    _call("hulc_mlp2_rows_bwd", x, dy, W1, b1, W1T, W2T, T, 128, H, OUT, dx, h, dh, key=("mlp2_rows_bwd", T, H, OUT), flops=fl, nbytes=nb)
 
 
 def txl_block_desc(emb, pos, pos_ids, B, S, H, FF, drop_p, seed_pos, eps, layers, pooled=None, dpooled=None, demb=None, share=None):
@@ -1413,6 +1429,16 @@ def layernorm_fwd_ld(x, gamma, beta, eps, R, D, y, ld_y, mean, rstd):
 def layernorm_bwd_ld(dy, ld_dy, pre, mean, rstd, gamma, R, D, dpre, dgamma, dbeta, accumulate_params=False):
     ws = _ws(_L.load().hulc_layernorm_bwd_workspace(R, D), dy.device)
     _call("hulc_layernorm_bwd_ld", dy, ld_dy, pre, mean, rstd, gamma, R, D, dpre, dgamma, dbeta, accumulate_params, ws)
+
+
+def l2norm_layernorm_fwd_ld(x, gamma, beta, eps, R, D, y, ld_y, inv_norm, mean, rstd):
+    """y = LayerNorm(x / max(||x||_2, 1e-12)), rows ld_y apart (F.normalize in front of an encoder's final LayerNorm)"""
+    _call("hulc_l2norm_layernorm_fwd_ld", x, gamma, beta, eps, R, D, y, ld_y, inv_norm, mean, rstd)
+
+
+def l2norm_layernorm_bwd_ld(dy, ld_dy, x, inv_norm, mean, rstd, gamma, R, D, dx, dgamma, dbeta, accumulate_params=False):
+    ws = _ws(_L.load().hulc_layernorm_bwd_workspace(R, D), dy.device)
+    _call("hulc_l2norm_layernorm_bwd_ld", dy, ld_dy, x, inv_norm, mean, rstd, gamma, R, D, dx, dgamma, dbeta, accumulate_params, ws)
 
 
 def world_to_tcp(act, robot_obs, n, obs_dim, out):

@@ -313,7 +313,8 @@ class Hulc2(LightningModule):
                                                    self.language_goal.mlp_layers()))
                         else:
                             pre = [self.language_goal(db["lang"], pre_ln=True) if "lang" in scope else self.visual_goal(emb_last, pre_ln=True) for scope, db in mods]
-                        goal_all = HF.layer_norm_cat(pre, [self.language_goal.ln if "lang" in scope else self.visual_goal.ln for scope, _ in mods], dim=0)
+                        goal_encs = [self.language_goal if "lang" in scope else self.visual_goal for scope, _ in mods]
+                        goal_all = HF.layer_norm_cat(pre, [g.ln for g in goal_encs], dim=0, l2=[g.l2_normalize_output for g in goal_encs])
                     goals = [None] * len(mods)
                 else:
                     embs = [emb_all[i * B:(i + 1) * B] for i in range(len(mods))]
@@ -370,7 +371,7 @@ class Hulc2(LightningModule):
         else:
             for self.modality_scope, db in mods:
                 with kn.site_scope("enc"):
-                    emb = self.perceptual_encoder(db["rgb_obs"], db["depth_obs"], db["robot_obs"])
+                    emb = self._encode_modality(db)
                 with self._goal_site("lang" in self.modality_scope):
                     latent_goal = self.language_goal(db["lang"]) if "lang" in self.modality_scope else self.visual_goal(emb[:, -1])
                 with kn.site_scope("prior"):
@@ -418,6 +419,29 @@ class Hulc2(LightningModule):
         logged.append(("train/action_loss", logs[1], dict(on_step=False, on_epoch=True, batch_size=total_bs)))
         logged.append(("train/total_loss", total_loss, dict(on_step=False, on_epoch=True, batch_size=total_bs)))
         return total_loss, logged
+
+    def _encode_modality(self, db):
+        """the perceptual encoder on ONE modality's frames (rows restart at 0 per call): ConcatEncoders hands the camera heads' fc dropout
+        the modality's own RNG site, so vis and lang draw different masks; other encoder classes take the reference's three arguments"""
+        from hulc2_amd.models.perceptual_encoders.concat_encoders import ConcatEncoders
+        if isinstance(self.perceptual_encoder, ConcatEncoders):
+            return self.perceptual_encoder(db["rgb_obs"], db["depth_obs"], db["robot_obs"], modality_scope=self.modality_scope)
+        return self.perceptual_encoder(db["rgb_obs"], db["depth_obs"], db["robot_obs"])
+
+    def regulariser_key(self) -> tuple:
+        """the encoder regularisers a captured step has baked in as kernel choices and arguments (dropout_vis_fc of both cameras, word_dropout_p,
+        the four l2 flags): part of what keys a captured graph (StepNode._signature, ArenaTrainer.capture / replay)"""
+        key = []
+        enc = self.perceptual_encoder
+        for name in ("rgb_static_encoder", "rgb_gripper_encoder"):
+            e = getattr(enc, name, None)
+            key.append((float(getattr(e, "drop_p", 0.0)), bool(getattr(e, "l2_normalize_output", False))) if e is not None else None)
+        key.append(bool(getattr(self.visual_goal, "l2_normalize_output", False)))
+        lg = self.language_goal
+        if lg is not None:
+            m0 = lg.mlp[0] if hasattr(lg, "mlp") else None
+            key.append((float(m0.p) if (isinstance(m0, nn.Dropout) and lg.training) else 0.0, bool(getattr(lg, "l2_normalize_output", False))))
+        return tuple(key)
 
     @staticmethod
     def _batchable(mods) -> bool:

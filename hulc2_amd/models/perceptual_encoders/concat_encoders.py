@@ -71,9 +71,17 @@ class ConcatEncoders(nn.Module):
     def latent_size(self):
         return self._latent_size
 
-    def forward(self, imgs: Dict[str, torch.Tensor], depth_imgs: Dict[str, torch.Tensor], state_obs: torch.Tensor) -> torch.Tensor:
+    def _set_scope(self, modality_scope) -> None:
+        """the fc-dropout site of the camera heads: None = the stacked call's (rows distinct), else the modality's own (rows restart at 0)"""
+        for e in (self.rgb_static_encoder, self.rgb_gripper_encoder):
+            if e is not None and hasattr(e, "modality_scope"):
+                e.modality_scope = modality_scope
+
+    def forward(self, imgs: Dict[str, torch.Tensor], depth_imgs: Dict[str, torch.Tensor], state_obs: torch.Tensor,
+                modality_scope: Optional[str] = None) -> torch.Tensor:
         if isinstance(imgs, (list, tuple)):             # several modalities at once (Hulc2.training_step): see forward_multi
             return self.forward_multi(imgs)
+        self._set_scope(modality_scope)
         x, sh, ix, b, s = self._frames(imgs, "rgb_static")
         enc = self.rgb_static_encoder(x, sh, self.aug_pad["rgb_static"], ix).reshape(b, s, -1)
         if "rgb_gripper" in imgs and self.rgb_gripper_encoder is not None:
@@ -86,6 +94,7 @@ class ConcatEncoders(nn.Module):
     def forward_multi(self, imgs_list) -> torch.Tensor:
         """Several observation dicts of identical shapes (the modalities of one training step) through the shared encoders
         in one pass: rows of the result are modality-major, (sum B, S, latent).  Same arithmetic per frame as `forward`."""
+        self._set_scope(None)
         fr = [self._frames(im, "rgb_static") for im in imgs_list]
         b, s = fr[0][3], fr[0][4]
         has_gripper = self.rgb_gripper_encoder is not None and all("rgb_gripper" in im for im in imgs_list)
@@ -117,7 +126,9 @@ class ConcatEncoders(nn.Module):
             g = run_g()
         if fuse_ln:
             from hulc2_amd import functional as HF
-            enc = HF.layer_norm_cat([enc, g], [self.rgb_static_encoder.ln, self.rgb_gripper_encoder.ln], dim=-1).reshape(len(fr) * b, s, -1)
+            enc = HF.layer_norm_cat([enc, g], [self.rgb_static_encoder.ln, self.rgb_gripper_encoder.ln], dim=-1,
+                                    l2=[getattr(e, "l2_normalize_output", False) for e in (self.rgb_static_encoder, self.rgb_gripper_encoder)]
+                                    ).reshape(len(fr) * b, s, -1)
         elif has_gripper:
             enc = torch.cat([enc, g], dim=-1)
         self.current_visual_embedding = enc.detach()

@@ -15,6 +15,28 @@ from hulc2_amd import functional as HF
 from hulc2_amd import kernels as kn
 
 
+# Dropout sites of the camera heads' fc1 dropout (dropout_vis_fc; the per-step stream comes from the device step state).  The stacked call
+# (ConcatEncoders.forward_multi: all modalities' frames in one tensor) needs one site, its rows are distinct; a call per modality restarts
+# its rows at 0 and takes the modality's own site, like plan_recognition_net.trunk_site.
+STATIC_FC_SITE = 0x5EED4001
+STATIC_FC_MODALITY_SITES = {"vis": 0x5EED4101, "lang": 0x5EED4201}
+GRIPPER_FC_SITE = 0x5EED5001
+GRIPPER_FC_MODALITY_SITES = {"vis": 0x5EED5101, "lang": 0x5EED5201}
+
+
+def fc_site(stacked: int, per_modality: dict, modality_scope) -> int:
+    if modality_scope is None:
+        return stacked
+    return per_modality["lang" if "lang" in modality_scope else "vis"]
+
+
+def check_dropout_p(p: float, name: str) -> float:
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"{name} must be in [0, 1), got {p} (the kernels scale kept elements by 1 / (1 - p))")
+    return p
+
+
 class SpatialSoftmax(nn.Module):
     """Buffers follow the reference's quirk (vision_network.py:88-92): x_map varies along rows."""
 
@@ -46,9 +68,12 @@ class VisionNetwork(nn.Module):
                  l2_normalize_output: bool, visual_features: int, num_c: int, use_sinusoid: bool,
                  spatial_softmax_temp: float):
         super().__init__()
-        if activation_function != "ReLU" or use_sinusoid or l2_normalize_output or dropout_vis_fc != 0.0:
-            raise NotImplementedError("hulc2_amd VisionNetwork implements the configured path only: ReLU, no sinusoid, "
-                                      "no l2-normalise, dropout_vis_fc 0 (conf/model/perceptual_encoder/rgb_static/default.yaml)")
+        if activation_function != "ReLU" or use_sinusoid:
+            raise NotImplementedError("hulc2_amd VisionNetwork implements ReLU without the sinusoid map; dropout_vis_fc in [0, 1) and "
+                                      "l2_normalize_output are supported (conf/model/perceptual_encoder/rgb_static/default.yaml)")
+        dropout_vis_fc = check_dropout_p(dropout_vis_fc, "dropout_vis_fc")
+        self.l2_normalize_output = bool(l2_normalize_output)
+        self.modality_scope = None           # set by ConcatEncoders in front of a per-modality call: selects the dropout site
         self.act_fn = nn.ReLU()
         w, h = input_width, input_height
         for k, s in ((8, 4), (4, 2), (3, 1)):
@@ -74,10 +99,16 @@ class VisionNetwork(nn.Module):
         a3 = HF.conv_stack(x, self.conv_params(), grad_premasked=True, aug_pad=aug_pad, aug_shifts=aug_shift, frame_index=frame_index)      # (N, 21, 21, 64) NHWC
         feat = self.spatial_softmax(a3)                                     # (N, 128)
         with kn.site_scope("encfc"):         # (selective precision, DESIGN §5: the fc tail is one of the sites HULC_FP32_SITES can make exact)
-            y = HF.mlp2_rows(feat, self.fc1[0].weight, self.fc1[0].bias, self.fc2.weight, self.fc2.bias)
+            y = HF.mlp2_rows(feat, self.fc1[0].weight, self.fc1[0].bias, self.fc2.weight, self.fc2.bias, drop_p=self.drop_p,
+                             seed=fc_site(STATIC_FC_SITE, STATIC_FC_MODALITY_SITES, self.modality_scope))
         if pre_ln:                # ConcatEncoders applies the LayerNorms of both cameras while writing the concatenated embedding
             return y
-        return HF.layer_norm(y, self.ln.weight, self.ln.bias, self.ln.eps)
+        return HF.layer_norm(y, self.ln.weight, self.ln.bias, self.ln.eps, l2=self.l2_normalize_output)
+
+    @property
+    def drop_p(self) -> float:
+        """fc1's nn.Dropout is active iff the module is in training mode (nn.Dropout's rule)"""
+        return float(self.fc1[2].p) if self.training else 0.0
 
     @staticmethod
     def calc_out_size(w: int, h: int, kernel_size: int, padding: int, stride: int) -> Tuple[int, int]:

@@ -11,6 +11,7 @@ import torch.nn as nn
 
 from hulc2_amd import functional as HF
 from hulc2_amd import kernels as kn
+from hulc2_amd.models.perceptual_encoders.vision_network import GRIPPER_FC_MODALITY_SITES, GRIPPER_FC_SITE, check_dropout_p, fc_site
 
 
 def nature_cnn(act_fn, num_c):
@@ -22,9 +23,12 @@ class VisionNetwork(nn.Module):
     def __init__(self, input_width: int, input_height: int, conv_encoder: str, activation_function: str,
                  dropout_vis_fc: float, l2_normalize_output: bool, visual_features: int, num_c: int):
         super().__init__()
-        if conv_encoder != "nature_cnn" or activation_function != "ReLU" or l2_normalize_output or dropout_vis_fc != 0.0:
-            raise NotImplementedError("hulc2_amd gripper VisionNetwork implements the configured path only: nature_cnn, ReLU, "
-                                      "no l2-normalise, dropout 0 (conf/model/perceptual_encoder/rgb_gripper/default.yaml)")
+        if conv_encoder != "nature_cnn" or activation_function != "ReLU":
+            raise NotImplementedError("hulc2_amd gripper VisionNetwork implements nature_cnn with ReLU; dropout_vis_fc in [0, 1) and "
+                                      "l2_normalize_output are supported (conf/model/perceptual_encoder/rgb_gripper/default.yaml)")
+        dropout_vis_fc = check_dropout_p(dropout_vis_fc, "dropout_vis_fc")
+        self.l2_normalize_output = bool(l2_normalize_output)
+        self.modality_scope = None           # set by ConcatEncoders in front of a per-modality call: selects the dropout site
         self.act_fn = nn.ReLU()
         self.conv_model = nature_cnn(self.act_fn, num_c)
         self.fc1 = nn.Sequential(nn.Linear(128, 512), self.act_fn, nn.Dropout(dropout_vis_fc))
@@ -51,10 +55,16 @@ class VisionNetwork(nn.Module):
         c = self.conv_model
         with kn.site_scope("encfc"):         # (selective precision)
             y = HF.flatten_linear_relu(a3, c[7].weight, c[7].bias)
-            y = HF.mlp2_rows(y, self.fc1[0].weight, self.fc1[0].bias, self.fc2.weight, self.fc2.bias)
+            y = HF.mlp2_rows(y, self.fc1[0].weight, self.fc1[0].bias, self.fc2.weight, self.fc2.bias, drop_p=self.drop_p,
+                             seed=fc_site(GRIPPER_FC_SITE, GRIPPER_FC_MODALITY_SITES, self.modality_scope))
         if pre_ln:
             return y
-        return HF.layer_norm(y, self.ln.weight, self.ln.bias, self.ln.eps)
+        return HF.layer_norm(y, self.ln.weight, self.ln.bias, self.ln.eps, l2=self.l2_normalize_output)
+
+    @property
+    def drop_p(self) -> float:
+        """fc1's nn.Dropout is active iff the module is in training mode (nn.Dropout's rule)"""
+        return float(self.fc1[2].p) if self.training else 0.0
 
     @staticmethod
     def calc_out_size(w: int, h: int, kernel_size: int, padding: int, stride: int) -> Tuple[int, int]:

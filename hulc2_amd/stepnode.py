@@ -185,7 +185,7 @@ class StepNode:
         kl_beta = "device" if getattr(m, "kl_beta_on_device", False) else float(m.kl_beta)
         return (tuple((path, tuple(t.shape), t.dtype, t.device) for path, t in leaves), kn.base_mode(), kn.get_compute(),
                 switches.graph_key(), kn.concurrent_streams(), kn.fork_branches(), kl_beta, float(m.kl_balancing_mix),
-                float(m.clip_auxiliary_loss_beta), bool(m.use_clip_auxiliary_loss))
+                float(m.clip_auxiliary_loss_beta), bool(m.use_clip_auxiliary_loss), m.regulariser_key())
 
     def usable(self) -> bool:
         """the keeper's parameter list is still the model's trainable set.  (A live `.grad` is NOT a reason to leave the node — round 6, ADVICE

@@ -751,6 +751,7 @@ class ArenaTrainer(WeightKeeper):
         return j == k - 1
 
     # ---- KL annealing: the KL weight as a device scalar the captured KL launches read (Hulc2.set_kl_beta) --------------------------------
+    _reg_captured = None           # Hulc2.regulariser_key() of the captured graphs (dropout probabilities, l2 flags)
     _kl_captured = None            # the by-value KL weight baked into the captured graphs; None: no graphs, or they read the model's device word
     _kl_schedule = None            # the attached annealing rule (set_kl_schedule)
 
@@ -1010,6 +1011,12 @@ class ArenaTrainer(WeightKeeper):
         # a KL weight taken by value is baked into graph_fb: replay() refuses to run it under another one
         kl = getattr(self.model, "kl_beta", None)
         self._kl_captured = None if (kl is None or getattr(self.model, "kl_beta_on_device", False)) else float(kl)
+        # the encoder regularisers (dropout probabilities, l2 flags) are kernel choices and by-value arguments of graph_fb
+        self._reg_captured = self._regulariser_key()
+
+    def _regulariser_key(self):
+        key = getattr(self.model, "regulariser_key", None)
+        return key() if key is not None else None
 
     def replay(self) -> torch.Tensor:
         if self.graph_fb is None:
@@ -1018,6 +1025,10 @@ class ArenaTrainer(WeightKeeper):
             raise RuntimeError(f"ArenaTrainer.replay: the graphs were captured with kl_beta = {self._kl_captured!r} as a kernel argument and cannot "
                                f"see model.kl_beta = {float(self.model.kl_beta)!r}: set the weight through ArenaTrainer.set_kl_beta (the captured "
                                "launches then read a device scalar) and call capture() again")
+        if self._regulariser_key() != self._reg_captured:
+            raise RuntimeError(f"ArenaTrainer.replay: the graphs were captured with the encoder regularisers {self._reg_captured!r} and the model "
+                               f"now has {self._regulariser_key()!r} (dropout_vis_fc / word_dropout_p / l2 flags, or train / eval mode): call "
+                               "capture() again")
         if self.accumulate_grad_batches > 1:
             with self.gpu_section():
                 if self.micro_batch == 0:            # a window opens: the optimizer step count of the pass that will close it

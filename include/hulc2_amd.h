@@ -475,6 +475,38 @@ int hulc_mlp2_rows_fwd(const float* x, const void* W1, const float* b1, const vo
 int hulc_mlp2_rows_bwd(const float* x, const float* dy, const void* W1, const float* b1, const void* W1T, const void* W2T, int T, int K, int H, int OUT,
                        float* dx, void* h, void* dh, void* stream);
 
+/* (added under ABI 7 — new symbols only; every earlier prototype and hulc_abi_version() are unchanged.)  ENCODER REGULARISERS: the switches
+ * of conf/model/perceptual_encoder/{rgb_static,rgb_gripper}/default.yaml, visual_goal/default.yaml and language_goal/default.yaml.
+ *
+ * hulc_mlp2_rows_fwd_drop / _bwd_drop: the head above with inverted dropout between the ReLU and fc2 — fc1 = Sequential(Linear, ReLU,
+ * Dropout(dropout_vis_fc)) (vision_network.py:49-51, vision_network_gripper.py:76-78) — on the register-resident hidden tile.  Hidden unit j
+ * of row t is kept with the counter RNG's keep-scale of element t * H + j under seed ^ seed_dev[0] (seed_dev may be NULL): the element the
+ * GEMM epilogue (hulc_gemm_desc.drop_p) drops in the same (T, H) matrix for the same seed.  Backward recomputes the mask: the h it stores is
+ * post-dropout (the operand of dW2) and dh carries mask * scale inside its ReLU gate.  drop_p == 0 runs the plain entry points' kernels
+ * (bit-identical results); drop_p outside [0, 1) is refused (-2).  Every other argument and refusal as hulc_mlp2_rows_fwd / _bwd. */
+int hulc_mlp2_rows_fwd_drop(const float* x, const void* W1, const float* b1, const void* W2, const float* b2, const void* W1_lo, const void* W2_lo,
+                            int T, int K, int H, int OUT, float* y, float drop_p, unsigned long long seed, const unsigned long long* seed_dev,
+                            void* stream);
+int hulc_mlp2_rows_bwd_drop(const float* x, const float* dy, const void* W1, const float* b1, const void* W1T, const void* W2T, int T, int K, int H,
+                            int OUT, float* dx, void* h, void* dh, float drop_p, unsigned long long seed, const unsigned long long* seed_dev,
+                            void* stream);
+/* y = LayerNorm(x / max(||x||_2, 1e-12)): F.normalize(x, p=2, dim=1) between fc2 / the goal MLP and `ln` (l2_normalize_output,
+ * l2_normalize_goal_embeddings: vision_network.py:62-64, goal_encoders.py:31-33,68-70), in the form of hulc_layernorm_fwd_ld / _bwd_ld: x (R, D)
+ * contiguous, row r of y at y + r * ld_y, the incoming gradient read in place with row pitch ld_dy, D in 1..256.  Forward saves
+ * inv_norm[r] = 1 / max(||x_r||, 1e-12), mean and rstd of the normalised row; backward: du from the LayerNorm, dx = (du - u (u . du)) *
+ * inv_norm with u = x * inv_norm; dgamma / dbeta as hulc_layernorm_bwd_ld (accumulate_params, ws of hulc_layernorm_bwd_workspace(R, D)
+ * bytes).  Fixed summation order: the same call gives the same bits.  Refused with untouched outputs: a null pointer (-1); D outside
+ * 1..256, a pitch below D, R < 1 (-2). */
+int hulc_l2norm_layernorm_fwd_ld(const float* x, const float* gamma, const float* beta, float eps, int R, int D, float* y, long ld_y,
+                                 float* inv_norm, float* mean, float* rstd, void* stream);
+int hulc_l2norm_layernorm_bwd_ld(const float* dy, long ld_dy, const float* x, const float* inv_norm, const float* mean, const float* rstd,
+                                 const float* gamma, int R, int D, float* dx, float* dgamma, float* dbeta, int accumulate_params, void* ws,
+                                 void* stream);
+/* y[i] = x[i] * keep-scale(seed ^ seed_dev[0], i, drop_p) for i < n: word dropout on the (B, 384) sentence embedding in front of the
+ * language goal MLP (word_dropout_p, goal_encoders.py:52-54).  The embedding is data: there is no backward.  n == 0 is a successful no-op;
+ * refused: a null pointer (-1), n < 0 or drop_p outside [0, 1) (-2). */
+int hulc_dropout_fwd(const float* x, float* y, long n, float drop_p, unsigned long long seed, const unsigned long long* seed_dev, void* stream);
+
 /* ---- (ABI 3) the whole plan-recognition transformer trunk as ONE launch per direction (bf16 compute) -------------------------------- */
 /* PlanRecognitionTransformersNetwork.forward up to the sequence mean (plan_recognition_net.py:125-146): dropout(emb + pos[position_ids]) ->
  * L post-norm nn.TransformerEncoderLayer (d_model 128, 8 heads, ReLU feed-forward FF, dropout drop_p) -> mean over the S <= 32 positions.
