@@ -17,8 +17,9 @@ DISTRIBUTIONS = {
 
 def default_model_config(gripper_control: bool = True, dropout_p: float = 0.1, static_hw=(200, 200), distribution: str = "discrete",
                          dropout_vis_fc: float = 0.0, word_dropout_p: float = 0.0, l2_normalize_output: bool = False,
-                         l2_normalize_goal_embeddings: bool = False) -> Config:
-    """distribution: "discrete" (the headline config) or "continuous" (`model/distribution=continuous`).  The encoder regularisers:
+                         l2_normalize_goal_embeddings: bool = False, policy_rnn_dropout_p: float = 0.0) -> Config:
+    """distribution: "discrete" (the headline config) or "continuous" (`model/distribution=continuous`).  policy_rnn_dropout_p goes to the
+    action decoder's yaml (nn.RNN's inter-layer dropout).  The encoder regularisers:
     dropout_vis_fc / l2_normalize_output go to both camera yamls (rgb_static/default.yaml, rgb_gripper/default.yaml),
     l2_normalize_goal_embeddings to both goal encoders, word_dropout_p to language_goal/default.yaml; per-encoder values: edit the returned
     config (e.g. cfg["perceptual_encoder"]["rgb_gripper"]["dropout_vis_fc"])."""
@@ -60,7 +61,7 @@ def default_model_config(gripper_control: bool = True, dropout_p: float = 0.1, s
             "n_mixtures": 10, "hidden_size": 2048, "out_features": 7, "log_scale_min": -7.0, "act_max_bound": act7,
             "act_min_bound": [-v for v in act7], "dataset_dir": "", "load_action_bounds": False, "num_classes": 10,
             "latent_goal_features": 32, "plan_features": None, "perceptual_features": None, "gripper_alpha": 1.0,
-            "perceptual_emb_slice": [64, 128], "policy_rnn_dropout_p": 0.0, "num_layers": 2, "rnn_model": "rnn_decoder",
+            "perceptual_emb_slice": [64, 128], "policy_rnn_dropout_p": policy_rnn_dropout_p, "num_layers": 2, "rnn_model": "rnn_decoder",
             "gripper_control": gripper_control, "discrete_gripper": True},
         "optimizer": {"_target_": "torch.optim.Adam", "lr": 2e-4},
         "lr_scheduler": {"_target_": "transformers.get_constant_schedule"},

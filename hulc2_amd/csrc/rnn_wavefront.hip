@@ -21,6 +21,7 @@
 //     poisons the output with NaN instead of hanging the GPU.
 #include "hulc_common.h"
 #include "hulc_abi_internal.h"
+#include <type_traits>
 #ifdef HULC_PROBES
 #include <cstdio>
 #include <stdlib.h>
@@ -54,6 +55,15 @@ struct WaveP {
 #endif
 };
 
+// The dropout instances (hulc_rnn_wavefront_drop) take the plain parameter block plus the mask's: the plain instances keep WaveP, so
+// their argument block and their code are what they were.  The mask is never stored as values: element (t, row, j) is kept with scale
+// 1 / (1 - p) when dropout_scale(seed ^ seed_dev[0], (t * B + row) * H + j, p) is non-zero, t = t0 + tau * t_dir at wave step tau.
+struct WaveDropP : WaveP {
+    float drop_p; unsigned long long seed; const unsigned long long* seed_dev;
+    int t0, t_dir;
+    const unsigned long long* keep;              // K-side mode: the keep BITS of the sweep in fragment order, written by rnn_keep_bits_kernel
+};
+
 // The bf16 state copy is the only data exchanged between workgroups inside the kernel.  Measured alternatives:
 //   * agent-scope release/acquire fences around the barrier: buffer_wbl2 / buffer_inv from 2048 waves per step, ~90 us/step;
 //   * device-coherent (sc1) loads and stores on a ping-pong buffer: no cache maintenance, but every read bypasses the
@@ -66,6 +76,13 @@ struct WaveP {
 // 256 KB a workgroup reads per step took ~6 us (18 B/clk per CU).  Blocked, the 16 lanes read 256 contiguous bytes, an
 // instruction touches 8 full lines instead of 64 partial ones, and every 128-byte line has exactly one writer workgroup.
 HULC_DEVICE bf16x8_t load_state8(const uint16_t* p) { return *(const bf16x8_t*)p; }
+
+// bit 0 / bit 1 of `two`: keep the low / high bf16 of w, else zero it.  hulc_common.h's keep_u16x2 does the same in one asm instruction, but
+// the result here is the very next MFMA's A operand, and hipcc pads no VALU -> MFMA hazard behind an asm statement: plain C++
+HULC_DEVICE uint32_t keep_pair(uint32_t w, uint32_t two) {
+    const uint32_t lo = 0u - (two & 1u), hi = 0u - ((two >> 1) & 1u);
+    return w & ((lo & 0xffffu) | (hi << 16));
+}
 
 // T: element (n, k) is w[k*ld + n] instead of w[n*ld + k] — compile-time, so that the 24 fragment loads of a wave are issued back to
 // back (a run-time branch around a load makes hipcc wait for it at the join: 24 serial round trips at the start of every pass)
@@ -98,12 +115,24 @@ HULC_DEVICE bf16x8_t load_w(const uint16_t* w, long ld, int n, int k) {
 // wave: 128 KB per CU at 29 B/clk), 8-wave sum + epilogue 0.22, stores 0.13-0.23.  Reading the NEXT sub-step's counters at the end of this one (to save the
 // round trip at the top) made the pass 11 % slower: the counters are not complete yet at that point — a group's chain (stores -> acknowledgement ->
 // counter -> propagation -> loads -> MFMAs -> sum) is as long as the two sub-steps it has; the kernel is bound by that chain, not by throughput.
-template <int H, bool WT, bool TS = false>      // TS: the probe's instance with phase time stamps (-DHULC_PROBES builds, HULC_RNN_DBG & 8) — the stamps' branches cost the plain kernel 5 %
-__global__ __launch_bounds__(512) void rnn_wavefront2_kernel(WaveP p) {
+//
+// DROP (hulc_rnn_wavefront_drop): inter-layer dropout on the second half's wB1 product, which then has an accumulator and a slice of the
+// reduction tile of its own (the wB2 product and the first half read the same fragments undropped).
+//   1, K side (forward sweep):  second = f2( s * ((keep . z[:, :H]) wB1^T) + z[:, H:] wB2^T + biases ): the dropped bf16 values of the A fragment
+//      are zeroed (keep_pair) and s = 1 / (1 - p) multiplies the reduced product in fp32.  The keep bits are not drawn here (two draws per
+//      fragment x 8 fragments per lane and sub-step at ~50 slots each, on the chain the kernel is bound by): a launch in front of the sweep
+//      packs them so that a lane's 8 fragments of a sub-step are ONE 8-byte load, byte q = fragment q, bit j = its j-th value.
+//   2, N side (backward sweep): second = f2( keep * s . (z[:, :H] wB1^T) + z[:, H:] wB2^T ): one draw per output element, taken beside the
+//      epilogue operands while the state loads are in flight.
+// Everything the workgroups exchange, wave 0's vmcnt constant included, is untouched: see the note at the keep-bit load.
+template <int H, bool WT, bool TS = false, int DROP = 0>      // TS: the probe's instance with phase time stamps (-DHULC_PROBES builds, HULC_RNN_DBG & 8) — the stamps' branches cost the plain kernel 5 %
+__global__ __launch_bounds__(512) void rnn_wavefront2_kernel(std::conditional_t<DROP != 0, WaveDropP, WaveP> p) {
     constexpr int KS = H / 32;
     constexpr int KPW = KS / 8;
+    constexpr int NR = DROP ? 3 : 2;             // reduction tiles: first half, second half, (DROP) the masked wB1 product
     static_assert(KS % 8 == 0, "H must be a multiple of 256");
-    __shared__ float red[8][2][256];             // [wave][ct][reg*64 + lane] partial tiles of the current group
+    static_assert(DROP == 0 || KPW == 8, "the keep bits of a lane's sub-step are one 64-bit word: 8 fragments of 8 values");
+    __shared__ float red[8][NR][256];            // [wave][ct][reg*64 + lane] partial tiles of the current group
     __shared__ uint4 wlds[8][KPW][64];
     __shared__ __attribute__((aligned(16))) uint16_t otile[16][2][16 + 8];   // bf16 outputs of the sub-step, [row][half][col] (+pad)
     __shared__ __attribute__((aligned(16))) float ftile[16][2][16 + 4];      // the same values in fp32
@@ -142,6 +171,8 @@ __global__ __launch_bounds__(512) void rnn_wavefront2_kernel(WaveP p) {
     }
     int pending = -1;                                             // wave 0: group whose exchange stores await their acknowledgement
     const int U = 2 * (p.S + 1);
+    unsigned long long dseed = 0ull; float dkeep = 1.f;           // (DROP) the call's RNG stream and 1 / (1 - p), as dropout_scale computes it
+    if constexpr (DROP != 0) { dseed = p.seed ^ (p.seed_dev ? p.seed_dev[0] : 0ull); dkeep = 1.0f / (1.0f - p.drop_p); }
 #ifdef HULC_PROBES
     // (probe) phase stamps of workgroups 0 and 100, waves 1 (an ordinary wave), 0 (exchange stores) and 7 (polls)
     const int ts_wg = blockIdx.x == 0 ? 0 : (blockIdx.x == 100 ? 1 : -1), ts_wv = wave == 1 ? 0 : (wave == 0 ? 1 : (wave == 7 ? 2 : -1));
@@ -176,7 +207,9 @@ __global__ __launch_bounds__(512) void rnn_wavefront2_kernel(WaveP p) {
             asm volatile("" ::: "memory");
         }
         RNN_TS(u, 1)
-        f32x4_t acc[2] = {f32x4_t{0.f, 0.f, 0.f, 0.f}, f32x4_t{0.f, 0.f, 0.f, 0.f}};
+        f32x4_t acc[NR];
+#pragma unroll
+        for (int ct = 0; ct < NR; ++ct) acc[ct] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         const bool mul = tau > 0;
         bf16x8_t af[2][KPW];
         if (mul) {
@@ -205,20 +238,56 @@ __global__ __launch_bounds__(512) void rnn_wavefront2_kernel(WaveP p) {
                 if (p.mask1 && first_on) omask = p.mask1[(long)tau * p.mask1_step + (long)m * p.ld_mask1 + on];
             } else if (p.mask2 && second_on) omask = p.mask2[(long)tau * p.mask2_step + (long)m * p.ld_mask2 + on];
         }
+        // (DROP) the mask of this sub-step.  K side: this lane's 64 keep bits — a vector load issued HERE, behind wave 0's wait like the
+        // epilogue operands above (the "memory" clobbers of that block keep it below): between the exchange stores and the wait wave 0 still
+        // issues the 2 * KPW state loads and nothing else, so vmcnt(2 * KPW) proves the stores acknowledged exactly as in the plain kernel.
+        // The words were written by the launch in front of the sweep; no workgroup writes them.  N side: the scale of this thread's output.
+        unsigned long long kbits = 0ull; float oscale = 0.f;
+        if constexpr (DROP == 1) {
+            if (mul) kbits = p.keep[((long)((p.t0 + tau * p.t_dir) * 8 + wave) * 4 + kb) * 64 + rowhalf * 32 + g * 16 + i];
+        } else if constexpr (DROP == 2) {
+            if (oct == 1 && second_on) {
+                const int m = om < p.B ? om : p.B - 1;
+                oscale = dropout_scale(dseed, (uint64_t)((long)(p.t0 + tau * p.t_dir) * p.B + m) * (uint64_t)H + (uint64_t)on, p.drop_p);
+            }
+        }
         if (mul) {
+            if constexpr (DROP == 0) {
 #pragma unroll
-            for (int q = 0; q < KPW; ++q) {
-                acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0][q], wfa[q], acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0][q], wfb[q], acc[1], 0, 0, 0);
+                for (int q = 0; q < KPW; ++q) {
+                    acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0][q], wfa[q], acc[0], 0, 0, 0);
+                    acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0][q], wfb[q], acc[1], 0, 0, 0);
+                }
+            } else if constexpr (DROP == 2) {
+#pragma unroll
+                for (int q = 0; q < KPW; ++q) {
+                    acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0][q], wfa[q], acc[0], 0, 0, 0);
+                    acc[NR - 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0][q], wfb[q], acc[NR - 1], 0, 0, 0);
+                }
+            } else {
+#pragma unroll
+                for (int q = 0; q < KPW; ++q) acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0][q], wfa[q], acc[0], 0, 0, 0);
             }
 #pragma unroll
             for (int q = 0; q < KPW; ++q) {
                 union { bf16x8_t b; uint4 u; } wc; wc.u = wlds[wave][q][lane];
                 acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1][q], wc.b, acc[1], 0, 0, 0);
             }
+            if constexpr (DROP == 1) {
+                // the masked product last: the keep bits were requested after the state loads
+                const unsigned klo = (unsigned)kbits, khi = (unsigned)(kbits >> 32);
+#pragma unroll
+                for (int q = 0; q < KPW; ++q) {
+                    const unsigned k8 = ((q < 4 ? klo : khi) >> (8 * (q & 3))) & 0xffu;
+                    union { bf16x8_t b; uint4 u; } a; a.b = af[0][q];
+                    a.u.x = keep_pair(a.u.x, k8); a.u.y = keep_pair(a.u.y, k8 >> 2);
+                    a.u.z = keep_pair(a.u.z, k8 >> 4); a.u.w = keep_pair(a.u.w, k8 >> 6);
+                    acc[NR - 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.b, wfb[q], acc[NR - 1], 0, 0, 0);
+                }
+            }
         }
 #pragma unroll
-        for (int ct = 0; ct < 2; ++ct)
+        for (int ct = 0; ct < NR; ++ct)
 #pragma unroll
             for (int e = 0; e < 4; ++e) red[wave][ct][e * 64 + lane] = acc[ct][e];
         RNN_TS_MFMA_DONE
@@ -230,6 +299,14 @@ __global__ __launch_bounds__(512) void rnn_wavefront2_kernel(WaveP p) {
             float v = 0.f;
 #pragma unroll
             for (int w = 0; w < 8; ++w) v += red[w][oct][oe];
+            if constexpr (DROP != 0) {
+                if (oct == 1) {                                    // + scale * the masked wB1 product, summed in the same fixed order
+                    float vd = 0.f;
+#pragma unroll
+                    for (int w = 0; w < 8; ++w) vd += red[w][NR - 1][oe];
+                    v += (DROP == 1 ? dkeep : oscale) * vd;
+                }
+            }
             const bool on_ = oct == 0 ? first_on : second_on;
             asm volatile("" : "+v"(oadd), "+v"(omask));
             v += oadd + obias[g];
@@ -321,6 +398,48 @@ __global__ __launch_bounds__(256) void rnn_zero2d_kernel(uint16_t* __restrict__ 
     if (i < (long)rows * width) dst[(i / width) * pitch + i % width] = 0;
 }
 
+// The keep bits of a K-side sweep, [t][wave 0..7][k-block 0..3][row 0..63] 64-bit words: byte q of a word = the fragment q of that lane, i.e. the
+// 8 values k = (wave * 8 + q) * 32 + kb * 8 .. + 7 of (t, row); bit j set = value j kept.  One thread per byte, two dropout_scale4 draws: the bits are
+// those of dropout_scale(seed, (t * B + row) * H + k, p).  Rows >= B (never stored by the sweep) get zeros.
+template <int H>
+__global__ __launch_bounds__(256) void rnn_keep_bits_kernel(unsigned char* __restrict__ bits, int S, int B, float p, unsigned long long seed,
+                                                            const unsigned long long* __restrict__ seed_dev) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)S * 8 * 4 * 64 * 8) return;
+    if (seed_dev) seed ^= seed_dev[0];
+    const int q = (int)(i & 7), row = (int)((i >> 3) & 63), kb = (int)((i >> 9) & 3), wave = (int)((i >> 11) & 7);
+    const long t = i >> 14;
+    unsigned b = 0;
+    if (row < B) {
+        const uint64_t idx = (uint64_t)(t * B + row) * (uint64_t)H + (uint64_t)((wave * 8 + q) * 32 + kb * 8);
+        float s[4];
+        dropout_scale4(seed, idx, p, s);
+        b = (s[0] > 0.f ? 1u : 0u) | (s[1] > 0.f ? 2u : 0u) | (s[2] > 0.f ? 4u : 0u) | (s[3] > 0.f ? 8u : 0u);
+        dropout_scale4(seed, idx + 4, p, s);
+        b |= (s[0] > 0.f ? 16u : 0u) | (s[1] > 0.f ? 32u : 0u) | (s[2] > 0.f ? 64u : 0u) | (s[3] > 0.f ? 128u : 0u);
+    }
+    bits[i] = (unsigned char)b;
+}
+
+// out[r][j .. j+3] = x[r * ldx + j ..] * dropout_scale(seed, (row0 + r) * H + j .., p): four consecutive elements share one draw (H % 4 == 0)
+__global__ __launch_bounds__(256) void rnn_drop_rows_kernel(const float* __restrict__ x, long ldx, long rows, int H, long row0, float p,
+                                                            unsigned long long seed, const unsigned long long* __restrict__ seed_dev,
+                                                            float* __restrict__ out32, long ld32, uint16_t* __restrict__ out16, long ld16) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int H4 = H / 4;
+    if (i >= rows * H4) return;
+    if (seed_dev) seed ^= seed_dev[0];
+    const long r = i / H4; const int j = (int)(i % H4) * 4;
+    float s[4];
+    dropout_scale4(seed, (uint64_t)(row0 + r) * (uint64_t)H + (uint64_t)j, p, s);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float v = x[r * ldx + j + e] * s[e];
+        if (out32) out32[r * ld32 + j + e] = v;
+        if (out16) out16[r * ld16 + j + e] = f32_to_bf16_bits(v);
+    }
+}
+
 }  // namespace
 
 extern "C" long hulc_rnn_wavefront_mirror_offset(void) { return RNN_WS_HEADER; }
@@ -328,17 +447,21 @@ extern "C" long hulc_rnn_wavefront_mirror_offset(void) { return RNN_WS_HEADER; }
 extern "C" long hulc_rnn_wavefront_mirror_t_offset(int S, int B, int H) { return B % 8 ? 0 : RNN_WS_HEADER + (long)(S + 2) * (B + 64) * 2 * H * 2; }
 extern "C" long hulc_rnn_wavefront_workspace(int S, int B, int H) { return RNN_WS_HEADER + (long)(S + 2) * (B + 64 + (B % 8 ? 0 : B)) * 2 * H * 2; }
 
-// see include/hulc2_amd.h
-extern "C" int hulc_rnn_wavefront(const hulc_rnn_wave_desc* d, void* ws, void* stream) {
+// the refusals of a sweep, all of them before the first launch: a refused call writes nothing.  0 = the call may go ahead
+static int wave_refusal(const hulc_rnn_wave_desc* d, void* ws) {
     if (!d || !ws || !d->z || !d->wA || !d->wB1 || !d->wB2) return hulc_fail(-1, "hulc_rnn_wavefront: null pointer");
     if (d->H != 2048) return hulc_fail(-2, "hulc_rnn_wavefront: built for hidden size 2048 (use the per-step hulc_gemm path otherwise)");
     if (d->B < 1 || d->B > 64 || d->S < 1) return hulc_fail(-2, "hulc_rnn_wavefront: needs 1 <= B <= 64 rows and S >= 1");
     if ((!d->tA && (d->ldA % 8 || (uintptr_t)d->wA % 16)) || (!d->tB1 && (d->ldB1 % 8 || (uintptr_t)d->wB1 % 16)) ||
         (!d->tB2 && (d->ldB2 % 8 || (uintptr_t)d->wB2 % 16)))
         return hulc_fail(-4, "hulc_rnn_wavefront: k-major weights must be 16-byte aligned");
-    if (d->tA != d->tB1 || d->tA != d->tB2) return hulc_fail(-3, "hulc_rnn_wavefront: the three weight matrices share one layout (tA == tB1 == tB2)");     // before the first launch: a refused call writes nothing
-    hipStream_t s = (hipStream_t)stream;
-    WaveP p;
+    if (d->tA != d->tB1 || d->tA != d->tB2) return hulc_fail(-3, "hulc_rnn_wavefront: the three weight matrices share one layout (tA == tB1 == tB2)");
+    if ((uintptr_t)ws % 16 || RNN_WS_HEADER % 16) return hulc_fail(-4, "hulc_rnn_wavefront: workspace must be 16-byte aligned");
+    return 0;
+}
+
+// the kernel's parameter block of an accepted call
+static void wave_params(const hulc_rnn_wave_desc* d, void* ws, WaveP& p) {
     p.z = d->z; p.z_step = d->z_step;
     p.bar = (unsigned*)ws; p.err = (int*)((unsigned*)ws + RNN_ERR_WORD); p.zb = (uint16_t*)((char*)ws + RNN_WS_HEADER);
     p.xb = p.zb + (long)(d->S + 2) * d->B * 2 * d->H;
@@ -353,8 +476,35 @@ extern "C" int hulc_rnn_wavefront(const hulc_rnn_wave_desc* d, void* ws, void* s
     p.relu = d->relu; p.S = d->S; p.B = d->B; p.H = d->H; p.err_sticky = d->err_sticky;
     p.add1c = d->add1c; p.ld_add1c = d->ld_add1c;
     p.inject_timeout = d->inject_timeout;
+    p.zb_row0 = d->z_step > 0 ? 0 : d->S + 1; p.zb_dir = d->z_step > 0 ? 1 : -1;
 #ifdef HULC_PROBES
     p.ts = nullptr;
+#endif
+}
+
+// the launches in front of the sweep: barrier words, and the bf16 copy of the (zero) initial state row — the copy is a full mirror of the
+// fp32 rows for the weight-gradient GEMMs
+static void wave_prep(const hulc_rnn_wave_desc* d, void* ws, const WaveP& p, hipStream_t s) {
+    const long na = RNN_WS_HEADER / 16, nb = (long)d->B * 2 * d->H * 2 / 16;
+    const long nz0 = d->zero_edges ? (long)d->B * 2 * d->H / 4 : 0;
+    long n = na > nb ? na : nb;
+    if (nz0 > n) n = nz0;
+    float* zlast = d->zero_edges ? d->z + (long)(d->S + 1) * d->z_step : nullptr;       // row S+1 of the sweep
+    rnn_prep_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>((uint4*)ws, na, (uint4*)(p.zb + (long)p.zb_row0 * d->B * 2 * d->H), nb,
+                                                              d->zero_edges ? (float4*)d->z : nullptr, nz0, zlast, d->B, d->H);
+    if (p.zt) {
+        const long n = 2L * d->H * d->B;
+        rnn_zero2d_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(p.zt + (long)p.zb_row0 * d->B, p.ld_t, d->B, 2 * d->H);
+    }
+}
+
+// see include/hulc2_amd.h
+extern "C" int hulc_rnn_wavefront(const hulc_rnn_wave_desc* d, void* ws, void* stream) {
+    if (const int rc = wave_refusal(d, ws)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    WaveP p;
+    wave_params(d, ws, p);
+#ifdef HULC_PROBES
     if (getenv("HULC_RNN_DBG") && (atoi(getenv("HULC_RNN_DBG")) & 8)) {                                   // (probe, eager launches only: the next call prints the previous launch's phase stamps)
         static unsigned long long* buf = nullptr; static int calls = 0;
         const int NW = 2 * 3 * 80 * 8;
@@ -380,20 +530,7 @@ extern "C" int hulc_rnn_wavefront(const hulc_rnn_wave_desc* d, void* ws, void* s
         ++calls;
     }
 #endif
-    p.zb_row0 = d->z_step > 0 ? 0 : d->S + 1; p.zb_dir = d->z_step > 0 ? 1 : -1;
-    // barrier words, and the bf16 copy of the (zero) initial state row: the copy is a full mirror of the fp32 rows for the weight-gradient GEMMs
-    if ((uintptr_t)ws % 16 || RNN_WS_HEADER % 16) return hulc_fail(-4, "hulc_rnn_wavefront: workspace must be 16-byte aligned");
-    const long na = RNN_WS_HEADER / 16, nb = (long)d->B * 2 * d->H * 2 / 16;
-    const long nz0 = d->zero_edges ? (long)d->B * 2 * d->H / 4 : 0;
-    long n = na > nb ? na : nb;
-    if (nz0 > n) n = nz0;
-    float* zlast = d->zero_edges ? d->z + (long)(d->S + 1) * d->z_step : nullptr;       // row S+1 of the sweep
-    rnn_prep_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>((uint4*)ws, na, (uint4*)(p.zb + (long)p.zb_row0 * d->B * 2 * d->H), nb,
-                                                              d->zero_edges ? (float4*)d->z : nullptr, nz0, zlast, d->B, d->H);
-    if (p.zt) {
-        const long n = 2L * d->H * d->B;
-        rnn_zero2d_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(p.zt + (long)p.zb_row0 * d->B, p.ld_t, d->B, 2 * d->H);
-    }
+    wave_prep(d, ws, p, s);
 #ifdef HULC_PROBES
     if (p.ts) {
         if (d->tA) rnn_wavefront2_kernel<2048, true, true><<<2 * (2048 / 16), 512, 0, s>>>(p);
@@ -403,4 +540,52 @@ extern "C" int hulc_rnn_wavefront(const hulc_rnn_wave_desc* d, void* ws, void* s
     if (d->tA) rnn_wavefront2_kernel<2048, true><<<2 * (2048 / 16), 512, 0, s>>>(p);
     else rnn_wavefront2_kernel<2048, false><<<2 * (2048 / 16), 512, 0, s>>>(p);
     return hulc_check_launch("hulc_rnn_wavefront");
+}
+
+// the plain workspace, then the keep bits of a K-side sweep (S x 2048 words of 8 bytes at H = 2048)
+static long wave_keep_offset(int S, int B, int H) { return (hulc_rnn_wavefront_workspace(S, B, H) + 15) / 16 * 16; }
+extern "C" long hulc_rnn_wavefront_drop_workspace(int S, int B, int H) { return wave_keep_offset(S, B, H) + (long)S * 8 * 4 * 64 * 8; }
+
+// see include/hulc2_amd.h
+extern "C" int hulc_rnn_wavefront_drop(const hulc_rnn_wave_desc* d, float drop_p, unsigned long long seed, const unsigned long long* seed_dev,
+                                       int mode, int t0, int t_dir, void* ws, void* stream) {
+    if (!(drop_p >= 0.f) || !(drop_p < 1.f)) return hulc_fail(-2, "hulc_rnn_wavefront_drop: drop_p must be in [0, 1)");
+    if (drop_p == 0.f) return hulc_rnn_wavefront(d, ws, stream);                    // no mask: the plain sweep, launch for launch
+    if (const int rc = wave_refusal(d, ws)) return rc;
+    if (mode != HULC_RNN_DROP_K && mode != HULC_RNN_DROP_N)
+        return hulc_fail(-2, "hulc_rnn_wavefront_drop: mode is HULC_RNN_DROP_K or HULC_RNN_DROP_N");
+    // the masked product exists at wave steps 1 .. S: their time indices must be those of the S x B x H mask
+    const long ta = (long)t0 + t_dir, tb = (long)t0 + (long)d->S * t_dir;
+    if ((t_dir != 1 && t_dir != -1) || ta < 0 || ta >= d->S || tb < 0 || tb >= d->S)
+        return hulc_fail(-2, "hulc_rnn_wavefront_drop: t0 + tau * t_dir must stay in 0 .. S-1 for tau = 1 .. S (t_dir = +1 or -1)");
+    hipStream_t s = (hipStream_t)stream;
+    WaveDropP p;
+    wave_params(d, ws, p);
+    p.drop_p = drop_p; p.seed = seed; p.seed_dev = seed_dev; p.t0 = t0; p.t_dir = t_dir;
+    p.keep = (const unsigned long long*)((char*)ws + wave_keep_offset(d->S, d->B, d->H));
+    wave_prep(d, ws, p, s);
+    if (mode == HULC_RNN_DROP_K) {
+        const long n = (long)d->S * 8 * 4 * 64 * 8;
+        rnn_keep_bits_kernel<2048><<<(unsigned)((n + 255) / 256), 256, 0, s>>>((unsigned char*)p.keep, d->S, d->B, p.drop_p, p.seed, p.seed_dev);
+        if (d->tA) rnn_wavefront2_kernel<2048, true, false, 1><<<2 * (2048 / 16), 512, 0, s>>>(p);
+        else rnn_wavefront2_kernel<2048, false, false, 1><<<2 * (2048 / 16), 512, 0, s>>>(p);
+    } else {
+        if (d->tA) rnn_wavefront2_kernel<2048, true, false, 2><<<2 * (2048 / 16), 512, 0, s>>>(p);
+        else rnn_wavefront2_kernel<2048, false, false, 2><<<2 * (2048 / 16), 512, 0, s>>>(p);
+    }
+    return hulc_check_launch("hulc_rnn_wavefront_drop");
+}
+
+// see include/hulc2_amd.h
+extern "C" int hulc_rnn_drop_rows(const float* x, long ldx, long rows, int H, long row0, float drop_p, unsigned long long seed,
+                                  const unsigned long long* seed_dev, float* out32, long ld32, void* out16, long ld16, void* stream) {
+    if (rows == 0) return 0;
+    if (!x || (!out32 && !out16)) return hulc_fail(-1, "hulc_rnn_drop_rows: null pointer");
+    if (rows < 0 || H < 4 || H % 4 || row0 < 0 || ldx < H || (out32 && ld32 < H) || (out16 && ld16 < H))
+        return hulc_fail(-2, "hulc_rnn_drop_rows: needs rows >= 0, H a positive multiple of 4, row0 >= 0 and pitches >= H");
+    if (!(drop_p >= 0.f) || !(drop_p < 1.f)) return hulc_fail(-2, "hulc_rnn_drop_rows: drop_p must be in [0, 1)");
+    const long n = rows * (H / 4);
+    rnn_drop_rows_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(x, ldx, rows, H, row0, drop_p, seed, seed_dev, out32, ld32,
+                                                                                     (uint16_t*)out16, ld16);
+    return hulc_check_launch("hulc_rnn_drop_rows");
 }

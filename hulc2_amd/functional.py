@@ -1288,10 +1288,17 @@ def _rnn_persistent(B: int, Hd: int, device) -> bool:
             and not switches.on("NO_RNN_WAVEFRONT"))
 
 
-def _decoder_rnn_forward(plan, emb, goal, lo: int, hi: int, w_ih0, w_hh0, b_ih0, b_hh0, w_ih1, w_hh1, b_ih1, b_hh1, h0, emb_tm: bool = False):
+DECODER_RNN_SITE = 0x5EED7001            # dropout site of the decoder RNN's inter-layer mask (the stacked call; per-modality calls: logistic_decoder_rnn.py)
+
+
+def _decoder_rnn_forward(plan, emb, goal, lo: int, hi: int, w_ih0, w_hh0, b_ih0, b_hh0, w_ih1, w_hh1, b_ih1, b_hh1, h0, emb_tm: bool = False,
+                         drop_p: float = 0.0, site: int = DECODER_RNN_SITE):
     """Forward sweep shared by training (DecoderRNNFn) and inference (decoder_rnn_infer).  h0: None (zero initial state, the
     training path) or (2, B, H) initial hidden states of the two layers (stateful `act`).  Returns the time-major state buffer
-    zbuf (S+2, B, 2H) with zbuf[t+1] = [h0_t | h1_{t-1}], the operands backward needs, and whether the persistent kernel ran."""
+    zbuf (S+2, B, 2H) with zbuf[t+1] = [h0_t | h1_{t-1}], the operands backward needs, and whether the persistent kernel ran.
+    drop_p > 0 (policy_rnn_dropout_p of a module in train mode): layer 1 reads k_t * h0_t, k_t[b][j] = dropout_scale(site ^ the device step word,
+    (t * B + b) * H + j, drop_p) as nn.RNN(dropout=p) does; layer 0's recurrence and the state buffer keep the undropped h0_t.  With
+    drop_p == 0 every launch is the one made without these two arguments."""
     # emb_tm: `emb` already IS the decoder's column slice in time-major order, (S, B, hi - lo) (EmbFanoutFn)
     if emb_tm:
         S, B, _ = emb.shape
@@ -1328,12 +1335,31 @@ def _decoder_rnn_forward(plan, emb, goal, lo: int, hi: int, w_ih0, w_hh0, b_ih0,
         zbuf[1][:, Hd:] = h0[1]
     whh0 = weight_operand(w_hh0)
     meta = (B, S, Hd, P, G, E, lo, hi, emb.shape[2], emb_tm)
+    if persistent and drop_p > 0.0:
+        # the same sweep with the mask on the K side of layer 1's input product (hulc_rnn_wavefront_drop); the opt-in transposed mirror is
+        # not written: backward takes the row-major operands when dropout is on
+        z16 = kn.rnn_wavefront_drop(zbuf[0], B * 2 * Hd, S, B, Hd, whh0, weight_operand(w_ih1), weight_operand(w_hh1), False,
+                                    drop_p, site, kn.RNN_DROP_K, -1, 1,
+                                    add1=pre0, add1_step=B * Hd, ld_add1=Hd, bias1=(b_hh0, None), bias2=(b_ih1, b_hh1), relu=True,
+                                    mirror_t=False, add1c=c, zero_edges=True)
+        return zbuf, plan, emb_t, goal, z16, meta
     if persistent:
         # both layers, all S steps: one persistent kernel with register-resident weights (csrc/rnn_wavefront.hip)
         z16 = kn.rnn_wavefront(zbuf[0], B * 2 * Hd, S, B, Hd, whh0, weight_operand(w_ih1), weight_operand(w_hh1), False,
                                add1=pre0, add1_step=B * Hd, ld_add1=Hd, bias1=(b_hh0, None), bias2=(b_ih1, b_hh1), relu=True,
                                mirror_t=switches.on("RNN_WGRAD_TMIRROR"), add1c=c, zero_edges=True)
         return zbuf, plan, emb_t, goal, z16, meta
+    if drop_p > 0.0:
+        # per-step path with the mask: h0_t -> dropped copy, then W_ih1 and W_hh1 as two GEMMs (the second adds the first and applies the ReLU)
+        # instead of the concatenated one
+        wih1, whh1 = weight_operand(w_ih1), weight_operand(w_hh1)
+        hd, pre1 = torch.empty(B, Hd, dtype=torch.float32, device=dev), torch.empty(B, Hd, dtype=torch.float32, device=dev)
+        for t in range(S):
+            kn.gemm(zbuf[t][:, :Hd], whh0, zbuf[t + 1][:, :Hd], B, Hd, Hd, 2 * Hd, Hd, 2 * Hd, bias=b_hh0, add=pre0[t], ld_add=Hd, relu=True)
+            kn.rnn_drop_rows(zbuf[t + 1][:, :Hd], B, Hd, t * B, drop_p, site, out32=hd)
+            kn.gemm(hd, wih1, pre1, B, Hd, Hd, Hd, Hd, Hd, bias=b_ih1, add=b_hh1, ld_add=0)
+            kn.gemm(zbuf[t + 1][:, Hd:], whh1, zbuf[t + 2][:, Hd:], B, Hd, Hd, 2 * Hd, Hd, 2 * Hd, add=pre1, ld_add=Hd, relu=True)
+        return zbuf, plan, emb_t, goal, None, meta
     w1cat = weight_operand(torch.cat([w_ih1.detach(), w_hh1.detach()], dim=1))   # (H, 2H) = [W_ih1 | W_hh1]
     for t in range(S):
         kn.gemm(zbuf[t][:, :Hd], whh0, zbuf[t + 1][:, :Hd], B, Hd, Hd, 2 * Hd, Hd, 2 * Hd, bias=b_hh0, add=pre0[t], ld_add=Hd, relu=True)
@@ -1342,9 +1368,12 @@ def _decoder_rnn_forward(plan, emb, goal, lo: int, hi: int, w_ih0, w_hh0, b_ih0,
 
 
 @torch.no_grad()
-def decoder_rnn_infer(plan, emb, goal, lo: int, hi: int, w_ih0, w_hh0, b_ih0, b_hh0, w_ih1, w_hh1, b_ih1, b_hh1, h0=None):
-    """Inference forward of the decoder RNN (logistic_decoder_rnn.py:257-271 with h_0): -> (h1 (B,S,H), h_n (2,B,H))."""
-    zbuf, _, _, _, _, meta = _decoder_rnn_forward(plan, emb, goal, lo, hi, w_ih0, w_hh0, b_ih0, b_hh0, w_ih1, w_hh1, b_ih1, b_hh1, h0)
+def decoder_rnn_infer(plan, emb, goal, lo: int, hi: int, w_ih0, w_hh0, b_ih0, b_hh0, w_ih1, w_hh1, b_ih1, b_hh1, h0=None,
+                      drop_p: float = 0.0, site: int = DECODER_RNN_SITE):
+    """Inference forward of the decoder RNN (logistic_decoder_rnn.py:257-271 with h_0): -> (h1 (B,S,H), h_n (2,B,H)).  drop_p > 0: a module
+    in train mode under no_grad drops as nn.RNN does there; h1 and h_n are undropped states either way."""
+    zbuf, _, _, _, _, meta = _decoder_rnn_forward(plan, emb, goal, lo, hi, w_ih0, w_hh0, b_ih0, b_hh0, w_ih1, w_hh1, b_ih1, b_hh1, h0,
+                                                  False, float(drop_p), int(site))
     S, Hd = meta[1], meta[2]
     h1 = zbuf[2:S + 2, :, Hd:].permute(1, 0, 2).contiguous()
     h_n = torch.stack([zbuf[S][:, :Hd], zbuf[S + 1][:, Hd:]]).float()             # final states of layer 0 and layer 1
@@ -1367,13 +1396,16 @@ class DecoderRNNFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, plan, emb, goal, lo: int, hi: int, w_ih0, w_hh0, b_ih0, b_hh0, w_ih1, w_hh1, b_ih1, b_hh1, time_major_out: bool = False,
-                emb_tm: bool = False):
+                emb_tm: bool = False, drop_p: float = 0.0, site: int = DECODER_RNN_SITE):
         """time_major_out: return h1 as the (S*B, H) column slice of the state buffer it already lies in (row = step * B + batch row, row
         stride 2H) instead of a (B, S, H) copy; the incoming gradient then has the same time-major row order.
-        emb_tm: `emb` is the (S, B, hi - lo) time-major slice itself; its gradient comes back in the same layout."""
+        emb_tm: `emb` is the (S, B, hi - lo) time-major slice itself; its gradient comes back in the same layout.
+        drop_p, site: the inter-layer dropout of _decoder_rnn_forward; backward redraws the same mask from (site, device step word)."""
+        drop_p, site = float(drop_p), int(site)
         zbuf, plan, emb_t, goal, z16, meta = _decoder_rnn_forward(plan, emb, goal, lo, hi, w_ih0, w_hh0, b_ih0, b_hh0, w_ih1, w_hh1,
-                                                                 b_ih1, b_hh1, None, emb_tm)
+                                                                 b_ih1, b_hh1, None, emb_tm, drop_p, site)
         B, S, Hd = meta[0], meta[1], meta[2]
+        ctx.drop = (drop_p, site)
         ctx.time_major = bool(time_major_out)
         ctx.persistent = z16 is not None
         ctx.z16 = z16                                      # bf16 mirror of zbuf written by the persistent kernel (weight-gradient operand)
@@ -1396,13 +1428,34 @@ class DecoderRNNFn(torch.autograd.Function):
             dbuf = torch.empty(S + 2, B, 2 * Hd, dtype=zbuf.dtype, device=dev)     # edges (row S+1, first half of row 0) cleared by the launcher
         else:
             dbuf = torch.zeros(S + 2, B, 2 * Hd, dtype=zbuf.dtype, device=dev)     # dbuf[t+1][:, :H] = delta1_t, dbuf[t][:, H:] = delta0_t
-        if ctx.persistent:
+        drop_p, site = ctx.drop
+        if ctx.persistent and drop_p > 0.0:
+            # the reversed sweep with the mask on the outputs of the delta1 W_ih1 product: delta0_t = (k_t * (delta1_t W_ih1) + delta0_{t+1} W_hh0) * (h0_t > 0),
+            # wave step tau writes delta0_{S - tau}
+            d16, d16t = kn.rnn_wavefront_drop(dbuf[S + 1], -B * 2 * Hd, S, B, Hd, weight_operand(w_hh1), weight_operand(w_ih1), weight_operand(w_hh0), True,
+                                              drop_p, site, kn.RNN_DROP_N, S, -1,
+                                              add1=dH1_t[S - 1], add1_step=-B * Hd, ld_add1=Hd,
+                                              mask1=zbuf[S + 1][:, Hd:], mask1_step=-B * 2 * Hd, ld_mask1=2 * Hd,
+                                              mask2=zbuf[S + 1][:, :Hd], mask2_step=-B * 2 * Hd, ld_mask2=2 * Hd,
+                                              mirror_t=False, zero_edges=True)
+        elif ctx.persistent:
             # reversed sweep: wave step s reads dbuf[S+1-s] (row S+1 = 0) and writes dbuf[S-s]; weights read transposed in place
             d16, d16t = kn.rnn_wavefront(dbuf[S + 1], -B * 2 * Hd, S, B, Hd, weight_operand(w_hh1), weight_operand(w_ih1), weight_operand(w_hh0), True,
                                    add1=dH1_t[S - 1], add1_step=-B * Hd, ld_add1=Hd,
                                    mask1=zbuf[S + 1][:, Hd:], mask1_step=-B * 2 * Hd, ld_mask1=2 * Hd,
                                    mask2=zbuf[S + 1][:, :Hd], mask2_step=-B * 2 * Hd, ld_mask2=2 * Hd,
                                    mirror_t=switches.on("RNN_WGRAD_TMIRROR"), zero_edges=True)
+        elif drop_p > 0.0:
+            # per-step path with the mask: delta1_t W_ih1, times k_t, then added to delta0_{t+1} W_hh0 under the (h0_t > 0) gate
+            whh1_t, wih1_t, whh0_t = weight_operand(w_hh1, "t"), weight_operand(w_ih1, "t"), weight_operand(w_hh0, "t")
+            g1, g1d = torch.empty(B, Hd, **f32), torch.empty(B, Hd, **f32)
+            for t in range(S - 1, -1, -1):
+                h1_t, h0_t = zbuf[t + 2][:, Hd:], zbuf[t + 1][:, :Hd]
+                prev = dbuf[t + 2][:, :Hd] if t + 2 <= S else zbuf[0][:, :Hd]
+                kn.gemm(prev, whh1_t, dbuf[t + 1][:, :Hd], B, Hd, Hd, 2 * Hd, Hd, 2 * Hd, add=dH1_t[t], ld_add=Hd, mask=h1_t, ld_mask=2 * Hd)
+                kn.gemm(dbuf[t + 1][:, :Hd], wih1_t, g1, B, Hd, Hd, 2 * Hd, Hd, Hd)
+                kn.rnn_drop_rows(g1, B, Hd, t * B, drop_p, site, out32=g1d)
+                kn.gemm(dbuf[t + 1][:, Hd:], whh0_t, dbuf[t][:, Hd:], B, Hd, Hd, 2 * Hd, Hd, 2 * Hd, add=g1d, ld_add=Hd, mask=h0_t, ld_mask=2 * Hd)
         else:
             whh1_t = weight_operand(w_hh1, "t")
             wb0 = weight_operand(torch.cat([w_ih1.detach().t(), w_hh0.detach().t()], dim=1))   # (H, 2H) = [W_ih1^T | W_hh0^T]
@@ -1437,11 +1490,11 @@ class DecoderRNNFn(torch.autograd.Function):
                     accumulate=acc, rowsum=bout, rowsum_accumulate=acc_b)
             return ret, bret
 
-        def wgrad(dlt, inp_rows, ncols, param, bias):
+        def wgrad(dlt, inp_rows, ncols, param, bias, ld_inp=2 * Hd):
             """param.grad (+)= dlt^T inp_rows, bias.grad (+)= column sums of dlt (the row sums of the GEMM's A operand, fused into
             the same launch); straight into the gradient arena when the trainer registered sinks"""
             (out, acc, ret), (bout, acc_b, bret) = gradsink.dest(param, None, dbuf), gradsink.dest(bias, None, dbuf)
-            kn.gemm(dlt, inp_rows, out, Hd, ncols, M, 2 * Hd, 2 * Hd, ncols, a_kmajor=False, b_kmajor=False,
+            kn.gemm(dlt, inp_rows, out, Hd, ncols, M, 2 * Hd, ld_inp, ncols, a_kmajor=False, b_kmajor=False,
                     accumulate=acc, rowsum=bout if fuse_b else None, rowsum_accumulate=acc_b)
             if not fuse_b:
                 kn.colsum(dlt, M, Hd, 2 * Hd, bout, accumulate=acc_b)
@@ -1454,7 +1507,8 @@ class DecoderRNNFn(torch.autograd.Function):
         # on one box and nothing on another (3.13 either way); on a THIRD cached stream of its own the branch made a later step-node capture's
         # hipGraphLaunch segfault in every run of tests/test_trainer_gpu.py + tests/test_stepnode_gpu.py in that order (0 of 6 runs without it, 0 of 3
         # on the encoder stream): off by default.
-        wg_fork = (kn.fork_branches() and kn.wgrad_branch_ok() and dev.type == "cuda" and ctx.persistent and not use_t
+        # With dropout on (drop_p > 0) neither opt-in operand path is taken: the sweeps write no transposed mirror, and the branch is not forked.
+        wg_fork = (kn.fork_branches() and kn.wgrad_branch_ok() and dev.type == "cuda" and ctx.persistent and not use_t and drop_p == 0.0
                    and all(gradsink.get(t_) is not None for t_ in (w_ih1, b_ih1, w_hh1, b_hh1, w_hh0, b_hh0)))
         if wg_fork:
             # (on the gripper camera's encoder stream: idle between the encoders' forward and their backward at the end of the pass)
@@ -1476,7 +1530,15 @@ class DecoderRNNFn(torch.autograd.Function):
             dw_hh1, db_hh1 = wgrad_t(0, 1, Hd, 1, Hd, w_hh1, b_hh1)                 # h1_{t-1} = z[1:S+1][:, :, H:]
             dw_hh0, db_hh0 = wgrad_t(Hd, 0, 0, 0, Hd, w_hh0, b_hh0)                 # delta0 = d[0:S][:, :, H:], h0_{t-1} = z[0:S][:, :, :H]
         else:
-            dw_ih1, db_ih1 = wgrad(d1w, zw[1:S + 1], Hd, w_ih1, b_ih1)
+            if drop_p > 0.0:
+                # dW_ih1 = sum_t delta1_t^T (k_t * h0_t): the dropped operand is drawn once more from the fp32 rows; the mirror's h0_t stays the
+                # undropped operand of dW_hh0.  Same mask, but not bit for bit what the forward sweep consumed: this is bf16(s * h0_t), the sweep
+                # multiplied bf16(h0_t) and applied s in fp32 behind the product — one bf16 rounding apart, as the mirror operands are
+                h0d = torch.empty(M, Hd, dtype=torch.bfloat16 if use16 else torch.float32, device=dev)
+                kn.rnn_drop_rows(zbuf[1:S + 1].view(M, 2 * Hd)[:, :Hd], M, Hd, 0, drop_p, site, **{"out16" if use16 else "out32": h0d})
+                dw_ih1, db_ih1 = wgrad(d1w, h0d, Hd, w_ih1, b_ih1, ld_inp=Hd)
+            else:
+                dw_ih1, db_ih1 = wgrad(d1w, zw[1:S + 1], Hd, w_ih1, b_ih1)
             dw_hh1, db_hh1 = wgrad(d1w, zw[1:S + 1][:, :, Hd:], Hd, w_hh1, b_hh1)
             # layer 0 (b_ih0's gradient rides on the embedding-column GEMM of dW_ih0 below)
             dw_hh0, db_hh0 = wgrad(d0w, zw[0:S], Hd, w_hh0, b_hh0)                  # h0_{t-1} = zbuf[t][:, :H]
@@ -1508,7 +1570,7 @@ class DecoderRNNFn(torch.autograd.Function):
         else:
             demb = torch.zeros(B, S, Etot, **f32)
             demb[:, :, lo:hi] = demb_t.permute(1, 0, 2)
-        return (dplan, demb, dgoal, None, None, r_ih0, dw_hh0, rb_ih0, db_hh0, dw_ih1, dw_hh1, db_ih1, db_hh1, None, None)
+        return (dplan, demb, dgoal, None, None, r_ih0, dw_hh0, rb_ih0, db_hh0, dw_ih1, dw_hh1, db_ih1, db_hh1, None, None, None, None)
 
 
 @_scoped

@@ -1270,6 +1270,43 @@ def rnn_wavefront(z0, z_step, S, B, H, wA, wB1, wB2, transposed, add1=None, add1
     wave step 0 reads; rows advance by z_step elements.  Weights are bf16 (H, H) matrices, `transposed` applies to all three
     (or is a 3-tuple, one flag for each of wA, wB1, wB2).  HULC_RNN_DBG with bit 4 set (tests of the fault path, also handed to a child
     process): the launch ends as if a barrier had timed out (hulc_rnn_wave_desc.inject_timeout)."""
+    return _rnn_wave(None, z0, z_step, S, B, H, wA, wB1, wB2, transposed, add1=add1, add1_step=add1_step, ld_add1=ld_add1, bias1=bias1, bias2=bias2,
+                     mask1=mask1, mask1_step=mask1_step, ld_mask1=ld_mask1, mask2=mask2, mask2_step=mask2_step, ld_mask2=ld_mask2, relu=relu,
+                     mirror_t=mirror_t, add1c=add1c, zero_edges=zero_edges)
+
+
+RNN_DROP_K, RNN_DROP_N = (_L.DEFINES["HULC_" + n] for n in ("RNN_DROP_K", "RNN_DROP_N"))      # the header's codes for the masked side of the wB1 product
+
+
+def rnn_wavefront_drop(z0, z_step, S, B, H, wA, wB1, wB2, transposed, drop_p, seed, mode, t0, t_dir, **kw):
+    """`rnn_wavefront` with the inter-layer dropout of nn.RNN(dropout=p) on the second half's wB1 product (hulc_rnn_wavefront_drop): the
+    mask is dropout_scale(seed ^ the device step word, (t * B + row) * H + unit, drop_p) at t = t0 + tau * t_dir.  mode RNN_DROP_K masks the
+    product's inputs (the forward sweep: t0 = -1, t_dir = 1), RNN_DROP_N its outputs (the backward sweep: t0 = S, t_dir = -1).  The other
+    arguments are rnn_wavefront's; drop_p = 0 is that call."""
+    d = (float(drop_p), int(seed) & 0xFFFFFFFFFFFFFFFF, step_state(z0.device), int(mode), int(t0), int(t_dir))
+    a = dict(add1=None, add1_step=0, ld_add1=0, bias1=(None, None), bias2=(None, None), mask1=None, mask1_step=0, ld_mask1=0, mask2=None,
+             mask2_step=0, ld_mask2=0, relu=False, mirror_t=False, add1c=None, zero_edges=False)
+    unknown = set(kw) - set(a)
+    if unknown:
+        raise TypeError(f"rnn_wavefront_drop: unexpected arguments {sorted(unknown)}")
+    a.update(kw)
+    return _rnn_wave(d, z0, z_step, S, B, H, wA, wB1, wB2, transposed, **a)
+
+
+def rnn_drop_rows(x, rows, H, row0, drop_p, seed, out32=None, out16=None):
+    """out[r, j] = x[r, j] * dropout_scale(seed ^ the device step word, (row0 + r) * H + j, drop_p) for the first `rows` rows of the 2-d fp32
+    view x (any row pitch), to an fp32 and / or a bf16 2-d view (hulc_rnn_drop_rows): the decoder RNN's inter-layer mask on rows t * B + b."""
+    for t, dt in ((x, torch.float32), (out32, torch.float32), (out16, torch.bfloat16)):
+        if t is not None and (t.dtype != dt or t.dim() != 2 or t.stride(1) != 1):
+            raise _L.HulcKernelError("rnn_drop_rows: x / out32 are fp32 and out16 bf16 2-d views with unit column stride")
+    _call("hulc_rnn_drop_rows", x, x.stride(0), int(rows), int(H), int(row0), float(drop_p), int(seed) & 0xFFFFFFFFFFFFFFFF, step_state(x.device),
+          out32, out32.stride(0) if out32 is not None else 0, out16, out16.stride(0) if out16 is not None else 0,
+          nbytes=float(rows) * H * (4 + (4 if out32 is not None else 0) + (2 if out16 is not None else 0)))
+
+
+def _rnn_wave(drop, z0, z_step, S, B, H, wA, wB1, wB2, transposed, add1, add1_step, ld_add1, bias1, bias2, mask1, mask1_step, ld_mask1,
+              mask2, mask2_step, ld_mask2, relu, mirror_t, add1c, zero_edges):
+    """the launch behind rnn_wavefront (drop None) and rnn_wavefront_drop (drop: hulc_rnn_wavefront_drop's six mask arguments)"""
     for w in (wA, wB1, wB2):
         if w.dtype != torch.bfloat16:
             raise _L.HulcKernelError("rnn_wavefront: weights must be bf16 shadows (bf16 compute mode)")
@@ -1294,13 +1331,17 @@ def rnn_wavefront(z0, z_step, S, B, H, wA, wB1, wB2, transposed, add1=None, add1
     d.zero_edges = int(bool(zero_edges))
     d.inject_timeout = switches.value("RNN_DBG") & 4
     lib = _L.load()
-    ws = _ws(lib.hulc_rnn_wavefront_workspace(S, B, H), z0.device)
+    ws = _ws((lib.hulc_rnn_wavefront_workspace if drop is None else lib.hulc_rnn_wavefront_drop_workspace)(S, B, H), z0.device)
     # algorithmic work: S wave steps of a (B x 2H) x (2H x 2H) product with one H x H block structurally zero; bytes: the
     # three weight matrices once, per step the fp32 state row written + the bf16 copy written and read + add / masks read
     flops = 2.0 * B * 3 * H * H * S
     nbytes = 3.0 * H * H * 2 + S * B * (2 * H * 4 + 2 * 2 * H * 2 + (H * 4 if add1 is not None else 0)
                                         + (H * 4 if mask1 is not None else 0) + (H * 4 if mask2 is not None else 0))
-    _call("hulc_rnn_wavefront", _c.byref(d), ws, key=("rnn_wavefront", S, B, H, int(bool(transposed))), flops=flops, nbytes=nbytes)
+    if drop is None:
+        _call("hulc_rnn_wavefront", _c.byref(d), ws, key=("rnn_wavefront", S, B, H, int(bool(transposed))), flops=flops, nbytes=nbytes)
+    else:
+        _call("hulc_rnn_wavefront_drop", _c.byref(d), *drop, ws, key=("rnn_wavefront_drop", S, B, H, int(bool(transposed)), drop[3]),
+              flops=flops, nbytes=nbytes + (S * 2048 * 8 * 2 if drop[3] == RNN_DROP_K else 0))
     off = lib.hulc_rnn_wavefront_mirror_offset() // 2
     w16 = ws.view(torch.bfloat16)
     z16 = w16[off:off + (S + 2) * B * 2 * H].view(S + 2, B, 2 * H)

@@ -13,6 +13,11 @@ import torch.nn as nn
 from hulc2_amd import functional as HF
 from hulc2_amd import gradsink
 from hulc2_amd.models.decoders.action_decoder import ActionDecoder
+from hulc2_amd.models.perceptual_encoders.vision_network import check_dropout_p, fc_site
+
+# Dropout sites of policy_rnn_dropout_p, after vision_network's pattern: functional.DECODER_RNN_SITE (0x5EED7001) for the stacked call, the
+# modality's own where a modality runs a call of its own (Hulc2.lmp_train; unequal batches in loss_segments), whose rows restart at 0.
+DECODER_RNN_MODALITY_SITES = {"vis": 0x5EED7101, "lang": 0x5EED7201}
 
 
 class LogisticDecoderRNN(ActionDecoder):
@@ -21,9 +26,11 @@ class LogisticDecoderRNN(ActionDecoder):
                  dataset_dir: str, load_action_bounds: bool, num_classes: int, gripper_alpha: float, perceptual_emb_slice: tuple,
                  policy_rnn_dropout_p: float, num_layers: int, rnn_model: str, gripper_control: bool, discrete_gripper: bool):
         super().__init__()
-        if rnn_model != "rnn_decoder" or num_layers != 2 or not discrete_gripper or policy_rnn_dropout_p != 0.0:
-            raise NotImplementedError("configured path: 2-layer ReLU rnn_decoder, discrete gripper, no RNN dropout "
+        if rnn_model != "rnn_decoder" or num_layers != 2 or not discrete_gripper:
+            raise NotImplementedError("configured path: 2-layer ReLU rnn_decoder, discrete gripper "
                                       "(conf/model/action_decoder/logistic_decoder_rnn_calvin.yaml)")
+        policy_rnn_dropout_p = check_dropout_p(policy_rnn_dropout_p, "policy_rnn_dropout_p")
+        self.policy_rnn_dropout_p = policy_rnn_dropout_p      # nn.RNN(dropout=p): layer 1 reads a dropped h0_t while the module trains
         if load_action_bounds:
             raise NotImplementedError("load_action_bounds reads dataset statistics (file IO outside the hot path); "
                                       "pass the bounds in the config")
@@ -86,33 +93,43 @@ class LogisticDecoderRNN(ActionDecoder):
                        self.prob_fc.bias.new_zeros(pad)], dim=0)
         return HF.mlp(h.reshape(-1, h.shape[-1]), [(w, b, False)])
 
-    def _rnn(self, latent_plan, perceptual_emb, latent_goal, time_major: bool = False, emb_tm: bool = False) -> torch.Tensor:
+    def rnn_dropout(self, modality_scope=None) -> Tuple[float, int]:
+        """(effective policy_rnn_dropout_p, RNG site) of a call: p only while the module trains; the stacked call (all modalities' rows in
+        one tensor) has one site, a call per modality restarts its rows at 0 and takes the modality's own (vision_network.fc_site)"""
+        return (self.policy_rnn_dropout_p if self.training else 0.0,
+                fc_site(HF.DECODER_RNN_SITE, DECODER_RNN_MODALITY_SITES, modality_scope))
+
+    def _rnn(self, latent_plan, perceptual_emb, latent_goal, time_major: bool = False, emb_tm: bool = False, modality_scope=None) -> torch.Tensor:
         r = self.rnn
         lo, hi = self.perceptual_emb_slice
         return HF.DecoderRNNFn.apply(latent_plan, perceptual_emb, latent_goal, lo, hi, r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0,
-                                     r.bias_hh_l0, r.weight_ih_l1, r.weight_hh_l1, r.bias_ih_l1, r.bias_hh_l1, time_major, emb_tm)
+                                     r.bias_hh_l0, r.weight_ih_l1, r.weight_hh_l1, r.bias_ih_l1, r.bias_hh_l1, time_major, emb_tm,
+                                     *self.rnn_dropout(modality_scope))
 
-    def loss(self, latent_plan, perceptual_emb, latent_goal, actions, robot_obs) -> torch.Tensor:
-        return self.loss_segments([latent_plan], [perceptual_emb], [latent_goal], [actions], [robot_obs])[0]
+    def loss(self, latent_plan, perceptual_emb, latent_goal, actions, robot_obs, modality_scope=None) -> torch.Tensor:
+        """modality_scope ("vis" / "lang", Hulc2.lmp_train): the modality this call serves — selects the RNN dropout's site"""
+        return self.loss_stacked(latent_plan, perceptual_emb, latent_goal, [actions], [robot_obs], 1, modality_scope=modality_scope)[0]
 
-    def loss_segments(self, plans, embs, goals, actions, robot_obs) -> torch.Tensor:
+    def loss_segments(self, plans, embs, goals, actions, robot_obs, scopes=None) -> torch.Tensor:
         """Decoder loss of several independent batches (the 'vis' and 'lang' modalities of one training step) in ONE
         pass over the recurrence: sequences are independent and the weights shared, so the batches are concatenated
         (64 rows per recurrent GEMM instead of 2 x 32 — half the launches of the latency-bound part) and the loss
-        kernel returns one mean per segment, exactly what separate `loss` calls give (logistic_decoder_rnn.py:118-131)."""
+        kernel returns one mean per segment, exactly what separate `loss` calls give (logistic_decoder_rnn.py:118-131).
+        scopes: the modalities' names, for the separate passes of unequal batches (each draws its RNN dropout from its own site)."""
         n = len(plans)
         if n > 1 and len({p.shape[0] for p in plans}) > 1:          # unequal batches: fall back to separate passes
-            return torch.cat([self.loss_segments([plans[i]], [embs[i]], [goals[i]], [actions[i]], [robot_obs[i]]) for i in range(n)])
+            return torch.cat([self.loss_stacked(plans[i], embs[i], goals[i], [actions[i]], [robot_obs[i]], 1,
+                                                modality_scope=scopes[i] if scopes is not None else None) for i in range(n)])
         cat = (lambda ts: ts[0] if n == 1 else torch.cat(ts, dim=0))
         return self.loss_stacked(cat(plans), cat(embs), cat(goals), list(actions), list(robot_obs), n)
 
-    def loss_stacked(self, plan, emb, goal, act, obs, n: int = 1, emb_tm: bool = False) -> torch.Tensor:
+    def loss_stacked(self, plan, emb, goal, act, obs, n: int = 1, emb_tm: bool = False, modality_scope=None) -> torch.Tensor:
         """`loss_segments` on inputs that are already stacked on the batch axis (n equal segments, rows segment-major).
         emb_tm: `emb` is the decoder's embedding slice in time-major order (S, B, hi - lo), as EmbFanoutFn hands it over."""
         # training path: everything after the recurrence stays in the time-major row order the recurrent kernel leaves behind (row = step * B
         # + batch row): the heads read h1 in place, the loss maps rows to modality segments itself — no (B, S, 2048) transposes either way
         B, S = (emb.shape[1], emb.shape[0]) if emb_tm else (emb.shape[0], emb.shape[1])
-        y = self._heads(self._rnn(plan, emb, goal, time_major=True, emb_tm=emb_tm))  # (S*B, heads)
+        y = self._heads(self._rnn(plan, emb, goal, time_major=True, emb_tm=emb_tm, modality_scope=modality_scope))  # (S*B, heads)
         # targets in the same time-major row order, world -> tcp frame on the way (gripper_control.py:16-36): one launch for the stacked
         # modalities (act / obs: one tensor, or the list of per-modality tensors — no concatenation, no transposing copy)
         acts_l = list(act) if isinstance(act, (list, tuple)) else list(act.reshape(n, B // n, *act.shape[1:]).unbind(0))
@@ -145,7 +162,7 @@ class LogisticDecoderRNN(ActionDecoder):
             r = self.rnn
             lo, hi = self.perceptual_emb_slice
             h, h_n = HF.decoder_rnn_infer(latent_plan, perceptual_emb, latent_goal, lo, hi, r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0,
-                                          r.bias_hh_l0, r.weight_ih_l1, r.weight_hh_l1, r.bias_ih_l1, r.bias_hh_l1, h_0)
+                                          r.bias_hh_l0, r.weight_ih_l1, r.weight_hh_l1, r.bias_ih_l1, r.bias_hh_l1, h_0, *self.rnn_dropout())
         else:
             h = self._rnn(latent_plan, perceptual_emb, latent_goal)
             h_n = torch.stack([h.new_zeros(B, h.shape[-1]), h[:, -1]])

@@ -179,7 +179,8 @@ class Hulc2(LightningModule):
         pr_state, seq_feat = self.plan_recognition(perceptual_emb, seed=trunk_site(self.modality_scope))
         site = 0xA11CE if "lang" in self.modality_scope else 0xB0B       # distinct RNG sites for the two modalities
         sampled_plan, _ = self.dist.rsample_plan(pr_state, seed=site, idx=plan_idx, eps=plan_eps)
-        action_loss = self.action_decoder.loss(sampled_plan, perceptual_emb, latent_goal, train_acts, robot_obs)
+        # (one modality's rows, restarting at 0: the decoder's RNN dropout takes the modality's own RNG site)
+        action_loss = self.action_decoder.loss(sampled_plan, perceptual_emb, latent_goal, train_acts, robot_obs, modality_scope=self.modality_scope)
         kl_loss = self.compute_kl_loss(pp_state, pr_state)
         return kl_loss, action_loss, action_loss + kl_loss, pp_state, pr_state, seq_feat
 
@@ -383,7 +384,8 @@ class Hulc2(LightningModule):
             # the action decoder sees all modalities at once (shared weights, independent sequences); it returns one loss per
             # modality, each the mean over that modality's own tokens as in the reference (hulc2.py:239-241)
             act_losses = self.action_decoder.loss_segments([p[5] for p in per], [p[2] for p in per], [p[3] for p in per],
-                                                           [p[1]["actions"] for p in per], [p[1]["state_info"]["robot_obs"] for p in per])
+                                                           [p[1]["actions"] for p in per], [p[1]["state_info"]["robot_obs"] for p in per],
+                                                           scopes=[p[0] for p in per])
         # the scalar tail (hulc2.py:400-430) is one launch per direction: total = (sum act + sum kl) / n + beta * clip
         for i, (self.modality_scope, db, emb, latent_goal, seq_feat, plan, kl) in enumerate(per):
             if "lang" in self.modality_scope:
@@ -429,8 +431,9 @@ class Hulc2(LightningModule):
         return self.perceptual_encoder(db["rgb_obs"], db["depth_obs"], db["robot_obs"])
 
     def regulariser_key(self) -> tuple:
-        """the encoder regularisers a captured step has baked in as kernel choices and arguments (dropout_vis_fc of both cameras, word_dropout_p,
-        the four l2 flags): part of what keys a captured graph (StepNode._signature, ArenaTrainer.capture / replay)"""
+        """the regularisers a captured step has baked in as kernel choices and arguments (dropout_vis_fc of both cameras, word_dropout_p, the
+        four l2 flags and, as the last element, the decoder's effective policy_rnn_dropout_p: 0.0 in eval mode): part of what keys a captured
+        graph (StepNode._signature, ArenaTrainer.capture / replay)"""
         key = []
         enc = self.perceptual_encoder
         for name in ("rgb_static_encoder", "rgb_gripper_encoder"):
@@ -441,6 +444,8 @@ class Hulc2(LightningModule):
         if lg is not None:
             m0 = lg.mlp[0] if hasattr(lg, "mlp") else None
             key.append((float(m0.p) if (isinstance(m0, nn.Dropout) and lg.training) else 0.0, bool(getattr(lg, "l2_normalize_output", False))))
+        dec = self.action_decoder
+        key.append(float(getattr(dec, "policy_rnn_dropout_p", 0.0)) if dec.training else 0.0)
         return tuple(key)
 
     @staticmethod

@@ -41,7 +41,7 @@ TABLE = (
     Switch("HULC_FP32_SITES", str, "head,goal,encfc,txl", "call", True, "parts of a bf16 step whose forward runs in exact fp32, comma separated (kernels.fp32_sites)"),
     Switch("HULC_FP32_SITES_BWD", bool, False, "call", True, "the selected sites run their backward in exact fp32 too"),
     Switch("HULC_FORK", bool, True, "call", True, "prior and posterior branch of a step on two streams; 0: one after the other"),
-    Switch("HULC_WGRAD_FORK", bool, False, "call", True, "recurrent weight gradients as a third branch beside the data-gradient chain (native trainer only)"),
+    Switch("HULC_WGRAD_FORK", bool, False, "call", True, "recurrent weight gradients as a third branch beside the data-gradient chain (native trainer only; not taken with policy_rnn_dropout_p > 0)"),
     Switch("HULC_NO_MLP_CHAIN", bool, False, "call", True, "per-layer GEMMs in place of the chained MLP kernel"),
     Switch("HULC_NO_MLP2_ROWS", bool, False, "call", True, "per-layer GEMMs in place of the camera encoders' fused fc1-ReLU-fc2 head"),
     Switch("HULC_TXL_NO_SHARE", bool, False, "call", True, "the whole-trunk transformer launch keeps one workgroup per sequence"),
@@ -51,7 +51,7 @@ TABLE = (
     Switch("HULC_NO_FUSED_FFN", bool, False, "call", True, "the feed-forward network of a transformer layer as separate GEMMs (also turns the fused layer launch off)"),
     Switch("HULC_NO_TXL_BLOCK", bool, False, "call", True, "one launch per transformer layer in place of the whole-trunk launch"),
     Switch("HULC_NO_RNN_WAVEFRONT", bool, False, "call", True, "per-step GEMMs in place of the persistent recurrent wavefront kernel"),
-    Switch("HULC_RNN_WGRAD_TMIRROR", bool, False, "call", True, "the recurrent sweep keeps transposed (feature-major) mirrors for the weight-gradient GEMMs"),
+    Switch("HULC_RNN_WGRAD_TMIRROR", bool, False, "call", True, "the recurrent sweep keeps transposed (feature-major) mirrors for the weight-gradient GEMMs (not taken with policy_rnn_dropout_p > 0)"),
     Switch("HULC_ENC_STREAMS", bool, True, "call", True, "the two camera encoders on two streams; 0: one stream"),
     Switch("HULC_NO_MODALITY_BATCHING", bool, False, "call", True, "one pass per modality in place of one batched pass over vision and language windows"),
     Switch("HULC_FULL_ZERO_GRAD", bool, False, "call", True, "zero the whole gradient arena every step, not only the ranges no kernel overwrites"),

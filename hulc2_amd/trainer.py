@@ -1011,7 +1011,7 @@ class ArenaTrainer(WeightKeeper):
         # a KL weight taken by value is baked into graph_fb: replay() refuses to run it under another one
         kl = getattr(self.model, "kl_beta", None)
         self._kl_captured = None if (kl is None or getattr(self.model, "kl_beta_on_device", False)) else float(kl)
-        # the encoder regularisers (dropout probabilities, l2 flags) are kernel choices and by-value arguments of graph_fb
+        # the regularisers (dropout probabilities of the encoders and of the decoder's RNN, l2 flags) are kernel choices and by-value arguments of graph_fb
         self._reg_captured = self._regulariser_key()
 
     def _regulariser_key(self):
@@ -1026,9 +1026,9 @@ class ArenaTrainer(WeightKeeper):
                                f"see model.kl_beta = {float(self.model.kl_beta)!r}: set the weight through ArenaTrainer.set_kl_beta (the captured "
                                "launches then read a device scalar) and call capture() again")
         if self._regulariser_key() != self._reg_captured:
-            raise RuntimeError(f"ArenaTrainer.replay: the graphs were captured with the encoder regularisers {self._reg_captured!r} and the model "
-                               f"now has {self._regulariser_key()!r} (dropout_vis_fc / word_dropout_p / l2 flags, or train / eval mode): call "
-                               "capture() again")
+            raise RuntimeError(f"ArenaTrainer.replay: the graphs were captured with the encoder regularisers and decoder dropout "
+                               f"{self._reg_captured!r} and the model now has {self._regulariser_key()!r} (dropout_vis_fc / word_dropout_p / l2 flags / "
+                               "policy_rnn_dropout_p, or train / eval mode): call capture() again")
         if self.accumulate_grad_batches > 1:
             with self.gpu_section():
                 if self.micro_batch == 0:            # a window opens: the optimizer step count of the pass that will close it

@@ -731,6 +731,30 @@ long hulc_rnn_wavefront_mirror_offset(void);   /* byte offset of the bf16 state 
 long hulc_rnn_wavefront_mirror_t_offset(int S, int B, int H);
 int hulc_rnn_wavefront(const hulc_rnn_wave_desc* d, void* ws, void* stream);
 
+/* ---- recurrent decoder: inter-layer dropout (policy_rnn_dropout_p, nn.RNN(num_layers=2, dropout=p) of decoders/utils/rnn.py:5-14) ---- */
+/* torch drops layer 0's output on its way into layer 1 and nowhere else: layer 0's own recurrence, the heads and h_n read undropped values.
+ * The mask is a convention, not a tensor:   k_t[b][j] = dropout_scale(seed ^ seed_dev[0], (t * B + b) * H + j, drop_p)   in {0, 1 / (1 - p)},
+ * t the time step, b the row of the call, j the hidden unit (csrc/hulc_common.h: dropout_scale; oracle/counter_rng.py is its numpy twin).
+ * hulc_rnn_wavefront_drop runs the sweep of hulc_rnn_wavefront (same descriptor, same state rows, mirrors and barrier protocol) with that mask
+ * on the second half's wB1 product, at wave steps tau = 1 .. S with t = t0 + tau * t_dir:
+ *     HULC_RNN_DROP_K (forward:  t0 = -1, t_dir = +1):  f2( s * ((keep . z_tau[:, :H]) wB1^T) + z_tau[:, H:] wB2^T + bias2a + bias2b ),
+ *         keep in {0, 1} indexed (t, row, k), s = 1 / (1 - p) applied in fp32; the first half reads z_tau[:, :H] undropped;
+ *     HULC_RNN_DROP_N (backward: t0 = S,  t_dir = -1):  f2( k_t . (z_tau[:, :H] wB1^T) + z_tau[:, H:] wB2^T ), k_t indexed (t, row, n).
+ * drop_p = 0 IS hulc_rnn_wavefront (same launches, same bits); drop_p outside [0, 1) is refused (-2) before anything is launched.
+ * ws: hulc_rnn_wavefront_drop_workspace(S, B, H) bytes, laid out as hulc_rnn_wavefront's with the keep bits of the K mode behind it.
+ * The mask's six values go by value, the RNG triple as everywhere in this header: seed is the site's, seed_dev the optional device word xor-ed
+ * into it; mode says which side of the wB1 product carries the mask; t_dir is +1 or -1 and 0 <= t0 + tau * t_dir < S for tau = 1 .. S. */
+#define HULC_RNN_DROP_K 1
+#define HULC_RNN_DROP_N 2
+long hulc_rnn_wavefront_drop_workspace(int S, int B, int H);
+int hulc_rnn_wavefront_drop(const hulc_rnn_wave_desc* d, float drop_p, unsigned long long seed, const unsigned long long* seed_dev, int mode,
+                            int t0, int t_dir, void* ws, void* stream);
+/* out[r][j] = x[r * ldx + j] * k, k = dropout_scale(seed ^ seed_dev[0], (row0 + r) * H + j, drop_p), r < rows, j < H (H % 4 == 0), to an fp32
+ * destination (out32, pitch ld32) and / or a bf16 one (out16, pitch ld16): the mask of the convention above on rows t * B + b, for the operand
+ * k . h0 of dW_ih1 and for the per-step path of geometries the persistent kernel does not take. */
+int hulc_rnn_drop_rows(const float* x, long ldx, long rows, int H, long row0, float drop_p, unsigned long long seed,
+                       const unsigned long long* seed_dev, float* out32, long ld32, void* out16, long ld16, void* stream);
+
 /* ---- optimizer ------------------------------------------------------------------------------- */
 /* torch.optim.Adam semantics (hulc2.py:185-198, conf/model/optimizer/adam.yaml) over a flat fp32 arena;
  * bf16_shadow (optional) receives the updated weights rounded to bf16 for the MFMA kernels. */

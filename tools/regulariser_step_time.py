@@ -1,6 +1,6 @@
 """What the encoder regularisers cost in the native captured loop: bench.py's headline configuration (B = 32 per modality, S = 32, bf16
 compute, ArenaTrainer capture / replay) with the switches at their defaults and with dropout_vis_fc = 0.1, word_dropout_p = 0.1 and all
-four l2 flags on, one trainer at a time in the order A B A B.
+four l2 flags on, and with the decoder's policy_rnn_dropout_p = 0.1 alone, one trainer at a time in the order A B C A B C.
 
     python tools/regulariser_step_time.py [--rounds 20] [--steps 10]
 
@@ -23,8 +23,9 @@ def main(rounds: int, steps: int, batch_size: int, seq_len: int) -> None:
     dev = torch.device("cuda")
     kn.set_compute("bf16")
     on = dict(dropout_vis_fc=0.1, word_dropout_p=0.1, l2_normalize_output=True, l2_normalize_goal_embeddings=True)
-    times, loss = {"default": [], "regularisers_on": []}, {}
-    for name, kw in (("default", {}), ("regularisers_on", on)) * 2:      # A B A B, one live trainer at a time: both see the box twice
+    times, loss = {"default": [], "regularisers_on": [], "rnn_dropout": []}, {}
+    # A B C A B C, one live trainer at a time: each configuration sees the box twice
+    for name, kw in (("default", {}), ("regularisers_on", on), ("rnn_dropout", dict(policy_rnn_dropout_p=0.1))) * 2:
         kn.reset_step_state(dev)
         m = instantiate(default_model_config(gripper_control=True, dropout_p=0.1, **kw)).to(dev)
         syn.fill_state_dict_(m.state_dict(), 42)
