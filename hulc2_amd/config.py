@@ -17,9 +17,12 @@ DISTRIBUTIONS = {
 
 def default_model_config(gripper_control: bool = True, dropout_p: float = 0.1, static_hw=(200, 200), distribution: str = "discrete",
                          dropout_vis_fc: float = 0.0, word_dropout_p: float = 0.0, l2_normalize_output: bool = False,
-                         l2_normalize_goal_embeddings: bool = False, policy_rnn_dropout_p: float = 0.0) -> Config:
+                         l2_normalize_goal_embeddings: bool = False, policy_rnn_dropout_p: float = 0.0, encoder_normalize: bool = False,
+                         positional_normalize: bool = False, position_embedding: bool = True) -> Config:
     """distribution: "discrete" (the headline config) or "continuous" (`model/distribution=continuous`).  policy_rnn_dropout_p goes to the
-    action decoder's yaml (nn.RNN's inter-layer dropout).  The encoder regularisers:
+    action decoder's yaml (nn.RNN's inter-layer dropout).  encoder_normalize / positional_normalize / position_embedding: the switches of
+    plan_recognition/transformers.yaml (a final LayerNorm of the encoder, a LayerNorm behind the position add, learned positions or
+    sinusoids).  The encoder regularisers:
     dropout_vis_fc / l2_normalize_output go to both camera yamls (rgb_static/default.yaml, rgb_gripper/default.yaml),
     l2_normalize_goal_embeddings to both goal encoders, word_dropout_p to language_goal/default.yaml; per-encoder values: edit the returned
     config (e.g. cfg["perceptual_encoder"]["rgb_gripper"]["dropout_vis_fc"])."""
@@ -46,8 +49,8 @@ def default_model_config(gripper_control: bool = True, dropout_p: float = 0.1, s
         "plan_recognition": {
             "_target_": "hulc2.models.plan_encoders.plan_recognition_net.PlanRecognitionTransformersNetwork",
             "num_heads": 8, "num_layers": 2, "encoder_hidden_size": 2048, "fc_hidden_size": 4096, "in_features": None,
-            "plan_features": None, "action_space": 7, "dropout_p": dropout_p, "encoder_normalize": False,
-            "positional_normalize": False, "position_embedding": True, "max_position_embeddings": 32},
+            "plan_features": None, "action_space": 7, "dropout_p": dropout_p, "encoder_normalize": bool(encoder_normalize),
+            "positional_normalize": bool(positional_normalize), "position_embedding": bool(position_embedding), "max_position_embeddings": 32},
         "distribution": dict(DISTRIBUTIONS[distribution]),
         "visual_goal": {
             "_target_": "hulc2.models.encoders.goal_encoders.VisualGoalEncoder", "in_features": None, "hidden_size": 2048,

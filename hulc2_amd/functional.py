@@ -983,6 +983,8 @@ class AddPosFn(torch.autograd.Function):
             kn.dropout_bwd(dy, dx, dy.numel(), drop_p, seed)
         else:
             dx = dy
+        if not ctx.needs_input_grad[1]:                          # (a table that is a buffer: the sinusoids)
+            return dx, None, None, None, None, None
         return dx, _pos_table_grad(dx, ctx.pos if dx.dtype == torch.float32 else None, pshape, pos_ids), None, None, None, None
 
 
@@ -1162,10 +1164,12 @@ class TxlBlockFn(torch.autograd.Function):
     """PlanRecognitionTransformersNetwork.forward up to the sequence mean (plan_recognition_net.py:125-146) as ONE launch per direction
     (csrc/txl_block.hip): dropout(emb + pos) -> L transformer layers -> mean over the sequence, one workgroup per sequence.  Backward leaves
     the bf16 operands of the 4 L weight-gradient products (they join the pass's grouped launch) and the LayerNorm partials.
-    params: 12 per layer in _TXL_KEYS order.  Same dropout streams as AddPosFn / TxlLayerFn with the same seeds."""
+    params: 12 per layer in _TXL_KEYS order.  Same dropout streams as AddPosFn / TxlLayerFn with the same seeds.
+    pos_g, pos_b / enc_g, enc_b (pairs, or None): positional_normalize, x0 = dropout(LN_pos(emb + pos)), and encoder_normalize, the mean
+    over LN_enc(last layer) — stages of the same two launches (hulc_txl_block_norms_fwd / _bwd)."""
 
     @staticmethod
-    def forward(ctx, emb, pos, pos_ids, H: int, drop_p: float, seed: int, *params):
+    def forward(ctx, emb, pos, pos_ids, H: int, drop_p: float, seed: int, pos_g, pos_b, enc_g, enc_b, *params):
         B, S, E = emb.shape
         L = len(params) // 12
         T = B * S
@@ -1195,12 +1199,26 @@ class TxlBlockFn(torch.autograd.Function):
             x = t["y2"]
         pooled = _f32(B, E, like=emb)
         d = kn.txl_block_desc(emb, pos, pos_ids, B, S, H, FF, drop_p, seed, 1e-5, recs, pooled=pooled)
-        kn.txl_block_fwd(d, B, S, H, E, FF, L)
+        nk = {}
+        if pos_g is not None:
+            nk.update(pos_g=pos_g, pos_b=pos_b)
+            if keep:
+                nk.update(pre0=_f32(T, E, like=emb), mean0=_f32(T, like=emb), rstd0=_f32(T, like=emb))
+        if enc_g is not None:
+            nk.update(enc_g=enc_g, enc_b=enc_b)
+            if keep:
+                nk.update(meanF=_f32(T, like=emb), rstdF=_f32(T, like=emb))
+        if nk:
+            kn.txl_block_norms_fwd(d, kn.txl_block_norms(**nk), B, S, H, E, FF, L)
+        else:
+            kn.txl_block_fwd(d, B, S, H, E, FF, L)
         if keep:
             flat = [recs[0]["x"]]
             for t in kept:
                 flat += [t[k] for k in ("y1", "pre1", "mean1", "rstd1", "ctx", "y2", "pre2", "mean2", "rstd2")]
-            ctx.save_for_backward(emb, pos, pos_ids, *flat, *params)
+            stats = [nk[k] for k in ("pre0", "mean0", "rstd0", "meanF", "rstdF") if k in nk]
+            ctx.save_for_backward(emb, pos, pos_ids, *flat, *params, *stats, *(t for t in (pos_g, pos_b, enc_g, enc_b) if t is not None))
+            ctx.norms = (pos_g is not None, enc_g is not None)
             ctx.meta = (B, S, E, H, FF, L, drop_p, seed)
             ctx.pos_identity = bool(getattr(pos_ids, "_hulc_arange", False)) and pos_ids.numel() == S
             ctx.share = kn.coop_share()                    # (the posterior as a forked branch: the backward launch keeps to the same share of the device)
@@ -1211,14 +1229,25 @@ class TxlBlockFn(torch.autograd.Function):
         B, S, E, H, FF, L, drop_p, seed = ctx.meta
         saved = ctx.saved_tensors
         emb, pos, pos_ids, x0 = saved[:4]
-        acts, params = saved[4:4 + 9 * L], saved[4 + 9 * L:]
+        acts, params, rest = saved[4:4 + 9 * L], saved[4 + 9 * L:4 + 21 * L], list(saved[4 + 21 * L:])
+        pn, en = ctx.norms
+        nk = {}
+        if pn:
+            nk.update(pre0=rest.pop(0), mean0=rest.pop(0), rstd0=rest.pop(0))
+        if en:
+            nk.update(meanF=rest.pop(0), rstdF=rest.pop(0))
+        if pn:
+            nk.update(pos_g=rest.pop(0), pos_b=rest.pop(0))
+        if en:
+            nk.update(enc_g=rest.pop(0), enc_b=rest.pop(0))
+        NL = 2 * L + pn + en                                # LayerNorms of the launch: two per layer, then LN_pos, then LN_enc
         T = B * S
         dev = emb.device
         like = dpooled = _c(dpooled)
         bf = dict(dtype=torch.bfloat16, device=dev)
         recs, outs = [], []
         x = x0
-        lnp = _f32(2 * L, B, 2, E, like=like)              # every LayerNorm's per-sequence partials: one reduce launch
+        lnp = _f32(NL, B, 2, E, like=like)                 # every LayerNorm's per-sequence partials: one reduce launch
         for li in range(L):
             w_in, b_in, w_out, b_out, w1, b1, w2, b2, g1, be1, g2, be2 = params[12 * li:12 * li + 12]
             y1, pre1, mean1, rstd1, ctxb, y2, pre2, mean2, rstd2 = acts[9 * li:9 * li + 9]
@@ -1235,15 +1264,28 @@ class TxlBlockFn(torch.autograd.Function):
             x = y2
         demb = _f32(B, S, E, like=like)
         d = kn.txl_block_desc(emb, pos, pos_ids, B, S, H, FF, drop_p, seed, 1e-5, recs, dpooled=dpooled, demb=demb, share=ctx.share)
-        kn.txl_block_bwd(d, B, S, H, E, FF, L)
+        if pn:
+            nk["lnp0"] = lnp[2 * L]
+        if en:
+            nk["lnpF"] = lnp[2 * L + pn]
+        if nk:
+            kn.txl_block_norms_bwd(d, kn.txl_block_norms(**nk), B, S, H, E, FF, L)
+        else:
+            kn.txl_block_bwd(d, B, S, H, E, FF, L)
         grads = [None] * (12 * L)                           # per layer in _TXL_KEYS order
+        ngrads = [None] * 4                                 # pos_g, pos_b, enc_g, enc_b
         dgs, dbs, accs = [], [], []
         for li in range(L):
             for j in (8, 10):                               # (g1, be1), (g2, be2): one flag per LayerNorm
                 k = 12 * li + j
                 (dg, db), acc, grads[k:k + 2] = gradsink.joint(params[k:k + 2], None, like)
                 dgs.append(dg); dbs.append(db); accs.append(acc)
-        kn.ln_partial_reduce_multi(lnp, B, E, dgs, dbs, accs)
+        for j, on, names in ((0, pn, ("pos_g", "pos_b")), (2, en, ("enc_g", "enc_b"))):
+            if on:
+                (dg, db), acc, ngrads[j:j + 2] = gradsink.joint((nk[names[0]], nk[names[1]]), None, like)
+                dgs.append(dg); dbs.append(db); accs.append(acc)
+        for i in range(0, NL, 8):                           # (one launch; L = 4 with both norms: ten LayerNorms, two launches)
+            kn.ln_partial_reduce_multi(lnp[i:i + 8], B, E, dgs[i:i + 8], dbs[i:i + 8], accs[i:i + 8])
         for li in range(L):
             w_in, b_in, w_out, b_out, w1, b1, w2, b2 = params[12 * li:12 * li + 8]
             o, xin, y1, ctxb = outs[li]
@@ -1256,7 +1298,7 @@ class TxlBlockFn(torch.autograd.Function):
                          defer=grads[k] is None and grads[k + 1] is None)
         # the position table: rows pos_ids of its gradient = the sum of demb over the batch (AddPosFn.backward)
         dpos = _pos_table_grad(demb, pos if ctx.pos_identity else None, pos.shape, pos_ids) if ctx.needs_input_grad[1] else None
-        return (demb if ctx.needs_input_grad[0] else None, dpos, None, None, None, None, *grads)
+        return (demb if ctx.needs_input_grad[0] else None, dpos, None, None, None, None, *ngrads, *grads)
 
 
 def txl_block_ok(emb, layer_params, S: int, nhead: int) -> bool:
@@ -1268,10 +1310,11 @@ def txl_block_ok(emb, layer_params, S: int, nhead: int) -> bool:
             and not switches.on("NO_TXL_BLOCK") and not switches.on("NO_FUSED_TXL") and not switches.on("NO_FUSED_FFN"))
 
 
-def transformer_trunk_pooled(emb, pos, pos_ids, layer_params, nhead: int, drop_p: float, seed: int):
-    """mean_s(TransformerEncoder(dropout(emb + pos[pos_ids]))) — only call after txl_block_ok"""
+def transformer_trunk_pooled(emb, pos, pos_ids, layer_params, nhead: int, drop_p: float, seed: int, pos_norm=None, enc_norm=None):
+    """mean_s(TransformerEncoder(dropout(emb + pos[pos_ids]))) — only call after txl_block_ok.  pos_norm / enc_norm: (weight, bias) of the
+    LayerNorm between the position add and the dropout (positional_normalize) / behind the last layer (encoder_normalize), or None"""
     params = [p[k] for p in layer_params for k in _TXL_KEYS]
-    return TxlBlockFn.apply(emb, pos, pos_ids, int(nhead), float(drop_p), int(seed), *params)
+    return TxlBlockFn.apply(emb, pos, pos_ids, int(nhead), float(drop_p), int(seed), *(pos_norm or (None, None)), *(enc_norm or (None, None)), *params)
 
 
 # ------------------------------------------------------------------------------------------------

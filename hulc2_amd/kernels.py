@@ -1236,6 +1236,35 @@ def txl_block_bwd(d, B, S, H, E, FF, L):
     _call("hulc_txl_block_bwd", _c.byref(d), key=("txl_block_bwd", B, S, L), flops=_txl_block_flops(B, S, H, E, FF, L, True))
 
 
+_TXL_NORM_FWD = ("pos_g", "pos_b", "pre0", "mean0", "rstd0", "enc_g", "enc_b", "meanF", "rstdF")
+_TXL_NORM_BWD = ("pos_g", "pos_b", "pre0", "mean0", "rstd0", "lnp0", "enc_g", "enc_b", "meanF", "rstdF", "lnpF")
+
+
+def txl_block_norms(**tensors):
+    """the operands of the two LayerNorm stages of hulc_txl_block_norms_fwd / _bwd as {name: tensor or None}: pos_g, pos_b, pre0, mean0,
+    rstd0, lnp0, enc_g, enc_b, meanF, rstdF, lnpF; a missing key or None is a null pointer (pos_g / enc_g null: that stage is off)"""
+    n = dict.fromkeys(_TXL_NORM_FWD + ("lnp0", "lnpF"))
+    for name, v in tensors.items():
+        if name not in n:
+            raise _L.HulcKernelError("txl_block_norms: no operand named %s" % name)
+        if v is None:
+            continue
+        _require_cuda(v)
+        if not v.is_contiguous() or v.dtype != torch.float32:
+            raise _L.HulcKernelError("txl_block_norms: %s must be contiguous float32" % name)
+        n[name] = v
+    return n
+
+
+def txl_block_norms_fwd(d, n, B, S, H, E, FF, L):
+    """txl_block_fwd with the optional LayerNorm stages, operands from txl_block_norms() (both off: the same launch)"""
+    _call("hulc_txl_block_norms_fwd", _c.byref(d), *[n[k] for k in _TXL_NORM_FWD], key=("txl_block_norms_fwd", B, S, L), flops=_txl_block_flops(B, S, H, E, FF, L, False))
+
+
+def txl_block_norms_bwd(d, n, B, S, H, E, FF, L):
+    _call("hulc_txl_block_norms_bwd", _c.byref(d), *[n[k] for k in _TXL_NORM_BWD], key=("txl_block_norms_bwd", B, S, L), flops=_txl_block_flops(B, S, H, E, FF, L, True))
+
+
 def residual_bf16(p32, hi, lo, segments):
     """lo = bf16(p32 - float(hi)) on the segments {src offset, count, dst offset} (int64 (n, 3) device tensor)"""
     _call("hulc_residual_bf16", p32, hi, lo, segments, segments.shape[0])

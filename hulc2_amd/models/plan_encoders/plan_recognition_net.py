@@ -1,14 +1,17 @@
 """Plan recognition (posterior) transformer.
 
 Mirrors hulc2.models.plan_encoders.plan_recognition_net.PlanRecognitionTransformersNetwork (reference
-plan_recognition_net.py:77-148): learned positions, 2 post-norm encoder layers (8 heads of 16), fc 128->4096,
-mean over the sequence, fc_state.  nn.TransformerEncoder is instantiated only as the parameter container that
-yields the reference's state_dict keys; the arithmetic is HIP (MFMA GEMM chains, per-(batch,head) attention
+plan_recognition_net.py:77-168): learned positions or the sinusoid table (position_embedding), 2 post-norm encoder
+layers (8 heads of 16), an optional final LayerNorm of the encoder (encoder_normalize), fc 128->4096, mean over the
+sequence, fc_state.  positional_normalize (a LayerNorm between the position add and the dropout) is still refused at
+construction, although its stage exists in the kernels.  nn.TransformerEncoder is instantiated only as the parameter
+container that yields the reference's state_dict keys; the arithmetic is HIP (MFMA GEMM chains, per-(batch,head) attention
 waves, fused residual+dropout+LayerNorm).
 
 The sequence mean is taken before the 128->4096 projection: mean_s(W x_s + b) = W mean_s(x_s) + b exactly, which
 removes 31/32 of that layer's FLOPs.
 """
+import math
 from typing import Tuple
 
 import torch
@@ -29,6 +32,28 @@ def trunk_site(modality_scope: str) -> int:
     return MODALITY_SITES["lang" if "lang" in modality_scope else "vis"]
 
 
+class PositionalEncoding(nn.Module):
+    """the parameter-free position table of position_embedding = false (plan_recognition_net.py:151-167): the persistent buffer
+    pe (max_len, 1, d_model) with pe[t, 0, 2i] = sin(t w_i), pe[t, 0, 2i + 1] = cos(t w_i), w_i = 10000^(-2i / d_model), evaluated in
+    float32 like the reference's.  The trunk kernels read it as the (max_len, d_model) table `table`."""
+
+    def __init__(self, d_model: int, max_len: int = 5000):
+        super().__init__()
+        if d_model % 2:
+            raise NotImplementedError("sinusoid positions: an even d_model")
+        # (the expression of the public PyTorch tutorial pytorch.org/tutorials/beginner/transformer_tutorial.html, which the reference names
+        # as its source; the same float32 operations in the same order are what makes the table equal the reference's to the last bit)
+        t = torch.arange(0, max_len, dtype=torch.float32).unsqueeze(1)
+        w = torch.exp(torch.arange(0, d_model, 2).float() * (-math.log(10000.0) / d_model))
+        pe = torch.zeros(max_len, 1, d_model)
+        pe[:, 0, 0::2], pe[:, 0, 1::2] = torch.sin(t * w), torch.cos(t * w)
+        self.register_buffer("pe", pe)
+
+    @property
+    def table(self) -> torch.Tensor:
+        return self.pe.view(self.pe.shape[0], self.pe.shape[2])
+
+
 class PlanRecognitionTransformersNetwork(nn.Module):
     def __init__(self, num_heads: int, num_layers: int, encoder_hidden_size: int, fc_hidden_size: int, plan_features: int,
                  in_features: int, action_space: int, encoder_normalize: bool, positional_normalize: bool,
@@ -36,20 +61,26 @@ class PlanRecognitionTransformersNetwork(nn.Module):
         super().__init__()
         if in_features % num_heads != 0 or in_features // num_heads != 16:
             raise NotImplementedError("attention kernel is specialised for head_dim 16 without padding (128 / 8)")
-        if not position_embedding or encoder_normalize or positional_normalize:
-            raise NotImplementedError("configured path: learned position embedding, no extra norms "
-                                      "(conf/model/plan_recognition/transformers.yaml)")
+        if positional_normalize:
+            # (the LayerNorm stage exists in the trunk launches, functional.transformer_trunk_pooled(pos_norm=...); the module does not
+            # take the switch: its refusal is part of the suite's contract, tests/test_host_cpu.py::test_unsupported_configs_fail_loudly)
+            raise NotImplementedError("positional_normalize is not enabled in this module (conf/model/plan_recognition/transformers.yaml)")
         self.in_features, self.plan_features, self.action_space = in_features, plan_features, action_space
         self.padding = False
         self.dist = dist
         self.hidden_size = fc_hidden_size
-        self.position_embedding, self.encoder_normalize, self.positional_normalize = True, False, False
+        self.position_embedding, self.encoder_normalize = bool(position_embedding), bool(encoder_normalize)
+        self.positional_normalize = False
         self.num_heads, self.num_layers, self.dropout_p = num_heads, num_layers, float(dropout_p)
-        self.position_embeddings = nn.Embedding(max_position_embeddings, in_features)
+        if self.position_embedding:
+            self.position_embeddings = nn.Embedding(max_position_embeddings, in_features)
+        else:
+            self.positional_encoder = PositionalEncoding(in_features)
         layer = nn.TransformerEncoderLayer(in_features, num_heads, dim_feedforward=encoder_hidden_size, dropout=float(dropout_p))
-        self.layernorm = nn.LayerNorm(in_features)
+        self.layernorm = nn.LayerNorm(in_features)                 # (always constructed, as the reference does; unused here)
         self.dropout = nn.Dropout(p=float(dropout_p))
-        self.transformer_encoder = nn.TransformerEncoder(layer, num_layers=num_layers, norm=None, enable_nested_tensor=False)
+        self.transformer_encoder = nn.TransformerEncoder(layer, num_layers=num_layers, norm=nn.LayerNorm(in_features) if self.encoder_normalize else None,
+                                                         enable_nested_tensor=False)
         self.fc = nn.Linear(in_features, fc_hidden_size)
         self.fc_state = self.dist.build_state(fc_hidden_size, plan_features)
 
@@ -92,16 +123,23 @@ class PlanRecognitionTransformersNetwork(nn.Module):
         p = self.dropout_p if self.training else 0.0
         position_ids = self._position_ids(S, perceptual_emb.device)
         layers = [self._layer_params(l) for l in range(self.num_layers)]
+        # the position table: the learned embedding, or the sinusoid buffer (a table without a gradient: rows arange(S) of either)
+        table = self.position_embeddings.weight if self.position_embedding else self.positional_encoder.table
+        enc = self.transformer_encoder.norm
+        enc_norm = (enc.weight, enc.bias) if self.encoder_normalize else None
         if HF.txl_block_ok(perceptual_emb, layers, S, self.num_heads):
-            # position embedding -> every layer -> sequence mean: one launch per direction, one workgroup per sequence (csrc/txl_block.hip)
-            pooled = HF.transformer_trunk_pooled(perceptual_emb, self.position_embeddings.weight, position_ids, layers, self.num_heads, p, seed)
+            # position embedding -> every layer -> sequence mean: one launch per direction, one workgroup per sequence (csrc/txl_block.hip;
+            # with a LayerNorm switched on, the same two launches with its stage: csrc/txl_block_norms.hip)
+            pooled = HF.transformer_trunk_pooled(perceptual_emb, table, position_ids, layers, self.num_heads, p, seed, None, enc_norm)
         else:
-            x = HF.AddPosFn.apply(perceptual_emb, self.position_embeddings.weight, position_ids, p, seed, True)
+            x = HF.AddPosFn.apply(perceptual_emb, table, position_ids, p, seed, True)
             x = x.reshape(B * S, E)
             with kn.site_scope("txl"):
                 for l in range(self.num_layers):
                     x = HF.transformer_encoder_layer(x, layers[l], B, S, self.num_heads, p, seed + 100 * (l + 1))
             with kn.site_scope("pool"):
+                if enc_norm:
+                    x = HF.layer_norm(x, *enc_norm)
                 pooled = HF.SeqMeanFn.apply(x.reshape(B, S, E))
         # selective precision: seq_feat feeds the contrastive head, whose gradient is a cancelling remainder of nearly identical
         # rows — its projection runs exact-fp32 inside a bf16 step (67 MFLOP of the step's 904 GFLOP)

@@ -11,7 +11,10 @@ from typing import Dict, Tuple
 
 def trainable_shapes(static_hw=(200, 200), hidden=2048, plan=1024, n_mix=10, act_dims=6, fc_hidden=4096,
                      d_model=128, ff=2048, n_layers=2, max_pos=32, goal=32, lang_in=384,
-                     decoder_in=1120) -> "OrderedDict[str, Tuple[int, ...]]":
+                     decoder_in=1120, encoder_normalize=False, positional_normalize=False,
+                     position_embedding=True) -> "OrderedDict[str, Tuple[int, ...]]":
+    """encoder_normalize / positional_normalize / position_embedding: the posterior transformer's switches
+    (conf/model/plan_recognition/transformers.yaml); the defaults are the yaml's."""
     s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
 
     def lin(name, o, i):
@@ -38,8 +41,9 @@ def trainable_shapes(static_hw=(200, 200), hidden=2048, plan=1024, n_mix=10, act
         lin(f"plan_proposal.fc_model.{i}", hidden, hidden)
     lin("plan_proposal.fc_state.0", plan, hidden)
     # plan recognition (posterior) transformer
-    s["plan_recognition.position_embeddings.weight"] = (max_pos, d_model)
-    ln("plan_recognition.layernorm", d_model)
+    if position_embedding:
+        s["plan_recognition.position_embeddings.weight"] = (max_pos, d_model)
+    ln("plan_recognition.layernorm", d_model)                    # (always constructed; used with positional_normalize)
     for l in range(n_layers):
         p = f"plan_recognition.transformer_encoder.layers.{l}."
         s[p + "self_attn.in_proj_weight"] = (3 * d_model, d_model)
@@ -49,6 +53,8 @@ def trainable_shapes(static_hw=(200, 200), hidden=2048, plan=1024, n_mix=10, act
         lin(p + "linear2", d_model, ff)
         ln(p + "norm1", d_model)
         ln(p + "norm2", d_model)
+    if encoder_normalize:
+        ln("plan_recognition.transformer_encoder.norm", d_model)
     lin("plan_recognition.fc", fc_hidden, d_model)
     lin("plan_recognition.fc_state.0", plan, fc_hidden)
     # goal encoders
@@ -78,8 +84,11 @@ def trainable_shapes(static_hw=(200, 200), hidden=2048, plan=1024, n_mix=10, act
     return s
 
 
-def buffer_shapes(n_mix=10, act_dims=6) -> Dict[str, Tuple[int, ...]]:
+def buffer_shapes(n_mix=10, act_dims=6, position_embedding=True, d_model=128) -> Dict[str, Tuple[int, ...]]:
+    """position_embedding=False: the posterior's sinusoid table (PositionalEncoding.pe, max_len 5000) takes the place of the learned one"""
+    sinus = {} if position_embedding else {"plan_recognition.positional_encoder.pe": (5000, 1, d_model)}
     return {
+        **sinus,
         "perceptual_encoder.rgb_static_encoder.spatial_softmax.x_map": (441,),
         "perceptual_encoder.rgb_static_encoder.spatial_softmax.y_map": (441,),
         "perceptual_encoder.rgb_static_encoder.spatial_softmax.temperature": (1,),

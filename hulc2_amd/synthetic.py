@@ -24,7 +24,7 @@ def fill_state_dict_(sd: Dict[str, torch.Tensor], seed: int) -> None:
     scale), LayerNorm gains 1 + 0.1 N(0,1), LayerNorm biases 0.1 N(0,1), embeddings N(0,1).
     Registered buffers (maps, bounds, eye) are left untouched."""
     skip = ("x_map", "y_map", "temperature", "one_hot_embedding_eye", ".ones", "gripper_bounds",
-            "action_max_bound", "action_min_bound")
+            "action_max_bound", "action_min_bound", "positional_encoder.pe")
     for name, t in sd.items():
         if not t.is_floating_point() or any(s in name for s in skip):
             continue
@@ -41,7 +41,7 @@ def fill_state_dict_(sd: Dict[str, torch.Tensor], seed: int) -> None:
                 t.copy_(torch.randn(t.shape, generator=g) * 0.1)
         elif name == "logit_scale":
             t.fill_(math.log(1 / 0.07))
-        elif ".ln." in name or ".norm1." in name or ".norm2." in name or ".layernorm." in name:
+        elif ".ln." in name or ".norm1." in name or ".norm2." in name or ".layernorm." in name or ".transformer_encoder.norm." in name:
             r = torch.randn(t.shape, generator=g) * 0.1
             t.copy_(r + 1.0 if leaf == "weight" else r)
         elif "position_embeddings" in name:

@@ -560,6 +560,29 @@ typedef struct hulc_txl_block_desc {
 long hulc_txl_block_workspace(int B, int L);
 int hulc_txl_block_fwd(const hulc_txl_block_desc* d, void* stream);
 int hulc_txl_block_bwd(const hulc_txl_block_desc* d, void* stream);
+/* (added under ABI 7 — new symbols only; every earlier prototype, struct layout and hulc_abi_version() are unchanged.)  PLAN RECOGNITION
+ * NORMS: the two optional LayerNorms of conf/model/plan_recognition/transformers.yaml inside the same two launches
+ * (plan_recognition_net.py:118-121, 140-143), eps = the descriptor's.
+ *   positional_normalize (pos_g, pos_b non-null): x0 = dropout(LN_pos(emb + pos[pos_ids])) with the dropout stream and element index of
+ *     the plain launch (the same mask for the same seed).  Forward keeps pre0 = emb + pos (T, E) and mean0 / rstd0 (T,) (all three or none:
+ *     inference); backward sends the gradient through the dropout, then through LN_pos into demb, and leaves the per-sequence
+ *     {dgamma, dbeta} partials lnp0 (B, 2, E).
+ *   encoder_normalize (enc_g, enc_b non-null): pooled = mean_s LN_enc(y2 of the last layer) (nn.TransformerEncoder(norm=...); its input is
+ *     kept anyway).  Forward keeps meanF / rstdF (T,) (both or none); backward sends dpooled / S through LN_enc ahead of the last layer and
+ *     leaves the partials lnpF (B, 2, E).
+ * The partials have the layout of lnp1 / lnp2 (hulc_ln_partial_reduce_multi).  Positions s >= S contribute to nothing.  Shared sequences:
+ * every member computes both stages (identical values); the exchange protocol is untouched.  A null pos_g / enc_g switches that stage
+ * off; with both off the call IS the launch hulc_txl_block_fwd / _bwd makes (bit-identical results).  Refused without a launch, outputs
+ * untouched: everything hulc_txl_block_fwd / _bwd refuse; gamma without beta or beta without gamma (-3); statistics kept in part (-3);
+ * backward without the kept statistics or the partial buffer of an enabled stage (-1).
+ * The stages' operands go by value, not in a descriptor struct (the list of descriptor structs of this header is pinned):
+ *   pos_g, pos_b (E,) LN_pos weight / bias, null = stage off; pre0 (T, E), mean0, rstd0 (T,) kept; lnp0 (B, 2, E) backward out;
+ *   enc_g, enc_b (E,) LN_enc weight / bias, null = stage off; meanF, rstdF (T,) kept; lnpF (B, 2, E) backward out. */
+int hulc_txl_block_norms_fwd(const hulc_txl_block_desc* d, const float* pos_g, const float* pos_b, float* pre0, float* mean0, float* rstd0,
+                             const float* enc_g, const float* enc_b, float* meanF, float* rstdF, void* stream);
+int hulc_txl_block_norms_bwd(const hulc_txl_block_desc* d, const float* pos_g, const float* pos_b, const float* pre0, const float* mean0,
+                             const float* rstd0, float* lnp0, const float* enc_g, const float* enc_b, const float* meanF, const float* rstdF,
+                             float* lnpF, void* stream);
 
 /* ---- a stack of Linear(+ReLU) layers on M <= 64 rows as one persistent launch (bf16 compute) -------------------------------------- */
 /* y_l = f_l(y_{l-1} W_l^T + b_l), l = 0 .. nl-1 (nl <= 8): the per-sequence MLPs of the policy — PlanProposalNetwork (plan_proposal_net.py:
