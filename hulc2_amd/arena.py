@@ -94,7 +94,7 @@ def plan_tiles(params, offsets, names, member, groups, group_spans):
     mats = []
     for p, off in zip(params, offsets):
         nm = names.get(id(p), "")
-        if p.dim() != 2 or "rnn.weight_hh" in nm or "rnn.weight_ih_l1" in nm or min(p.shape) < 8 or id(p) in member:
+        if p.dim() != 2 or "rnn.weight_hh" in nm or "rnn.weight_ih_l1" in nm or "birnn_model.weight_hh" in nm or min(p.shape) < 8 or id(p) in member:
             continue
         mats.append((p, off, tuple(p.shape)))
     mats += [(gi, group_spans[gi], tuple(g["shape"])) for gi, (_, g) in enumerate(groups) if len(g["shape"]) == 2]

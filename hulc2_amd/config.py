@@ -18,8 +18,10 @@ DISTRIBUTIONS = {
 def default_model_config(gripper_control: bool = True, dropout_p: float = 0.1, static_hw=(200, 200), distribution: str = "discrete",
                          dropout_vis_fc: float = 0.0, word_dropout_p: float = 0.0, l2_normalize_output: bool = False,
                          l2_normalize_goal_embeddings: bool = False, policy_rnn_dropout_p: float = 0.0, encoder_normalize: bool = False,
-                         positional_normalize: bool = False, position_embedding: bool = True) -> Config:
-    """distribution: "discrete" (the headline config) or "continuous" (`model/distribution=continuous`).  policy_rnn_dropout_p goes to the
+                         positional_normalize: bool = False, position_embedding: bool = True, posterior: str = "transformers") -> Config:
+    """posterior: "transformers" (conf/model/plan_recognition/transformers.yaml, the headline config) or "birnn"
+    (conf/model/plan_recognition/birnn.yaml: the recurrent posterior; its feature width is 4096 too, so proj_vis_lang.im_dim stays).
+    distribution: "discrete" (the headline config) or "continuous" (`model/distribution=continuous`).  policy_rnn_dropout_p goes to the
     action decoder's yaml (nn.RNN's inter-layer dropout).  encoder_normalize / positional_normalize / position_embedding: the switches of
     plan_recognition/transformers.yaml (a final LayerNorm of the encoder, a LayerNorm behind the position add, learned positions or
     sinusoids).  The encoder regularisers:
@@ -27,7 +29,9 @@ def default_model_config(gripper_control: bool = True, dropout_p: float = 0.1, s
     l2_normalize_goal_embeddings to both goal encoders, word_dropout_p to language_goal/default.yaml; per-encoder values: edit the returned
     config (e.g. cfg["perceptual_encoder"]["rgb_gripper"]["dropout_vis_fc"])."""
     act7 = [1.0] * 7
-    return Config.wrap({
+    if posterior not in ("transformers", "birnn"):
+        raise NotImplementedError(f"posterior={posterior!r}: plan_recognition=transformers and plan_recognition=birnn are built")
+    cfg = Config.wrap({
         "_target_": "hulc2.models.hulc2.Hulc2",
         "_recursive_": False,
         "perceptual_encoder": {
@@ -73,6 +77,11 @@ def default_model_config(gripper_control: bool = True, dropout_p: float = 0.1, s
             "output_dim": 32, "proj_lang": True},
         "kl_beta": 0.01, "kl_balancing_mix": 0.8, "replan_freq": 30, "use_clip_auxiliary_loss": True, "clip_auxiliary_loss_beta": 3.0,
     })
+    if posterior == "birnn":
+        cfg["plan_recognition"] = Config.wrap({
+            "_target_": "hulc2.models.plan_encoders.plan_recognition_net.PlanRecognitionBiRNNNetwork", "in_features": None,
+            "plan_features": None, "action_space": 7, "birnn_dropout_p": 0.0})
+    return cfg
 
 
 def real_world_model_config(dropout_p: float = 0.1, dropout_vis_fc: float = 0.0, word_dropout_p: float = 0.0, l2_normalize_output: bool = False,

@@ -64,6 +64,15 @@ struct WaveDropP : WaveP {
     const unsigned long long* keep;              // K-side mode: the keep BITS of the sweep in fragment order, written by rnn_keep_bits_kernel
 };
 
+// The paired instances (hulc_rnn_wavefront_pair) take the plain parameter block plus the second half's own external term and destinations: like
+// the dropout instances they leave WaveP, and with it the plain and DROP instances, as they were.
+struct WavePairP : WaveP {
+    float* z2; long z2_step;                     // fp32 rows of the second half: wave step tau writes z2 + tau*z2_step, columns H .. 2H-1
+    int zb2_row0, zb2_step;                      // bf16 mirror region of the second half at wave step tau = zb2_row0 + tau * zb2_step
+    const float* add2; long add2_step, ld_add2;  // per-step external term of the second half (nullable)
+    const float* add2c; long ld_add2c;           // per-row constant of the second half (nullable)
+};
+
 // The bf16 state copy is the only data exchanged between workgroups inside the kernel.  Measured alternatives:
 //   * agent-scope release/acquire fences around the barrier: buffer_wbl2 / buffer_inv from 2048 waves per step, ~90 us/step;
 //   * device-coherent (sc1) loads and stores on a ping-pong buffer: no cache maintenance, but every read bypasses the
@@ -125,10 +134,19 @@ HULC_DEVICE bf16x8_t load_w(const uint16_t* w, long ld, int n, int k) {
 //   2, N side (backward sweep): second = f2( keep * s . (z[:, :H] wB1^T) + z[:, H:] wB2^T ): one draw per output element, taken beside the
 //      epilogue operands while the state loads are in flight.
 // Everything the workgroups exchange, wave 0's vmcnt constant included, is untouched: see the note at the keep-bit load.
-template <int H, bool WT, bool TS = false, int DROP = 0>      // TS: the probe's instance with phase time stamps (-DHULC_PROBES builds, HULC_RNN_DBG & 8) — the stamps' branches cost the plain kernel 5 %
-__global__ __launch_bounds__(512) void rnn_wavefront2_kernel(std::conditional_t<DROP != 0, WaveDropP, WaveP> p) {
+//
+// PAIR (hulc_rnn_wavefront_pair): the two halves are independent recurrences, z_{tau+1} = [ f1(z_tau[:, :H] wA^T + ..) | f2(z_tau[:, H:] wB2^T + ..) ],
+// both written at every one of the S wave steps (no lag): the wB1 product is gone (no wfb registers, no MFMAs), the second tile reads af[1] only
+// and has an external term of its own.  The exchange copy stays in sweep order (it is what the next wave step reads); the second half's fp32
+// rows and row-major mirror rows go where WavePairP says.  PAIR == 2 is the solo sweep (wB2 == NULL): the second half is neither loaded,
+// multiplied nor stored, so a sub-step has KPW state loads, and wave 0's vmcnt constant is NLD = the state loads of a sub-step in every mode.
+template <int H, bool WT, bool TS = false, int DROP = 0, int PAIR = 0>      // TS: the probe's instance with phase time stamps (-DHULC_PROBES builds, HULC_RNN_DBG & 8) — the stamps' branches cost the plain kernel 5 %
+__global__ __launch_bounds__(512) void rnn_wavefront2_kernel(std::conditional_t<PAIR != 0, WavePairP, std::conditional_t<DROP != 0, WaveDropP, WaveP>> p) {
+    static_assert(PAIR == 0 || (DROP == 0 && !TS), "the paired sweep has no dropout and no probe instance");
+    constexpr int NH = PAIR == 2 ? 1 : 2;        // state halves a sub-step loads
     constexpr int KS = H / 32;
     constexpr int KPW = KS / 8;
+    constexpr int NLD = NH * KPW;                // state loads of a wave per sub-step
     constexpr int NR = DROP ? 3 : 2;             // reduction tiles: first half, second half, (DROP) the masked wB1 product
     static_assert(KS % 8 == 0, "H must be a multiple of 256");
     static_assert(DROP == 0 || KPW == 8, "the keep bits of a lane's sub-step are one 64-bit word: 8 fragments of 8 values");
@@ -149,9 +167,11 @@ __global__ __launch_bounds__(512) void rnn_wavefront2_kernel(std::conditional_t<
     for (int q = 0; q < KPW; ++q) {
         const int k = (wave * KPW + q) * 32 + kb * 8;
         wfa[q] = load_w<WT>(p.wA, p.ldA, n0 + i, k);
-        wfb[q] = load_w<WT>(p.wB1, p.ldB1, n0 + i, k);
-        union { bf16x8_t b; uint4 u; } wc; wc.b = load_w<WT>(p.wB2, p.ldB2, n0 + i, k);
-        wlds[wave][q][lane] = wc.u;
+        if constexpr (PAIR == 0) wfb[q] = load_w<WT>(p.wB1, p.ldB1, n0 + i, k);
+        if constexpr (PAIR != 2) {
+            union { bf16x8_t b; uint4 u; } wc; wc.b = load_w<WT>(p.wB2, p.ldB2, n0 + i, k);
+            wlds[wave][q][lane] = wc.u;
+        }
     }
     // this thread's output of a sub-step: tile ct = tid >> 8, accumulator element e
     const int oct = tid >> 8, oe = tid & 255, oln = oe & 63;
@@ -167,10 +187,12 @@ __global__ __launch_bounds__(512) void rnn_wavefront2_kernel(std::conditional_t<
             const int m = rowhalf * 32 + g * 16 + orow;
             obias[g] = b0;
             if (!oct && p.add1c) obias[g] += p.add1c[(long)(m < p.B ? m : p.B - 1) * p.ld_add1c + on];
+            if constexpr (PAIR == 1) { if (oct && p.add2c) obias[g] += p.add2c[(long)(m < p.B ? m : p.B - 1) * p.ld_add2c + on]; }
         }
     }
     int pending = -1;                                             // wave 0: group whose exchange stores await their acknowledgement
-    const int U = 2 * (p.S + 1);
+    const int NT = PAIR ? p.S : p.S + 1;                           // wave steps
+    const int U = 2 * NT;
     unsigned long long dseed = 0ull; float dkeep = 1.f;           // (DROP) the call's RNG stream and 1 / (1 - p), as dropout_scale computes it
     if constexpr (DROP != 0) { dseed = p.seed ^ (p.seed_dev ? p.seed_dev[0] : 0ull); dkeep = 1.0f / (1.0f - p.drop_p); }
 #ifdef HULC_PROBES
@@ -186,7 +208,7 @@ __global__ __launch_bounds__(512) void rnn_wavefront2_kernel(std::conditional_t<
     for (int u = 0; u < U; ++u) {
         const int g = u & 1, tau = u >> 1;
         RNN_TS(u, 0)
-        const bool first_on = tau < p.S, second_on = tau >= 1;
+        const bool first_on = PAIR ? true : tau < p.S, second_on = PAIR ? PAIR == 1 : tau >= 1;
         const int om = rowhalf * 32 + g * 16 + orow;
         if (tau > 0) {
             // ---- inputs of (g, tau): every workgroup of this row half has published the group's z_tau
@@ -215,15 +237,15 @@ __global__ __launch_bounds__(512) void rnn_wavefront2_kernel(std::conditional_t<
         if (mul) {
             const uint16_t* a = p.xb + (long)(p.zb_row0 + tau * p.zb_dir) * 64 * ldz + (long)(rowhalf * 32 + g * 16 + i) * 8;
 #pragma unroll
-            for (int hf = 0; hf < 2; ++hf)
+            for (int hf = 0; hf < NH; ++hf)
 #pragma unroll
                 for (int q = 0; q < KPW; ++q) af[hf][q] = load_state8(a + ((long)(hf * (H / 8) + (wave * KPW + q) * 4 + kb) * 64) * 8);
         }
         if (wave == 0 && pending >= 0) {
             // the previous sub-step's exchange stores are OLDER than everything this wave has issued since (compiler barrier after them): once at
-            // most the 2 * KPW state loads above are outstanding they have been acknowledged — the other workgroups may read them
+            // most the NLD (2 * KPW; solo sweep: KPW) state loads above are outstanding they have been acknowledged — the other workgroups may read them
             asm volatile("" ::: "memory");
-            if (mul) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * KPW) : "memory");
+            if (mul) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NLD) : "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             if (lane == 0) __hip_atomic_fetch_add(p.bar + (pending * 8 + xcd) * RNN_CTR_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             pending = -1;
@@ -236,7 +258,10 @@ __global__ __launch_bounds__(512) void rnn_wavefront2_kernel(std::conditional_t<
             if (oct == 0) {
                 if (p.add1 && first_on) oadd = p.add1[(long)tau * p.add1_step + (long)m * p.ld_add1 + on];
                 if (p.mask1 && first_on) omask = p.mask1[(long)tau * p.mask1_step + (long)m * p.ld_mask1 + on];
-            } else if (p.mask2 && second_on) omask = p.mask2[(long)tau * p.mask2_step + (long)m * p.ld_mask2 + on];
+            } else {
+                if constexpr (PAIR == 1) { if (p.add2) oadd = p.add2[(long)tau * p.add2_step + (long)m * p.ld_add2 + on]; }
+                if (p.mask2 && second_on) omask = p.mask2[(long)tau * p.mask2_step + (long)m * p.ld_mask2 + on];
+            }
         }
         // (DROP) the mask of this sub-step.  K side: this lane's 64 keep bits — a vector load issued HERE, behind wave 0's wait like the
         // epilogue operands above (the "memory" clobbers of that block keep it below): between the exchange stores and the wait wave 0 still
@@ -252,7 +277,10 @@ __global__ __launch_bounds__(512) void rnn_wavefront2_kernel(std::conditional_t<
             }
         }
         if (mul) {
-            if constexpr (DROP == 0) {
+            if constexpr (PAIR != 0) {
+#pragma unroll
+                for (int q = 0; q < KPW; ++q) acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0][q], wfa[q], acc[0], 0, 0, 0);
+            } else if constexpr (DROP == 0) {
 #pragma unroll
                 for (int q = 0; q < KPW; ++q) {
                     acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0][q], wfa[q], acc[0], 0, 0, 0);
@@ -268,10 +296,12 @@ __global__ __launch_bounds__(512) void rnn_wavefront2_kernel(std::conditional_t<
 #pragma unroll
                 for (int q = 0; q < KPW; ++q) acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[0][q], wfa[q], acc[0], 0, 0, 0);
             }
+            if constexpr (PAIR != 2) {
 #pragma unroll
-            for (int q = 0; q < KPW; ++q) {
-                union { bf16x8_t b; uint4 u; } wc; wc.u = wlds[wave][q][lane];
-                acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1][q], wc.b, acc[1], 0, 0, 0);
+                for (int q = 0; q < KPW; ++q) {
+                    union { bf16x8_t b; uint4 u; } wc; wc.u = wlds[wave][q][lane];
+                    acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[1][q], wc.b, acc[1], 0, 0, 0);
+                }
             }
             if constexpr (DROP == 1) {
                 // the masked product last: the keep bits were requested after the state loads
@@ -320,12 +350,14 @@ __global__ __launch_bounds__(512) void rnn_wavefront2_kernel(std::conditional_t<
         __syncthreads();
         RNN_TS(u, 5)
         const int region = p.zb_row0 + (tau + 1) * p.zb_dir;
+        // which halves of this sub-step are stored (plain: the first half while it is on, the second always, zero at tau = 0; paired: both; solo: the first)
+        auto stored = [&](int ct) { return PAIR ? (ct == 0 || PAIR == 1) : (ct == 1 || first_on); };
         if (wave == 0) {
             // exchange copy: lane = (row 0..15, half, 8-column chunk); skipped once nobody reads it any more (last wave step)
             const int row = lane & 15, ct = (lane >> 4) & 1, ch = lane >> 5;
             const int m = rowhalf * 32 + g * 16 + row;
-            if (tau < p.S) {
-                if (m < p.B && (ct == 1 || first_on)) {
+            if (PAIR ? tau + 1 < p.S : tau < p.S) {
+                if (m < p.B && stored(ct)) {
                     const uint4 v16 = *(const uint4*)&otile[row][ct][ch * 8];
                     unsigned long long* dst = (unsigned long long*)(p.xb + (long)region * 64 * ldz + ((long)(ct * (H / 8) + n0 / 8 + ch) * 64 + m) * 8);
                     __hip_atomic_store(dst, (unsigned long long)v16.x | ((unsigned long long)v16.y << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -338,20 +370,23 @@ __global__ __launch_bounds__(512) void rnn_wavefront2_kernel(std::conditional_t<
             // fp32 rows: 16 rows x 2 halves x 4 chunks of 4 columns = 128 float4 pieces
             const int t = tid - 64, row = t & 15, ct = (t >> 4) & 1, ch = t >> 5;
             const int m = rowhalf * 32 + g * 16 + row;
-            if (m < p.B && (ct == 1 || first_on)) {
+            if (m < p.B && stored(ct)) {
                 float* zn = p.z + (long)(tau + 1) * p.z_step;
+                if constexpr (PAIR == 1) { if (ct) zn = p.z2 + (long)tau * p.z2_step; }
                 *(float4*)(zn + (long)m * ldz + ct * H + n0 + ch * 4) = *(const float4*)&ftile[row][ct][ch * 4];
             }
         } else if (wave == 3) {
             const int row = lane & 15, ct = (lane >> 4) & 1, ch = lane >> 5;
             const int m = rowhalf * 32 + g * 16 + row;
-            if (m < p.B && (ct == 1 || first_on))
-                *(uint4*)(p.zb + (long)region * p.B * ldz + (long)m * ldz + ct * H + n0 + ch * 8) = *(const uint4*)&otile[row][ct][ch * 8];
+            int rg = region;
+            if constexpr (PAIR == 1) { if (ct) rg = p.zb2_row0 + tau * p.zb2_step; }
+            if (m < p.B && stored(ct))
+                *(uint4*)(p.zb + (long)rg * p.B * ldz + (long)m * ldz + ct * H + n0 + ch * 8) = *(const uint4*)&otile[row][ct][ch * 8];
         } else if (wave == 4 && p.zt) {
             // transposed mirror: lane = (half, column, 8-row chunk)
             const int ct = lane >> 5, col = (lane >> 1) & 15, ch = lane & 1;
             const int m = rowhalf * 32 + g * 16 + ch * 8;
-            if (m < p.B && (ct == 1 || first_on)) {               // B % 8 == 0 (checked by the launcher)
+            if (m < p.B && stored(ct)) {                          // B % 8 == 0 (checked by the launcher); the paired launcher hands in no transposed mirror
                 unsigned w[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) w[e] = (unsigned)otile[ch * 8 + 2 * e][ct][col] | ((unsigned)otile[ch * 8 + 2 * e + 1][ct][col] << 16);
@@ -369,10 +404,13 @@ __global__ __launch_bounds__(512) void rnn_wavefront2_kernel(std::conditional_t<
         if (p.err_sticky) __hip_atomic_fetch_or(p.err_sticky, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     if (__hip_atomic_load(p.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-        float* zn = p.z + (long)(p.S + 1) * p.z_step;
+        // the last row each half wrote (plain: row S+1, whose first half is never produced)
+        float* zn = p.z + (long)(PAIR ? p.S : p.S + 1) * p.z_step;
+        float* zn2 = zn;
+        if constexpr (PAIR == 1) zn2 = p.z2 + (long)(p.S - 1) * p.z2_step;
         for (int o = tid; o < 32 * 16; o += 512) {
             const int m = rowhalf * 32 + o / 16, n = n0 + o % 16;
-            if (m < p.B) { zn[(long)m * ldz + n] = __builtin_nanf(""); zn[(long)m * ldz + H + n] = __builtin_nanf(""); }
+            if (m < p.B) { zn[(long)m * ldz + n] = __builtin_nanf(""); if (PAIR != 2) zn2[(long)m * ldz + H + n] = __builtin_nanf(""); }
         }
     }
 }
@@ -447,18 +485,25 @@ extern "C" long hulc_rnn_wavefront_mirror_offset(void) { return RNN_WS_HEADER; }
 extern "C" long hulc_rnn_wavefront_mirror_t_offset(int S, int B, int H) { return B % 8 ? 0 : RNN_WS_HEADER + (long)(S + 2) * (B + 64) * 2 * H * 2; }
 extern "C" long hulc_rnn_wavefront_workspace(int S, int B, int H) { return RNN_WS_HEADER + (long)(S + 2) * (B + 64 + (B % 8 ? 0 : B)) * 2 * H * 2; }
 
-// the refusals of a sweep, all of them before the first launch: a refused call writes nothing.  0 = the call may go ahead
-static int wave_refusal(const hulc_rnn_wave_desc* d, void* ws) {
-    if (!d || !ws || !d->z || !d->wA || !d->wB1 || !d->wB2) return hulc_fail(-1, "hulc_rnn_wavefront: null pointer");
-    if (d->H != 2048) return hulc_fail(-2, "hulc_rnn_wavefront: built for hidden size 2048 (use the per-step hulc_gemm path otherwise)");
-    if (d->B < 1 || d->B > 64 || d->S < 1) return hulc_fail(-2, "hulc_rnn_wavefront: needs 1 <= B <= 64 rows and S >= 1");
-    if ((!d->tA && (d->ldA % 8 || (uintptr_t)d->wA % 16)) || (!d->tB1 && (d->ldB1 % 8 || (uintptr_t)d->wB1 % 16)) ||
-        (!d->tB2 && (d->ldB2 % 8 || (uintptr_t)d->wB2 % 16)))
-        return hulc_fail(-4, "hulc_rnn_wavefront: k-major weights must be 16-byte aligned");
-    if (d->tA != d->tB1 || d->tA != d->tB2) return hulc_fail(-3, "hulc_rnn_wavefront: the three weight matrices share one layout (tA == tB1 == tB2)");
-    if ((uintptr_t)ws % 16 || RNN_WS_HEADER % 16) return hulc_fail(-4, "hulc_rnn_wavefront: workspace must be 16-byte aligned");
+// the refusals of a sweep, all of them before the first launch: a refused call writes nothing.  0 = the call may go ahead.  One list for
+// every entry point: `pair` (hulc_rnn_wavefront_pair) takes no wB1 (pointer, pitch and layout flag are ignored) and an optional wB2
+#define WAVE_FAIL(code, text) return hulc_fail(code, pair ? "hulc_rnn_wavefront_pair: " text : "hulc_rnn_wavefront: " text)
+static int wave_refusal(const hulc_rnn_wave_desc* d, void* ws, bool pair = false) {
+    if (!d || !ws || !d->z || !d->wA || (!pair && (!d->wB1 || !d->wB2))) WAVE_FAIL(-1, "null pointer");
+    const bool hasB1 = !pair, hasB2 = d->wB2 != nullptr;
+    if (d->H != 2048) WAVE_FAIL(-2, "built for hidden size 2048 (use the per-step hulc_gemm path otherwise)");
+    if (d->B < 1 || d->B > 64 || d->S < 1) WAVE_FAIL(-2, "needs 1 <= B <= 64 rows and S >= 1");
+    if ((!d->tA && (d->ldA % 8 || (uintptr_t)d->wA % 16)) || (hasB1 && !d->tB1 && (d->ldB1 % 8 || (uintptr_t)d->wB1 % 16)) ||
+        (hasB2 && !d->tB2 && (d->ldB2 % 8 || (uintptr_t)d->wB2 % 16)))
+        WAVE_FAIL(-4, "k-major weights must be 16-byte aligned");
+    if ((hasB1 && d->tA != d->tB1) || (hasB2 && d->tA != d->tB2)) {
+        if (pair) return hulc_fail(-3, "hulc_rnn_wavefront_pair: the two weight matrices share one layout (tA == tB2)");
+        return hulc_fail(-3, "hulc_rnn_wavefront: the three weight matrices share one layout (tA == tB1 == tB2)");
+    }
+    if ((uintptr_t)ws % 16 || RNN_WS_HEADER % 16) WAVE_FAIL(-4, "workspace must be 16-byte aligned");
     return 0;
 }
+#undef WAVE_FAIL
 
 // the kernel's parameter block of an accepted call
 static void wave_params(const hulc_rnn_wave_desc* d, void* ws, WaveP& p) {
@@ -574,6 +619,40 @@ extern "C" int hulc_rnn_wavefront_drop(const hulc_rnn_wave_desc* d, float drop_p
         else rnn_wavefront2_kernel<2048, false, false, 2><<<2 * (2048 / 16), 512, 0, s>>>(p);
     }
     return hulc_check_launch("hulc_rnn_wavefront_drop");
+}
+
+// see include/hulc2_amd.h
+extern "C" int hulc_rnn_wavefront_pair(const hulc_rnn_wave_desc* d, float* z2, long z2_step, int mirror_row0, int mirror_step, const float* add2,
+                                       long add2_step, long ld_add2, const float* add2c, long ld_add2c, void* ws, void* stream) {
+    // the refusals, all of them before the first launch: the sweeps' common list, then this entry's own
+    if (const int rc = wave_refusal(d, ws, true)) return rc;
+    const bool solo = d->wB2 == nullptr;
+    if (d->mirror_t) return hulc_fail(-2, "hulc_rnn_wavefront_pair: no transposed mirror (mirror_t must be 0)");
+    if (!solo) {
+        if (!z2) return hulc_fail(-1, "hulc_rnn_wavefront_pair: null pointer (z2)");
+        const long ra = mirror_row0, rb = (long)mirror_row0 + (long)(d->S - 1) * mirror_step;
+        if (ra < 0 || ra > d->S + 1 || rb < 0 || rb > d->S + 1)
+            return hulc_fail(-2, "hulc_rnn_wavefront_pair: mirror_row0 + tau * mirror_step must stay in 0 .. S+1 for tau = 0 .. S-1");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    WavePairP p;
+    wave_params(d, ws, p);
+    p.wB1 = nullptr; p.zt = nullptr;
+    p.z2 = z2; p.z2_step = z2_step; p.zb2_row0 = mirror_row0; p.zb2_step = mirror_step;
+    p.add2 = add2; p.add2_step = add2_step; p.ld_add2 = ld_add2; p.add2c = add2c; p.ld_add2c = ld_add2c;
+    // the launch in front of the sweep: barrier words, the mirror's initial region and (zero_edges) the fp32 row at d->z
+    const long na = RNN_WS_HEADER / 16, nb = (long)d->B * 2 * d->H * 2 / 16, nz0 = d->zero_edges ? (long)d->B * 2 * d->H / 4 : 0;
+    const long n = na > nb ? (na > nz0 ? na : nz0) : (nb > nz0 ? nb : nz0);
+    rnn_prep_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>((uint4*)ws, na, (uint4*)(p.zb + (long)p.zb_row0 * d->B * 2 * d->H), nb,
+                                                              d->zero_edges ? (float4*)d->z : nullptr, nz0, nullptr, d->B, d->H);
+    if (solo) {
+        if (d->tA) rnn_wavefront2_kernel<2048, true, false, 0, 2><<<2 * (2048 / 16), 512, 0, s>>>(p);
+        else rnn_wavefront2_kernel<2048, false, false, 0, 2><<<2 * (2048 / 16), 512, 0, s>>>(p);
+    } else {
+        if (d->tA) rnn_wavefront2_kernel<2048, true, false, 0, 1><<<2 * (2048 / 16), 512, 0, s>>>(p);
+        else rnn_wavefront2_kernel<2048, false, false, 0, 1><<<2 * (2048 / 16), 512, 0, s>>>(p);
+    }
+    return hulc_check_launch("hulc_rnn_wavefront_pair");
 }
 
 // see include/hulc2_amd.h

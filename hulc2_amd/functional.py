@@ -1616,6 +1616,171 @@ class DecoderRNNFn(torch.autograd.Function):
         return (dplan, demb, dgoal, None, None, r_ih0, dw_hh0, rb_ih0, db_hh0, dw_ih1, dw_hh1, db_ih1, db_hh1, None, None, None, None)
 
 
+# ------------------------------------------------------------------------------------------------
+# BiRNN plan recognition: nn.RNN(128, 2048, num_layers=2, relu, bidirectional=True) and out[:, -1]
+# reference: plan_recognition_net.py (PlanRecognitionBiRNNNetwork)
+# ------------------------------------------------------------------------------------------------
+BIRNN_KEYS = tuple(f"{n}_l{l}{r}" for l in (0, 1) for r in ("", "_reverse") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"))
+
+
+def _birnn_sweep(persistent, buf, S, B, Hd, w_f, w_b, transposed, up, down, bias1=(None, None), bias2=(None, None), relu=False):
+    """One bidirectional layer (or its backward) over the time-aligned buffer buf (S + 2, B, 2H), buf[t + 1] = [first half at time t | second
+    half at time t].  `up` / `down` = (add: (S, B, .) view whose rows have pitch ld, ld, mask: (S, B, .) view of pitch 2H or None) of the half
+    that walks time upwards / downwards; forward: up = the forward direction in the first half, backward (transposed): up = the reverse direction's
+    delta in the second half.  w_b None: the solo sweep (the first half alone, walking `up` when not transposed, `down` when transposed).
+    Persistent: one launch (kernels.rnn_wavefront_pair), -> its bf16 mirror; else S steps of kn.gemm per half, -> None."""
+    step = B * 2 * Hd
+    first_up = not transposed                                         # which half walks up: the first in a forward sweep, the second in a backward one
+    (add_u, ld_u, mask_u), (add_d, ld_d, mask_d) = up, down
+    if persistent:
+        kw = dict(relu=relu, zero_edges=True, bias1=bias1, bias2=bias2)
+        a1, a2 = ("add1", "add2") if first_up else ("add2", "add1")
+        m1, m2 = ("mask1", "mask2") if first_up else ("mask2", "mask1")
+        if add_u is not None:
+            kw.update({a1: add_u[0], a1 + "_step": add_u.stride(0), "ld_" + a1: ld_u})
+            if mask_u is not None:
+                kw.update({m1: mask_u[0], m1 + "_step": step, "ld_" + m1: 2 * Hd})
+        if add_d is not None:
+            kw.update({a2: add_d[S - 1], a2 + "_step": -add_d.stride(0), "ld_" + a2: ld_d})
+            if mask_d is not None:
+                kw.update({m2: mask_d[S - 1], m2 + "_step": -step, "ld_" + m2: 2 * Hd})
+        if w_b is not None:
+            kw.update(dict(z2=buf[S], z2_step=-step, mirror2_row0=S, mirror2_step=-1) if first_up else dict(z2=buf[1], z2_step=step, mirror2_row0=1, mirror2_step=1))
+        return kn.rnn_wavefront_pair(buf[0] if first_up else buf[S + 1], step if first_up else -step, S, B, Hd, w_f, w_b, transposed, **kw)
+    # per-step path: buf is zero-filled, so the rows at either end are the zero initial states
+    halves = [(0, w_f, bias1, up if first_up else down, first_up)]
+    if w_b is not None:
+        halves.append((Hd, w_b, bias2, down if first_up else up, not first_up))
+    for col, w, bias, (add, ld, mask), goes_up in halves:
+        for t in (range(S) if goes_up else range(S - 1, -1, -1)):
+            prev = buf[t if goes_up else t + 2][:, col:col + Hd]
+            kn.gemm(prev, w, buf[t + 1][:, col:col + Hd], B, Hd, Hd, 2 * Hd, Hd, 2 * Hd, bias=bias[0], add=add[t], ld_add=ld,
+                    mask=None if mask is None else mask[t], ld_mask=2 * Hd if mask is not None else 0, relu=relu)
+    return None
+
+
+@_scoped
+class BiRNNPosteriorFn(torch.autograd.Function):
+    """emb (B, S, E) -> x (B, 2H) = out[:, -1] of the 2-layer bidirectional ReLU RNN, h_{-1} = 0: x = [hf1_{S-1} | hb1_{S-1}].
+
+    Only layer 1's forward direction is a recurrence the output can see: hb1_{S-1} is the FIRST step of layer 1's reverse direction,
+    relu(X1[S-1] W_ih_l1_reverse^T + b_ih + b_hh) with X1[t] = [hf0_t | hb0_t], so weight_hh_l1_reverse never reaches x (its gradient is
+    exactly zero, and both reverse biases of layer 1 get the same bits).  Launches, all time-major:
+      * pre0 = emb [W_ih_l0; W_ih_l0_reverse]^T + b_ih (one GEMM per direction into the two column halves of one (S, B, 2H) buffer);
+      * layer 0 as ONE paired sweep over the time-aligned buffer z0[t + 1] = [hf0_t | hb0_t], the second half walking time backwards;
+      * U = X1 W_ih_l1^T + b_ih (one GEMM over all tokens), layer 1's forward direction as a solo sweep, one skinny GEMM for hb1_{S-1}.
+    Backward mirrors it: a solo delta sweep for layer 1 (g_x[:, :H] enters at t = S-1 only), dX1 = Delta1 W_ih_l1 plus the reverse
+    direction's row at t = S-1, a paired delta sweep for layer 0 with the halves walking the other way, and the weight gradients as
+    token-major GEMMs into the gradsink destinations.  Outside _rnn_persistent's geometry every sweep is S steps of kn.gemm per half."""
+
+    @staticmethod
+    def forward(ctx, emb, *params):
+        p = dict(zip(BIRNN_KEYS, params))
+        B, S, E = emb.shape
+        Hd = p["weight_hh_l0"].shape[0]
+        dev = emb.device
+        M = S * B
+        persistent = _rnn_persistent(B, Hd, dev)
+        buf = torch.empty if persistent else torch.zeros
+        emb_t = emb.permute(1, 0, 2).contiguous()                                       # (S, B, E) time-major
+        pre0 = _f32(S, B, 2 * Hd, like=emb)
+        kn.gemm(emb_t, weight_operand(p["weight_ih_l0"]), pre0, M, Hd, E, E, E, 2 * Hd, bias=p["bias_ih_l0"])
+        kn.gemm(emb_t, weight_operand(p["weight_ih_l0_reverse"]), pre0[:, :, Hd:], M, Hd, E, E, E, 2 * Hd, bias=p["bias_ih_l0_reverse"])
+        z0 = buf(S + 2, B, 2 * Hd, dtype=torch.float32, device=dev)                      # z0[t + 1] = [hf0_t | hb0_t]
+        z0_16 = _birnn_sweep(persistent, z0, S, B, Hd, weight_operand(p["weight_hh_l0"]), weight_operand(p["weight_hh_l0_reverse"]), False,
+                             (pre0, 2 * Hd, None), (pre0[:, :, Hd:], 2 * Hd, None), bias1=(p["bias_hh_l0"], None),
+                             bias2=(p["bias_hh_l0_reverse"], None), relu=True)
+        if persistent:
+            # hb0_S = 0, the operand of dW_hh_l0_reverse next to hb0_{S-1}: the one row of the buffer and of its mirror nobody writes
+            z0[S + 1].zero_()
+            z0_16[S + 1].zero_()
+        x1 = z0_16[1:S + 1] if persistent else z0[1:S + 1]                               # (S, B, 2H) = X1, contiguous
+        u = _f32(S, B, Hd, like=emb)
+        kn.gemm(x1, weight_operand(p["weight_ih_l1"]), u, M, Hd, 2 * Hd, 2 * Hd, 2 * Hd, Hd, bias=p["bias_ih_l1"])
+        z1 = buf(S + 2, B, 2 * Hd, dtype=torch.float32, device=dev)                      # z1[t + 1][:, :H] = hf1_t (the second half is unused)
+        z1_16 = _birnn_sweep(persistent, z1, S, B, Hd, weight_operand(p["weight_hh_l1"]), None, False, (u, Hd, None), (None, 0, None),
+                             bias1=(p["bias_hh_l1"], None), relu=True)
+        x = _f32(B, 2 * Hd, like=emb)
+        x[:, :Hd].copy_(z1[S][:, :Hd])
+        kn.gemm(z0[S], weight_operand(p["weight_ih_l1_reverse"]), x[:, Hd:], B, Hd, 2 * Hd, 2 * Hd, 2 * Hd, 2 * Hd,
+                bias=p["bias_ih_l1_reverse"], add=p["bias_hh_l1_reverse"], ld_add=0, relu=True)
+        ctx.save_for_backward(emb_t, z0, z1, x, *params)
+        ctx.mirrors = (z0_16, z1_16)
+        ctx.persistent = persistent
+        return x
+
+    @staticmethod
+    def backward(ctx, g):
+        emb_t, z0, z1, x, *params = ctx.saved_tensors
+        p = dict(zip(BIRNN_KEYS, params))
+        S, B, E = emb_t.shape
+        Hd = z0.shape[2] // 2
+        dev = g.device
+        M = S * B
+        persistent = ctx.persistent
+        z0_16, z1_16 = ctx.mirrors
+        buf = torch.empty if persistent else torch.zeros
+        f32 = dict(dtype=torch.float32, device=dev)
+        g = _c(g)
+        # layer 1, reverse direction: one step, delta = g[:, H:] * (hb1_{S-1} > 0)
+        db1 = torch.empty(B, Hd, **f32)
+        kn.relu_bwd(g[:, Hd:].contiguous(), x[:, Hd:].contiguous(), db1, B * Hd)
+        # layer 1, forward direction: delta1_t = (g[:, :H] [t = S-1] + delta1_{t+1} W_hh_l1) * (hf1_t > 0), d1[t + 1][:, :H] = delta1_t
+        g1 = torch.zeros(S, B, Hd, **f32)
+        g1[S - 1].copy_(g[:, :Hd])
+        d1 = buf(S + 2, B, 2 * Hd, **f32)
+        w = weight_operand(p["weight_hh_l1"]) if persistent else weight_operand(p["weight_hh_l1"], "t")
+        d1_16 = _birnn_sweep(persistent, d1, S, B, Hd, w, None, True, (None, 0, None), (g1, Hd, z1[1:S + 1]))
+        # dX1 = Delta1 W_ih_l1, plus the reverse direction's one row at t = S-1
+        dl1 = (d1_16 if persistent else d1)[1:S + 1]                                     # rows (t, b), the first half = delta1_t, pitch 2H
+        dx1 = torch.empty(S, B, 2 * Hd, **f32)
+        kn.gemm(dl1, weight_operand(p["weight_ih_l1"], "t"), dx1, M, 2 * Hd, Hd, 2 * Hd, Hd, 2 * Hd)
+        kn.gemm(db1, weight_operand(p["weight_ih_l1_reverse"], "t"), dx1[S - 1], B, 2 * Hd, Hd, Hd, Hd, 2 * Hd, accumulate=True)
+        # layer 0: d0[t + 1] = [deltaf0_t | deltab0_t]; the forward direction's delta walks time downwards, the reverse direction's upwards
+        d0 = buf(S + 2, B, 2 * Hd, **f32)
+        lay = (None,) if persistent else ("t",)
+        d0_16 = _birnn_sweep(persistent, d0, S, B, Hd, weight_operand(p["weight_hh_l0"], *lay), weight_operand(p["weight_hh_l0_reverse"], *lay), True,
+                             (dx1[:, :, Hd:], 2 * Hd, z0[1:S + 1][:, :, Hd:]), (dx1, 2 * Hd, z0[1:S + 1]))
+        zw0, zw1, dw0, dw1 = (z0_16, z1_16, d0_16, d1_16) if persistent else (z0, z1, d0, d1)
+
+        def wgrad(dlt, inp, ncols, ld_inp, param, bias, rows=M):
+            """param.grad (+)= dlt^T inp over `rows` token rows (dlt: pitch 2H unless it is the (B, H) delta of the single reverse step),
+            bias.grad (+)= the column sums of dlt, fused into the same launch"""
+            out, acc, ret = gradsink.dest(param, None, g)
+            bout, acc_b, bret = gradsink.dest(bias, None, g) if bias is not None else (None, False, None)
+            kn.gemm(dlt, inp, out, Hd, ncols, rows, dlt.stride(-2), ld_inp, ncols, a_kmajor=False, b_kmajor=False, accumulate=acc,
+                    rowsum=bout, rowsum_accumulate=acc_b)
+            return ret, bret
+
+        gr = {}
+        gr["weight_ih_l1"], gr["bias_ih_l1"] = wgrad(dw1[1:S + 1], zw0[1:S + 1], 2 * Hd, 2 * Hd, p["weight_ih_l1"], p["bias_ih_l1"])
+        gr["weight_hh_l1"], gr["bias_hh_l1"] = wgrad(dw1[1:S + 1], zw1[0:S], Hd, 2 * Hd, p["weight_hh_l1"], p["bias_hh_l1"])      # hf1_{t-1}
+        gr["weight_ih_l1_reverse"], _ = wgrad(db1, z0[S], 2 * Hd, 2 * Hd, p["weight_ih_l1_reverse"], None, rows=B)
+        # both reverse biases of layer 1 saw the same delta: one reduction, the same bits to both
+        db = torch.empty(Hd, **f32)
+        kn.colsum(db1, B, Hd, Hd, db)
+        gr["bias_ih_l1_reverse"] = gradsink.deliver(p["bias_ih_l1_reverse"], db)
+        gr["bias_hh_l1_reverse"] = gradsink.deliver(p["bias_hh_l1_reverse"], db.clone())
+        # weight_hh_l1_reverse never reaches x: exact zeros
+        out, acc, gr["weight_hh_l1_reverse"] = gradsink.dest(p["weight_hh_l1_reverse"], None, g)
+        if not acc:
+            out.zero_()
+        gr["weight_hh_l0"], gr["bias_hh_l0"] = wgrad(dw0[1:S + 1], zw0[0:S], Hd, 2 * Hd, p["weight_hh_l0"], p["bias_hh_l0"])      # hf0_{t-1}
+        gr["weight_hh_l0_reverse"], gr["bias_hh_l0_reverse"] = wgrad(dw0[1:S + 1][:, :, Hd:], zw0[2:S + 2][:, :, Hd:], Hd, 2 * Hd,
+                                                                     p["weight_hh_l0_reverse"], p["bias_hh_l0_reverse"])           # hb0_{t+1}
+        gr["weight_ih_l0"], gr["bias_ih_l0"] = wgrad(dw0[1:S + 1], emb_t, E, E, p["weight_ih_l0"], p["bias_ih_l0"])
+        gr["weight_ih_l0_reverse"], gr["bias_ih_l0_reverse"] = wgrad(dw0[1:S + 1][:, :, Hd:], emb_t, E, E, p["weight_ih_l0_reverse"], p["bias_ih_l0_reverse"])
+        demb_t = torch.empty(S, B, E, **f32)
+        kn.gemm(d0[1:S + 1], weight_operand(p["weight_ih_l0"], "t"), demb_t, M, E, Hd, 2 * Hd, Hd, E)
+        kn.gemm(d0[1:S + 1][:, :, Hd:], weight_operand(p["weight_ih_l0_reverse"], "t"), demb_t, M, E, Hd, 2 * Hd, Hd, E, accumulate=True)
+        return (demb_t.permute(1, 0, 2).contiguous(), *[gr[k] for k in BIRNN_KEYS])
+
+
+def birnn_posterior(emb, rnn: torch.nn.RNN):
+    """x (B, 2H) = rnn(emb)[0][:, -1] for a 2-layer bidirectional ReLU nn.RNN used as a parameter container"""
+    return BiRNNPosteriorFn.apply(emb, *[getattr(rnn, k) for k in BIRNN_KEYS])
+
+
 @_scoped
 class EmbFanoutFn(torch.autograd.Function):
     """emb (N, S, D) -> (emb[:, 0], emb[:n_last, -1], emb, emb[:, :, lo:hi] time-major (S, N, hi-lo)): the four views Hulc2.training_step

@@ -1322,6 +1322,27 @@ def rnn_wavefront_drop(z0, z_step, S, B, H, wA, wB1, wB2, transposed, drop_p, se
     return _rnn_wave(d, z0, z_step, S, B, H, wA, wB1, wB2, transposed, **a)
 
 
+def rnn_wavefront_pair(z0, z_step, S, B, H, wA, wB2, transposed, z2=None, z2_step=0, mirror2_row0=0, mirror2_step=1, add1=None, add1_step=0,
+                       ld_add1=0, add1c=None, add2=None, add2_step=0, ld_add2=0, add2c=None, bias1=(None, None), bias2=(None, None), mask1=None,
+                       mask1_step=0, ld_mask1=0, mask2=None, mask2_step=0, ld_mask2=0, relu=False, zero_edges=False):
+    """One bidirectional RNN layer (or its backward) as one persistent sweep of two independent recurrences (hulc_rnn_wavefront_pair): wave
+    step tau = 0 .. S-1 writes f1(z[:, :H] wA^T + add1[tau] + add1c + biases) and f2(z[:, H:] wB2^T + add2[tau] + add2c + biases).  The first
+    half's rows advance from z0 by z_step like rnn_wavefront's; the second half's fp32 rows start at z2 (a view of the row wave step 0
+    writes, column 0) and advance by z2_step, its mirror rows are regions mirror2_row0 + tau * mirror2_step, and add2 / mask2 have steps of
+    their own, so the second half may walk time backwards inside a time-aligned buffer.  wB2 None is the solo sweep: the first half alone.
+    -> the bf16 row-major mirror (S + 2, B, 2H) in the workspace."""
+    d, transposed = _rnn_wave_desc(z0, z_step, S, B, H, wA, None, wB2, transposed, add1, add1_step, ld_add1, bias1, bias2, mask1, mask1_step,
+                                   ld_mask1, mask2, mask2_step, ld_mask2, relu, False, add1c, zero_edges)
+    lib = _L.load()
+    ws = _ws(lib.hulc_rnn_wavefront_workspace(S, B, H), z0.device)
+    halves = 1 if wB2 is None else 2
+    flops = 2.0 * B * halves * H * H * S
+    nbytes = float(halves) * H * H * 2 + S * B * (halves * H * (4 + 2 * 2) + sum(H * 4 for t in (add1, add2, mask1, mask2) if t is not None))
+    _call("hulc_rnn_wavefront_pair", _c.byref(d), z2, int(z2_step), int(mirror2_row0), int(mirror2_step), add2, int(add2_step), int(ld_add2), add2c,
+          add2c.stride(0) if add2c is not None else 0, ws, key=("rnn_wavefront_pair", S, B, H, int(bool(transposed)), halves), flops=flops, nbytes=nbytes)
+    return _rnn_mirrors(lib, ws, S, B, H, False)[0]
+
+
 def rnn_drop_rows(x, rows, H, row0, drop_p, seed, out32=None, out16=None):
     """out[r, j] = x[r, j] * dropout_scale(seed ^ the device step word, (row0 + r) * H + j, drop_p) for the first `rows` rows of the 2-d fp32
     view x (any row pitch), to an fp32 and / or a bf16 2-d view (hulc_rnn_drop_rows): the decoder RNN's inter-layer mask on rows t * B + b."""
@@ -1336,13 +1357,43 @@ def rnn_drop_rows(x, rows, H, row0, drop_p, seed, out32=None, out16=None):
 def _rnn_wave(drop, z0, z_step, S, B, H, wA, wB1, wB2, transposed, add1, add1_step, ld_add1, bias1, bias2, mask1, mask1_step, ld_mask1,
               mask2, mask2_step, ld_mask2, relu, mirror_t, add1c, zero_edges):
     """the launch behind rnn_wavefront (drop None) and rnn_wavefront_drop (drop: hulc_rnn_wavefront_drop's six mask arguments)"""
+    d, transposed = _rnn_wave_desc(z0, z_step, S, B, H, wA, wB1, wB2, transposed, add1, add1_step, ld_add1, bias1, bias2, mask1, mask1_step, ld_mask1,
+                                   mask2, mask2_step, ld_mask2, relu, mirror_t, add1c, zero_edges)
+    lib = _L.load()
+    ws = _ws((lib.hulc_rnn_wavefront_workspace if drop is None else lib.hulc_rnn_wavefront_drop_workspace)(S, B, H), z0.device)
+    # algorithmic work: S wave steps of a (B x 2H) x (2H x 2H) product with one H x H block structurally zero; bytes: the
+    # three weight matrices once, per step the fp32 state row written + the bf16 copy written and read + add / masks read
+    flops = 2.0 * B * 3 * H * H * S
+    nbytes = 3.0 * H * H * 2 + S * B * (2 * H * 4 + 2 * 2 * H * 2 + (H * 4 if add1 is not None else 0)
+                                        + (H * 4 if mask1 is not None else 0) + (H * 4 if mask2 is not None else 0))
+    if drop is None:
+        _call("hulc_rnn_wavefront", _c.byref(d), ws, key=("rnn_wavefront", S, B, H, int(bool(transposed))), flops=flops, nbytes=nbytes)
+    else:
+        _call("hulc_rnn_wavefront_drop", _c.byref(d), *drop, ws, key=("rnn_wavefront_drop", S, B, H, int(bool(transposed)), drop[3]),
+              flops=flops, nbytes=nbytes + (S * 2048 * 8 * 2 if drop[3] == RNN_DROP_K else 0))
+    return _rnn_mirrors(lib, ws, S, B, H, mirror_t)
+
+
+def _rnn_mirrors(lib, ws, S, B, H, mirror_t):
+    """the bf16 mirrors a sweep left in its workspace: (S + 2, B, 2H) row-major, and the transposed one or None"""
+    off = lib.hulc_rnn_wavefront_mirror_offset() // 2
+    w16 = ws.view(torch.bfloat16)
+    z16 = w16[off:off + (S + 2) * B * 2 * H].view(S + 2, B, 2 * H)
+    offt = lib.hulc_rnn_wavefront_mirror_t_offset(S, B, H) // 2
+    z16t = w16[offt:offt + (S + 2) * B * 2 * H].view(2 * H, (S + 2) * B) if (offt and mirror_t) else None     # (feature, token = row * B + b)
+    return z16, z16t      # bf16 mirror of the S+2 state rows
+
+
+def _rnn_wave_desc(z0, z_step, S, B, H, wA, wB1, wB2, transposed, add1, add1_step, ld_add1, bias1, bias2, mask1, mask1_step, ld_mask1,
+                   mask2, mask2_step, ld_mask2, relu, mirror_t, add1c, zero_edges):
+    """hulc_rnn_wave_desc of a sweep -> (descriptor, the layout flag of wA); a weight given as None is a null pointer (the paired sweep)"""
     for w in (wA, wB1, wB2):
-        if w.dtype != torch.bfloat16:
+        if w is not None and w.dtype != torch.bfloat16:
             raise _L.HulcKernelError("rnn_wavefront: weights must be bf16 shadows (bf16 compute mode)")
     d = _L.RnnWaveDesc()
     d.z, d.z_step = z0.data_ptr(), int(z_step)
-    d.wA, d.wB1, d.wB2 = wA.data_ptr(), wB1.data_ptr(), wB2.data_ptr()
-    d.ldA, d.ldB1, d.ldB2 = wA.stride(0), wB1.stride(0), wB2.stride(0)
+    d.wA, d.wB1, d.wB2 = (w.data_ptr() if w is not None else None for w in (wA, wB1, wB2))
+    d.ldA, d.ldB1, d.ldB2 = (w.stride(0) if w is not None else 0 for w in (wA, wB1, wB2))
     if isinstance(transposed, (tuple, list)):                       # one flag per matrix (wA, wB1, wB2): the launcher refuses mixed layouts
         d.tA, d.tB1, d.tB2 = (int(bool(t)) for t in transposed)
         transposed = d.tA
@@ -1359,24 +1410,7 @@ def _rnn_wave(drop, z0, z_step, S, B, H, wA, wB1, wB2, transposed, add1, add1_st
     d.add1c, d.ld_add1c = (add1c.data_ptr(), add1c.stride(0)) if add1c is not None else (None, 0)
     d.zero_edges = int(bool(zero_edges))
     d.inject_timeout = switches.value("RNN_DBG") & 4
-    lib = _L.load()
-    ws = _ws((lib.hulc_rnn_wavefront_workspace if drop is None else lib.hulc_rnn_wavefront_drop_workspace)(S, B, H), z0.device)
-    # algorithmic work: S wave steps of a (B x 2H) x (2H x 2H) product with one H x H block structurally zero; bytes: the
-    # three weight matrices once, per step the fp32 state row written + the bf16 copy written and read + add / masks read
-    flops = 2.0 * B * 3 * H * H * S
-    nbytes = 3.0 * H * H * 2 + S * B * (2 * H * 4 + 2 * 2 * H * 2 + (H * 4 if add1 is not None else 0)
-                                        + (H * 4 if mask1 is not None else 0) + (H * 4 if mask2 is not None else 0))
-    if drop is None:
-        _call("hulc_rnn_wavefront", _c.byref(d), ws, key=("rnn_wavefront", S, B, H, int(bool(transposed))), flops=flops, nbytes=nbytes)
-    else:
-        _call("hulc_rnn_wavefront_drop", _c.byref(d), *drop, ws, key=("rnn_wavefront_drop", S, B, H, int(bool(transposed)), drop[3]),
-              flops=flops, nbytes=nbytes + (S * 2048 * 8 * 2 if drop[3] == RNN_DROP_K else 0))
-    off = lib.hulc_rnn_wavefront_mirror_offset() // 2
-    w16 = ws.view(torch.bfloat16)
-    z16 = w16[off:off + (S + 2) * B * 2 * H].view(S + 2, B, 2 * H)
-    offt = lib.hulc_rnn_wavefront_mirror_t_offset(S, B, H) // 2
-    z16t = w16[offt:offt + (S + 2) * B * 2 * H].view(2 * H, (S + 2) * B) if (offt and mirror_t) else None     # (feature, token = row * B + b)
-    return z16, z16t      # bf16 mirror of the S+2 state rows
+    return d, transposed
 
 
 def mix_loss_fwd(y, act, out, T, A, n_mix, num_classes, ld, log_scale_min, gripper_alpha, act_min, act_max, nseg=1, time_major_B=0):

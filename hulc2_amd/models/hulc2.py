@@ -282,14 +282,19 @@ class Hulc2(LightningModule):
             # stream of its forward, so the backward forks the same way.  Both branches are cooperative launches that own a CU per workgroup:
             # each keeps to half of the device (kernels.coop_share_scope -> coop_share of the launches' descriptors, include/hulc2_amd.h).  HULC_FORK=0: one after the other.
             fork = fan and kn.fork_branches()
+            # a RECURRENT posterior (plan_recognition=birnn) is no branch: its persistent sweeps own every CU behind a device-wide barrier, and
+            # spinning beside the prior's cooperative chain on a side stream they would time out.  It runs on the main stream, after the prior,
+            # outside coop_share_scope(2); the contrastive branch below keeps its rule
+            fork_post = fork and not getattr(self.plan_recognition, "recurrent", False)
             if fan:
                 emb0, emb_last, emb_rec, emb_dec_t = HF.EmbFanoutFn.apply(emb_all, B, lo, hi)
             if fork:
                 cur, side = torch.cuda.current_stream(emb_all.device), kn.branch_stream(emb_all.device)
+            if fork_post:
                 side.wait_stream(cur)
                 with torch.cuda.stream(side), kn.coop_share_scope(2):
                     pr_all, seq_all = self.plan_recognition(emb_rec)
-            with kn.coop_share_scope(2 if fork else 1):           # (the prior branch's chain launches: half of the device next to the posterior's)
+            with kn.coop_share_scope(2 if fork_post else 1):      # (the prior branch's chain launches: half of the device next to the posterior's)
                 if fan:
                     # selective precision: of the goal encoders only the LANGUAGE one is upstream of the contrastive head; inside a bf16
                     # step with site "goal" it alone runs its forward exactly, the visual one stays on its bf16 chain launch
@@ -328,7 +333,7 @@ class Hulc2(LightningModule):
                     goal_all = torch.cat(goals, dim=0)
                 with kn.site_scope("prior"):
                     pp_all = self.plan_proposal(emb0, goal_all)
-            if fork:
+            if fork_post:
                 cur.wait_stream(side)                      # join: sample + KL consume both branches
                 for t_ in (self.dist.state_tensor(pr_all), seq_all):
                     t_.record_stream(cur)

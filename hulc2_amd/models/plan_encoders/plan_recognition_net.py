@@ -147,3 +147,37 @@ class PlanRecognitionTransformersNetwork(nn.Module):
             seq_feat = HF.mlp(pooled, [(self.fc.weight, self.fc.bias, False)])
         logits = HF.mlp(seq_feat, [(self.fc_state[0].weight, self.fc_state[0].bias, False)])
         return self.dist.forward_dist(logits), seq_feat
+
+
+class PlanRecognitionBiRNNNetwork(nn.Module):
+    """The recurrent posterior of conf/model/plan_recognition/birnn.yaml (the reference's PlanRecognitionBiRNNNetwork): a 2-layer bidirectional
+    ReLU nn.RNN of width 2048 over the perceptual embeddings, its output at the LAST time step, fc_state.  `birnn_model` is the parameter
+    container that yields the reference's state_dict keys; the arithmetic is HIP (functional.BiRNNPosteriorFn: paired persistent sweeps in
+    bf16 compute on a whole MI355X, per-step GEMMs otherwise).  forward -> (state, x) with x = [hf1_{S-1} | hb1_{S-1}] (B, 4096).
+    birnn_dropout_p > 0 (torch drops layer 0's output on its way into layer 1) is not built: refused at construction."""
+
+    recurrent = True          # Hulc2.training_step: not a forked branch (the sweeps' device-wide barrier needs the whole GPU)
+
+    def __init__(self, in_features: int, plan_features: int, action_space: int, birnn_dropout_p: float, dist: Distribution):
+        super().__init__()
+        if float(birnn_dropout_p) != 0.0:
+            raise NotImplementedError("birnn_dropout_p > 0 is not built: conf/model/plan_recognition/birnn.yaml with birnn_dropout_p: 0.0 is supported")
+        self.in_features, self.plan_features, self.action_space = in_features, plan_features, action_space
+        self.dist = dist
+        self.hidden_size = 2048
+        self.birnn_model = nn.RNN(input_size=in_features, hidden_size=self.hidden_size, nonlinearity="relu", num_layers=2, bidirectional=True,
+                                  batch_first=True, dropout=0.0)
+        self.fc_state = self.dist.build_state(2 * self.hidden_size, plan_features)
+
+    def forward(self, perceptual_emb: torch.Tensor, seed: int = TRUNK_SITE) -> Tuple[State, torch.Tensor]:
+        """seed: the dropout site Hulc2 passes to every posterior; this one draws nothing"""
+        x = HF.birnn_posterior(perceptual_emb, self.birnn_model)
+        logits = HF.mlp(x, [(self.fc_state[0].weight, self.fc_state[0].bias, False)])
+        return self.dist.forward_dist(logits), x
+
+
+class PlanRecognitionBiLSTMNetwork(nn.Module):
+    def __init__(self, *args, **kwargs):
+        super().__init__()
+        raise NotImplementedError("the BiLSTM posterior (conf/model/plan_recognition/bilstm.yaml) is not built: plan_recognition=transformers "
+                                  "and plan_recognition=birnn are")

@@ -12,8 +12,10 @@ from typing import Dict, Tuple
 def trainable_shapes(static_hw=(200, 200), hidden=2048, plan=1024, n_mix=10, act_dims=6, fc_hidden=4096,
                      d_model=128, ff=2048, n_layers=2, max_pos=32, goal=32, lang_in=384,
                      decoder_in=1120, encoder_normalize=False, positional_normalize=False,
-                     position_embedding=True) -> "OrderedDict[str, Tuple[int, ...]]":
-    """encoder_normalize / positional_normalize / position_embedding: the posterior transformer's switches
+                     position_embedding=True, posterior="transformers") -> "OrderedDict[str, Tuple[int, ...]]":
+    """posterior: "transformers" or "birnn" (conf/model/plan_recognition/birnn.yaml: the 18 tensors of PlanRecognitionBiRNNNetwork in
+    place of the transformer's; `plan` is then the width of fc_state, 2 * plan_features for the continuous distribution).
+    encoder_normalize / positional_normalize / position_embedding: the posterior transformer's switches
     (conf/model/plan_recognition/transformers.yaml); the defaults are the yaml's."""
     s: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
 
@@ -40,23 +42,34 @@ def trainable_shapes(static_hw=(200, 200), hidden=2048, plan=1024, n_mix=10, act
     for i in (2, 4, 6):
         lin(f"plan_proposal.fc_model.{i}", hidden, hidden)
     lin("plan_proposal.fc_state.0", plan, hidden)
-    # plan recognition (posterior) transformer
-    if position_embedding:
+    # plan recognition (posterior): the bidirectional RNN, or the transformer
+    if posterior == "birnn":
+        for l, i in ((0, d_model), (1, 2 * hidden)):
+            for r in ("", "_reverse"):
+                s[f"plan_recognition.birnn_model.weight_ih_l{l}{r}"] = (hidden, i)
+                s[f"plan_recognition.birnn_model.weight_hh_l{l}{r}"] = (hidden, hidden)
+                s[f"plan_recognition.birnn_model.bias_ih_l{l}{r}"] = (hidden,)
+                s[f"plan_recognition.birnn_model.bias_hh_l{l}{r}"] = (hidden,)
+        lin("plan_recognition.fc_state.0", plan, 2 * hidden)
+    elif posterior != "transformers":
+        raise NotImplementedError(f"posterior={posterior!r}")
+    if posterior == "transformers" and position_embedding:
         s["plan_recognition.position_embeddings.weight"] = (max_pos, d_model)
-    ln("plan_recognition.layernorm", d_model)                    # (always constructed; used with positional_normalize)
-    for l in range(n_layers):
-        p = f"plan_recognition.transformer_encoder.layers.{l}."
-        s[p + "self_attn.in_proj_weight"] = (3 * d_model, d_model)
-        s[p + "self_attn.in_proj_bias"] = (3 * d_model,)
-        lin(p + "self_attn.out_proj", d_model, d_model)
-        lin(p + "linear1", ff, d_model)
-        lin(p + "linear2", d_model, ff)
-        ln(p + "norm1", d_model)
-        ln(p + "norm2", d_model)
-    if encoder_normalize:
-        ln("plan_recognition.transformer_encoder.norm", d_model)
-    lin("plan_recognition.fc", fc_hidden, d_model)
-    lin("plan_recognition.fc_state.0", plan, fc_hidden)
+    if posterior == "transformers":
+        ln("plan_recognition.layernorm", d_model)                    # (always constructed; used with positional_normalize)
+        for l in range(n_layers):
+            p = f"plan_recognition.transformer_encoder.layers.{l}."
+            s[p + "self_attn.in_proj_weight"] = (3 * d_model, d_model)
+            s[p + "self_attn.in_proj_bias"] = (3 * d_model,)
+            lin(p + "self_attn.out_proj", d_model, d_model)
+            lin(p + "linear1", ff, d_model)
+            lin(p + "linear2", d_model, ff)
+            ln(p + "norm1", d_model)
+            ln(p + "norm2", d_model)
+        if encoder_normalize:
+            ln("plan_recognition.transformer_encoder.norm", d_model)
+        lin("plan_recognition.fc", fc_hidden, d_model)
+        lin("plan_recognition.fc_state.0", plan, fc_hidden)
     # goal encoders
     lin("visual_goal.mlp.0", hidden, d_model)
     lin("visual_goal.mlp.2", hidden, hidden)

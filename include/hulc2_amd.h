@@ -778,6 +778,30 @@ int hulc_rnn_wavefront_drop(const hulc_rnn_wave_desc* d, float drop_p, unsigned 
 int hulc_rnn_drop_rows(const float* x, long ldx, long rows, int H, long row0, float drop_p, unsigned long long seed,
                        const unsigned long long* seed_dev, float* out32, long ld32, void* out16, long ld16, void* stream);
 
+/* ---- BiRNN plan recognition: a PAIR of independent recurrences in one persistent sweep --------------------- */
+/* One layer of nn.RNN(nonlinearity="relu", bidirectional=True) of hulc2/models/plan_encoders/plan_recognition_net.py (both directions at
+ * once) and its backward.  The sweep of hulc_rnn_wavefront with the two halves decoupled: the second half has a recurrence, an external
+ * term and a gate of its own, and no one-step lag.  Row 0 (the row at d->z) is zero and is not read; wave step tau = 0 .. S-1 writes
+ *     first  half:  f1( z_tau[:, :H] wA^T  + add1[tau] + add1c + bias1a + bias1b )
+ *     second half:  f2( z_tau[:, H:] wB2^T + add2[tau] + add2c + bias2a + bias2b )
+ * f as above: keep where mask[tau] > 0 when a mask is given, else ReLU when relu != 0; both halves are written at every wave step.
+ * d is hulc_rnn_wavefront's descriptor: d->wB1 is not read (d->ldB1 and d->tB1 are ignored with it), d->mask2 is indexed d->mask2 + tau * d->mask2_step for tau = 0 .. S-1 (like
+ * mask1; a step may be negative, so the second half can walk time the other way), d->mirror_t must be 0, and d->zero_edges clears the
+ * row at d->z only.  The first half's fp32 rows are at d->z + (tau + 1) * d->z_step, columns 0 .. H-1, and its bf16 mirror rows in region
+ * r0 + (tau + 1) * dir (r0 = 0, dir = +1 for z_step > 0; r0 = S+1, dir = -1 otherwise), as in hulc_rnn_wavefront.  The second half goes
+ * where its own arguments say: fp32 to z2 + tau * z2_step, columns H .. 2H-1 (z2 points at column 0 of the row, pitch 2H like d->z), and its bf16
+ * mirror rows to region mirror_row0 + tau * mirror_step (all of them inside 0 .. S+1).  So a caller may keep the state
+ * time-aligned, row t+1 = [forward h_t | backward h_t], while the second half walks time backwards.  The mirror's region r0 is zeroed, the
+ * regions nobody writes are left as they were.
+ * d->wB2 == NULL is the SOLO sweep: the first half alone, the second half idle (its arguments are ignored; no wave step reads or writes
+ * anything of the second half, in the fp32 rows or the mirror).  The launch in front of the sweep is the same in both forms and clears
+ * whole 2H-wide rows: the mirror's region r0, and with d->zero_edges the fp32 row at d->z, second halves included.
+ * H must be 2048, 1 <= B <= 64, S >= 1; wA and wB2 share one layout (tA == tB2).  Refusals come before the first launch and write nothing.
+ * add2 / add2c: the second half's per-step term (add2 + tau * add2_step, row pitch ld_add2) and per-row constant (pitch ld_add2c), nullable.
+ * ws, the barrier, the timeout (NaN in the last row each half wrote, bit 0 of *err_sticky) and the stream rule are hulc_rnn_wavefront's. */
+int hulc_rnn_wavefront_pair(const hulc_rnn_wave_desc* d, float* z2, long z2_step, int mirror_row0, int mirror_step, const float* add2, long add2_step,
+                            long ld_add2, const float* add2c, long ld_add2c, void* ws, void* stream);
+
 /* ---- optimizer ------------------------------------------------------------------------------- */
 /* torch.optim.Adam semantics (hulc2.py:185-198, conf/model/optimizer/adam.yaml) over a flat fp32 arena;
  * bf16_shadow (optional) receives the updated weights rounded to bf16 for the MFMA kernels. */
