@@ -330,11 +330,13 @@ static int gridconv_launch(const void* x, long ldx, const void* wt, void* y, lon
 
 extern "C" int hulc_gridconv3x3(const void* x, long ldx, const void* wt, void* y, long ldy, int N, int H, int W, int Cin, int Cout, int flip_taps,
                                 float* stats, float* out0, const float* bias0, void* stream) {
+    hulc_conv_path_clear();
     return gridconv_launch(x, ldx, wt, y, ldy, N, H, W, Cin, Cout, flip_taps, stats, out0, bias0, nullptr, nullptr, 0, 0, stream);
 }
 
 extern "C" int hulc_gridconv3x3_fused(const void* x, long ldx, const void* wt, void* y, long ldy, int N, int H, int W, int Cin, int Cout, const float* bias,
                                       const void* add, long ldadd, int relu, void* stream) {
+    hulc_conv_path_clear();
     if (!y) return hulc_fail(-1, "hulc_gridconv3x3_fused: null pointer");
     if (add && (ldadd < Cout)) return hulc_fail(-3, "hulc_gridconv3x3_fused: residual rows shorter than Cout");
     return gridconv_launch(x, ldx, wt, y, ldy, N, H, W, Cin, Cout, 0, nullptr, nullptr, nullptr, bias, add, ldadd, relu, stream);
@@ -372,6 +374,7 @@ static int gridconv_launch(const void* x, long ldx, const void* wt, void* y, lon
                 attr = true;                                                                                           \
             }                                                                                                          \
             kern<<<wgs, 256, lds, s>>>(p, (int)gx);                                                                    \
+            hulc_conv_path_set("gridconv_thin<%d,%d> wgs=%d tiles=%d", CINv, NBv, wgs, (int)gx);                       \
         }
         if (Cin == 32 && Cout == 32) GT_LAUNCH(32, 1, 3)
         else if (Cin == 32) GT_LAUNCH(32, 2, 2)
@@ -392,6 +395,7 @@ static int gridconv_launch(const void* x, long ldx, const void* wt, void* y, lon
             attr = true;                                                                                               \
         }                                                                                                              \
         kern<<<dim3(gx, Cout / BNv), 256, lds, s>>>(p);                                                                \
+        hulc_conv_path_set("gridconv<%d,%d,%d> grid=%d tiles=%d", WNv, TNv, KCHv, (int)gx * (Cout / BNv), (int)gx);    \
     }
     // 128-channel k-steps for the layers that put at most one 128 x 128 workgroup on a CU (512-channel maps at 14 x 14): nothing overlaps a
     // workgroup's barriers there, so fewer, longer k-steps

@@ -395,7 +395,7 @@ def _slot_fields(d, x, x2, H, W, Cin, Cout, KH, stride, x_nchw) -> None:
 
 def conv_last_path():
     """(token, plan) of hulc_conv_last_path(): which kernel served this thread's last conv2d_fwd / conv2d_padded_fwd / conv2d_bwd_data /
-    conv2d_bwd_weight call — e.g. ("band_x<32,2,4,4,2>", {"xf32": 0, "bits": 1, "multi": 1, "R": 9, "F": 3, "units": 2, "grid": 2}); a follow-up
+    conv2d_bwd_weight / gridconv3x3 / gridconv3x3_fused call — e.g. ("band_x<32,2,4,4,2>", {"xf32": 0, "bits": 1, "multi": 1, "R": 9, "F": 3, "units": 2, "grid": 2}); a follow-up
     pass (`+relu_bits_pass`, `+cast_pass`) is a key with value 1.  ("", {}) after a refused call.  For tests and diagnostics: nothing acts on it."""
     words = _L.load().hulc_conv_last_path().decode().split()
     if not words:
@@ -1784,7 +1784,9 @@ def sum_chunks(src, W, chunk, dst):
 class Grid:
     """A bf16 map (N, H, W, C) on the padded grid (layout: include/hulc2_amd.h, "PADDED GRID"): `rows` = the 2-D tensor of all rows including
     the zero guards, `t` = rows [guard, guard + R) — the tensor the kernels address.  Every kernel writes all R rows of its output (borders as
-    zero), so only the guards are cleared here."""
+    zero), so only the guards are cleared here.  The one exception is hulc_grid_upcat_bwd's `dsmall`: it stores the pixel rows only and leaves
+    the border rows as they were (stale values of a recycled buffer included); its consumer, hulc_grid_bn_relu_bwd, masks `dout` by the border
+    of its own `out` and never uses them."""
 
     _pool = {}            # (device, N, H, W, C) -> [buffers]: guards zeroed once, recycled step after step (Grid.begin_step)
     _cursor = {}

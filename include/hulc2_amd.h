@@ -35,6 +35,8 @@ const char* hulc_last_error(void);
  * hulc_conv2d_fwd / hulc_conv2d_padded_fwd / hulc_conv2d_bwd_data / hulc_conv2d_bwd_weight call and the plan its launcher computed: a kernel token,
  * then key=value fields and `+pass` suffixes for follow-up launches, e.g. "band_x<32,2,4,4,2> xf32=0 bits=1 multi=1 R=9 F=3 units=2 grid=2",
  * "band_glds<4,2,2> bits=2 pad=1 units=3 grid=3", "conv1_band u8=0 x3=0 R=10 grid=5", "gather<bf16> +relu_bits_pass", "wgrad_gather f32=0 P=3".
+ * hulc_gridconv3x3 / hulc_gridconv3x3_fused report the same way: "gridconv<WN,TN,KCH> grid=G tiles=T" (G workgroups over T row tiles of 128) or
+ * "gridconv_thin<Cin,NB> wgs=G tiles=T" (G persistent workgroups, NB blocks of 32 output channels).
  * Thread-local like hulc_last_error(); every one of those entry points clears it on entry and a refused call leaves "".  Output only (tests and
  * diagnostics): nothing in the library reads it back. */
 const char* hulc_conv_last_path(void);
@@ -669,8 +671,11 @@ int hulc_wgrad_group(const hulc_wgrad_item* items, int n, void* ws, long ws_byte
  *   hulc_grid_bn_finalize (or NULL).
  * hulc_grid_upcat_fwd: DecoderBlock's input (unet_decoder.py:60-80): out grid (N, Ho, Wo) rows of Cx + Cs = [nearest-up-sampled x * g | skip];
  *   x (N, Ho/s, Wo/s, Cx) and skip (N, Ho, Wo, Cs) bf16 with element strides (n, y, x) — a grid tensor's pixels or a plain NHWC map; g (N, Cx)
- *   fp32 or NULL = lang_proj(l) of FusionMult (core/fusion.py:64-73).   hulc_grid_upcat_bwd: dsmall (grid (N, Hi, Wi) rows of Cx, pixels only)
- *   = g * the s x s block sums of dX's first Cx channels, dg (N, Cx) (+)= sum over pixels of x * block sums (either may be NULL).
+ *   fp32 or NULL = lang_proj(l) of FusionMult (core/fusion.py:64-73).   hulc_grid_upcat_bwd: dsmall (grid (N, Hi, Wi) rows of Cx)
+ *   = g * the s x s block sums of dX's first Cx channels, dg (N, Cx) (+)= sum over pixels of x * block sums (either may be NULL).  dsmall is the
+ *   ONE grid output whose border rows the kernel does not write: only the N Hi Wi pixel rows are stored, the border rows keep whatever the
+ *   caller left there.  Its consumer is hulc_grid_bn_relu_bwd (as dout), which masks by the border of its own `out`; a caller that hands dsmall
+ *   to a convolution must zero the border rows itself.
  * hulc_pixel_ce_fwd / _bwd: log-sum-exp over an image's H W logits (logit0: fp32 per grid row) and the labelled pixel's logit
  *   (p0 (N, 2) int32 = row, col); backward writes upstream (softmax - onehot) / (N H W) into channel 0 of a grid tensor of C channels. */
 /* hulc_gridconv3x3_fused: the same convolution with the epilogue of a frozen ResNet BasicBlock (torchvision resnet18 as r3m wraps it; BatchNorm

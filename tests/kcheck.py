@@ -1,6 +1,6 @@
 """Shared pieces of the kernel-level tests (tests/test_reductions_gpu.py, tests/test_losses_gpu.py, tests/test_ffn_kernel_gpu.py,
 tests/test_rnn_kernel_gpu.py, tests/test_conv_paths_gpu.py, tests/test_resnet_pieces_gpu.py, tests/test_lang_kernels_gpu.py,
-tests/test_mlp_chain_kernel_gpu.py, tests/test_mlp2_rows_kernel_gpu.py).
+tests/test_mlp_chain_kernel_gpu.py, tests/test_mlp2_rows_kernel_gpu.py, tests/test_grid_kernels_gpu.py).
 
 Every case of those files follows one pattern:
   1. inputs are drawn on the CPU in float64 from a seeded generator and rounded to the kernel's storage type; the float64 reference is given

@@ -53,7 +53,8 @@ def dgrad_weights(w):         # -> bf16 [Cin][9 Cout]: (ci, kh, kw, co), taps NO
 
 
 # the thin-layer kernel (Cin 32 / 64, filter in registers, persistent workgroups) takes (64, 32), (32, 64), (32, 32): one tile, a dozen tiles
-# over the XCDs, and 545 tiles (two trips for some workgroups)
+# over the XCDs, and 545 tiles (69 per XCD on the 96 slots of the 32 -> 32 instance at 256 CUs: still one trip per workgroup — the second trip
+# of the persistent loop is tests/test_grid_kernels_gpu.py::test_gridconv_thin_second_trip_lattice)
 @pytest.mark.parametrize("N,H,W,Cin,Cout", [(2, 6, 5, 64, 32), (3, 14, 14, 96, 128), (2, 9, 9, 32, 64), (1, 30, 17, 160, 256), (2, 11, 7, 32, 32),
                                             (3, 20, 20, 64, 32), (4, 130, 130, 32, 32), (2, 40, 33, 32, 64), (2, 23, 23, 64, 64)])
 def test_gridconv_forward_dgrad_wgrad(N, H, W, Cin, Cout):
