@@ -3,6 +3,7 @@
 Everything here takes device tensors, extracts `data_ptr()` / strides and calls libhulc2_amd.so on
 the current torch stream.  No arithmetic happens in Python.
 """
+import contextlib
 import ctypes
 
 import torch
@@ -810,6 +811,24 @@ def branch_stream(device, which: int = 0):
     if st is None:
         st = _branch_streams[(device, which)] = capture_stream(device)      # (distinct from every other cached stream)
     return st
+
+
+@contextlib.contextmanager
+def fork(cur, side, share=None):
+    """`with fork(cur, side, share):` — the body's launches become a branch on `side` that starts behind everything `cur` holds so far; with
+    `share` they run under coop_share_scope(share).  Leaving the block joins nothing: the matching `join(cur, side, ...)` goes where the main
+    stream first needs the branch's results."""
+    side.wait_stream(cur)
+    with torch.cuda.stream(side), (coop_share_scope(share) if share is not None else contextlib.nullcontext()):
+        yield
+
+
+def join(cur, side, *tensors) -> None:
+    """the end of a `fork(cur, side)` branch: `cur` waits for `side`, and every tensor the branch allocated that is used on `cur` from here on
+    is handed over — without record_stream the caching allocator could give its memory to `side` again while `cur` still reads it"""
+    cur.wait_stream(side)
+    for t in tensors:
+        t.record_stream(cur)
 
 
 _made_streams = []       # (kept alive: a stream wrapped by ExternalStream is never destroyed by torch)

@@ -16,7 +16,8 @@ from hulc2_amd.models.decoders.action_decoder import ActionDecoder
 from hulc2_amd.models.perceptual_encoders.vision_network import check_dropout_p, fc_site
 
 # Dropout sites of policy_rnn_dropout_p, after vision_network's pattern: functional.DECODER_RNN_SITE (0x5EED7001) for the stacked call, the
-# modality's own where a modality runs a call of its own (Hulc2.lmp_train; unequal batches in loss_segments), whose rows restart at 0.
+# modality's own where a modality runs a call of its own (Hulc2.lmp_train; Hulc2._step_per_modality with unequal batches: the separate passes of
+# loss_segments), whose rows restart at 0.
 DECODER_RNN_MODALITY_SITES = {"vis": 0x5EED7101, "lang": 0x5EED7201}
 
 
@@ -107,7 +108,8 @@ class LogisticDecoderRNN(ActionDecoder):
                                      *self.rnn_dropout(modality_scope))
 
     def loss(self, latent_plan, perceptual_emb, latent_goal, actions, robot_obs, modality_scope=None) -> torch.Tensor:
-        """modality_scope ("vis" / "lang", Hulc2.lmp_train): the modality this call serves — selects the RNN dropout's site"""
+        """modality_scope ("vis" / "lang", Hulc2.lmp_train; the training step itself calls loss_stacked / loss_segments): the modality this call
+        serves — selects the RNN dropout's site"""
         return self.loss_stacked(latent_plan, perceptual_emb, latent_goal, [actions], [robot_obs], 1, modality_scope=modality_scope)[0]
 
     def loss_segments(self, plans, embs, goals, actions, robot_obs, scopes=None) -> torch.Tensor:

@@ -13,9 +13,15 @@ Differences that do not change results:
     (B, plan_features) (`plan_eps_pp` / `plan_eps_pr` in validation); `plan_idx` is ignored there
   * `use_for_aux_lang_loss` is applied inside the CLIP loss kernel instead of boolean-mask indexing, so the step
     has no host synchronisation (the reference's `torch.any` / dynamic shapes, hulc2.py:391-394,490-493)
+
+The training step (`_training_step_impl`, what eager autograd, the step node and ArenaTrainer all run) is a driver over named stages:
+`_step_stacked` (modalities of one shape stacked on the batch axis; `_stacked_forks` decides fan-out, branches and the stacked contrastive
+head before the first launch, `_stacked_goals` / `_separate_goals` run the goal encoders) or `_step_per_modality` (everything else), each
+handing a `_Part` per modality, the KL and decoder losses and `_contrastive_loss` of the parts to `_step_tail` (loss combine + logging).
 """
+import contextlib
 import logging
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -27,6 +33,7 @@ from hulc2_amd import kernels as kn
 from hulc2_amd import switches
 from hulc2_amd.arena import WeightKeeper
 from hulc2_amd.compat import LightningModule, instantiate
+from hulc2_amd.models.perceptual_encoders.concat_encoders import ConcatEncoders
 from hulc2_amd.models.plan_encoders.plan_recognition_net import trunk_site
 from hulc2_amd.trainer import ArenaTrainer
 from hulc2_amd.utils.distributions import State
@@ -48,6 +55,15 @@ def _kernel_precision(fn):
                 return fn(self, *args, **kwargs)
         return fn(self, *args, **kwargs)
     return wrapped
+
+
+class _Part(NamedTuple):
+    """one modality of a training step, as the contrastive loss, the scalar tail and the logging see it"""
+    scope: str
+    db: Dict
+    goal: torch.Tensor                  # the modality's own goal rows (row0 None), or the stacked goals of all modalities
+    seq_feat: torch.Tensor              # the posterior's pooled features, rows as in `goal`
+    row0: Optional[int] = None          # set: `goal` / `seq_feat` are the stacked tensors and this modality's rows start here
 
 
 class Hulc2(LightningModule):
@@ -167,7 +183,6 @@ class Hulc2(LightningModule):
     def _goal_site(is_lang: bool):
         """precision scope of a goal encoder: only the LANGUAGE goal is upstream of the contrastive head — in a bf16 step the
         site "goal" makes that encoder's forward exact and leaves the visual one on its bf16 launches; 'mixed' / 'fp32' steps treat both alike"""
-        import contextlib
         if is_lang or kn.base_mode() != "bf16":
             return kn.site_scope("goal")
         return contextlib.nullcontext()
@@ -251,177 +266,188 @@ class Hulc2(LightningModule):
         return total_loss
 
     def _training_step_impl(self, batch: Dict[str, Dict], batch_idx: int):
-        """the arithmetic of training_step: -> (total loss, [(logged name, value, self.log keyword arguments)])"""
-        kl_loss = action_loss = total_loss = lang_clip_loss = None
-        clip_forked = False
-        batch_size: Dict[str, int] = {}
-        total_bs = 0
-
-        def acc(a, b):
-            return b if a is None else a + b
-
-        # encoders, goal, prior/posterior, latent plan sample, KL, decoder (hulc2.py:380-386,228-242).  Modalities of identical
-        # shape are stacked on the batch axis through every shared network (same per-row arithmetic, half the launches); only
-        # the goal encoders differ per modality, and every loss is still the mean over its own modality's rows.
-        per = []
-        kl_stacked = None
+        """the arithmetic of training_step: -> (total loss, [(logged name, value, self.log keyword arguments)]).  Encoders, goal, prior /
+        posterior, latent plan sample, KL, decoder (hulc2.py:380-386,228-242): modalities of identical shape are stacked on the batch axis
+        through every shared network (same per-row arithmetic, half the launches; only the goal encoders differ per modality, and every
+        loss is still the mean over its own modality's rows), any other batch runs one modality after the other."""
         mods = list(batch.items())
-        if self._batchable(mods):
-            with kn.site_scope("enc"):
-                emb_all = self.perceptual_encoder([db["rgb_obs"] for _, db in mods], None, None)
-            B = mods[0][1]["actions"].shape[0]
-            # the embedding's four consumers get their views from one fan-out node (one gather launch forward, ONE merge launch backward
-            # instead of autograd's select / slice backward fills and three accumulate adds): emb[:, 0] -> prior, emb[:B, -1] of a leading
-            # vision modality -> visual goal encoder, emb -> posterior, emb[..., lo:hi] time-major -> action decoder
-            vis_first = "lang" not in mods[0][0] and all("lang" in sc for sc, _ in mods[1:])
-            lo, hi = self.action_decoder.perceptual_emb_slice
-            fan = vis_first and emb_all.is_cuda
-            goal_all = None
-            # round 6: the posterior (transformer trunk + its head) does not depend on the goal encoders and the prior (hulc2.py:228-233): it runs as
-            # a second branch — a side stream eagerly, a branch of the captured graph in replay; autograd runs each branch's backward on the
-            # stream of its forward, so the backward forks the same way.  Both branches are cooperative launches that own a CU per workgroup:
-            # each keeps to half of the device (kernels.coop_share_scope -> coop_share of the launches' descriptors, include/hulc2_amd.h).  HULC_FORK=0: one after the other.
-            fork = fan and kn.fork_branches()
-            # a RECURRENT posterior (plan_recognition=birnn) is no branch: its persistent sweeps own every CU behind a device-wide barrier, and
-            # spinning beside the prior's cooperative chain on a side stream they would time out.  It runs on the main stream, after the prior,
-            # outside coop_share_scope(2); the contrastive branch below keeps its rule
-            fork_post = fork and not getattr(self.plan_recognition, "recurrent", False)
-            if fan:
-                emb0, emb_last, emb_rec, emb_dec_t = HF.EmbFanoutFn.apply(emb_all, B, lo, hi)
-            if fork:
-                cur, side = torch.cuda.current_stream(emb_all.device), kn.branch_stream(emb_all.device)
-            if fork_post:
-                side.wait_stream(cur)
-                with torch.cuda.stream(side), kn.coop_share_scope(2):
-                    pr_all, seq_all = self.plan_recognition(emb_rec)
-            with kn.coop_share_scope(2 if fork_post else 1):      # (the prior branch's chain launches: half of the device next to the posterior's)
-                if fan:
-                    # selective precision (DESIGN §5): of the goal encoders only the LANGUAGE one is upstream of the contrastive head; inside a bf16
-                    # step with site "goal" it alone runs its forward exactly, the visual one stays on its bf16 chain launch
-                    lang_only_exact = kn.base_mode() == "bf16" and kn.get_compute() == "bf16" and "goal" in kn.fp32_sites() and len(mods) == 2
-                    if lang_only_exact:
-                        # both encoders in ONE launch, the language one from split operands (three MFMAs per product: fp32-class values) ...
-                        pair = HF.dual_mlp(emb_last, self.visual_goal.mlp_layers(), self.language_goal.embed(mods[1][1]["lang"]),
-                                           self.language_goal.mlp_layers(), exact_b=True)
-                        if pair is None:        # ... or, where the pair does not fit the launch, on the exact-fp32 GEMMs
-                            pre_v = self.visual_goal(emb_last, pre_ln=True)
-                            with kn.site_scope("goal"):
-                                pre_l = self.language_goal(mods[1][1]["lang"], pre_ln=True)
-                            pair = (pre_v, pre_l)
-                        pre = list(pair)
-                    with kn.site_scope("goal"):
-                        # the modalities' goal encoders stop in front of their LayerNorms, which then write the rows of the stacked goal tensor
-                        # directly (no concatenation, no strided gradient slices on the way back)
-                        if lang_only_exact:
-                            pass
-                        elif len(mods) == 2:    # the two goal MLPs (same hidden widths, their own weights) as one launch each way
-                            pre = list(HF.dual_mlp(emb_last, self.visual_goal.mlp_layers(), self.language_goal.embed(mods[1][1]["lang"]),
-                                                   self.language_goal.mlp_layers()))
-                        else:
-                            pre = [self.language_goal(db["lang"], pre_ln=True) if "lang" in scope else self.visual_goal(emb_last, pre_ln=True) for scope, db in mods]
-                        goal_encs = [self.language_goal if "lang" in scope else self.visual_goal for scope, _ in mods]
-                        goal_all = HF.layer_norm_cat(pre, [g.ln for g in goal_encs], dim=0, l2=[g.l2_normalize_output for g in goal_encs])
-                    goals = [None] * len(mods)
-                else:
-                    embs = [emb_all[i * B:(i + 1) * B] for i in range(len(mods))]
-                    emb0, emb_rec = emb_all[:, 0], emb_all
-                    goals = []
-                    for i, (scope, db) in enumerate(mods):
-                        with self._goal_site("lang" in scope):
-                            goals.append(self.language_goal(db["lang"]) if "lang" in scope else self.visual_goal(embs[i][:, -1]))
-                if goal_all is None:
-                    goal_all = torch.cat(goals, dim=0)
-                with kn.site_scope("prior"):
-                    pp_all = self.plan_proposal(emb0, goal_all)
-            if fork_post:
-                cur.wait_stream(side)                      # join: sample + KL consume both branches
-                for t_ in (self.dist.state_tensor(pr_all), seq_all):
-                    t_.record_stream(cur)
-            else:
-                pr_all, seq_all = self.plan_recognition(emb_rec)
-            # the contrastive head sees the stacked rows when the language modality is the last segment: rows below row0 are masked out inside the
-            # loss kernel (their gradient is exactly zero) — no slice of the pooled features / goals, no gradient scatter on the way back
-            lang_ix = [i for i, (sc, _) in enumerate(mods) if "lang" in sc]
-            stacked_head = fan and lang_ix == [len(mods) - 1] and self.use_clip_auxiliary_loss and len(mods) * B <= 128
-            for i, (self.modality_scope, db) in enumerate(mods):
-                if stacked_head and i == lang_ix[0]:
-                    per.append((self.modality_scope, db, None, goal_all, seq_all, i * B, None))
-                else:
-                    per.append((self.modality_scope, db, None, goals[i] if goals[i] is not None else goal_all[i * B:(i + 1) * B],
-                                seq_all[i * B:(i + 1) * B], None, None))
-            # round 6: the contrastive head (two projections + the loss, forward and backward ~0.15 ms of small launches) needs the pooled
-            # posterior features and the goals only — it runs as a branch beside sample / KL / the decoder's input projections, and its backward
-            # beside the start of the decoder's.  The recurrent sweeps take every CU while they run, so nothing in this branch may be a
-            # cooperative launch (coop_share_scope(0): the projections' chains fall back to GEMMs — a chain spinning on some CUs while the sweep
-            # waits for all of them would never finish).
-            if fork and self.use_clip_auxiliary_loss and any("lang" in p_[0] for p_ in per):
-                side.wait_stream(cur)
-                with torch.cuda.stream(side), kn.coop_share_scope(0):
-                    for (scope_, db_, _e, goal_, seqf_, plan_, _k) in per:
-                        if "lang" in scope_:
-                            lang_clip_loss = acc(lang_clip_loss, self.clip_auxiliary_loss(seqf_, goal_, db_["use_for_aux_lang_loss"],
-                                                                                          row0=plan_ if isinstance(plan_, int) else 0))
-                clip_forked = True
-            # sample, KL and decoder once over the stacked rows; the KL / decoder kernels return one mean per modality.  Sample + KL are ONE
-            # autograd node (both consume the posterior's logits: their gradients meet inside the kernels, not in a fan-in add)
-            # (injected sample, parity tests: class indices for the categorical plan, Gaussian noise for the continuous one)
-            cont = self.dist.dist == "continuous"
-            inj = [db.get("plan_eps" if cont else "plan_idx") for _, db in mods]
-            inj_all = torch.cat(inj, dim=0) if all(i is not None for i in inj) else None
-            plan_all, _, kls = self.dist.rsample_plan_and_kl(pp_all, pr_all, 0xA11CE, None if cont else inj_all, self._kl_beta_arg(),
-                                                             self.kl_balancing_mix, len(mods), eps=inj_all if cont else None)
-            kl_stacked = kls
-            act_losses = self.action_decoder.loss_stacked(plan_all, emb_dec_t if fan else emb_all, goal_all,
-                                                          [db["actions"] for _, db in mods], [db["state_info"]["robot_obs"] for _, db in mods],
-                                                          len(mods), emb_tm=fan)
+        parts, kl_vec, act_losses, clip = self._step_stacked(mods) if self._batchable(mods) else self._step_per_modality(mods)
+        return self._step_tail(parts, kl_vec, act_losses, clip)
+
+    def _stacked_forks(self, mods, B: int):
+        """How the stacked step is arranged, decided before its first launch: -> (fan, fork, fork_post, stacked_head, fork_clip)
+          fan           the embedding's four consumers get their views from one fan-out node (one gather launch forward, ONE merge launch
+                        backward instead of autograd's select / slice backward fills and three accumulate adds): emb[:, 0] -> prior,
+                        emb[:B, -1] of the leading vision modality -> visual goal encoder, emb -> posterior, emb[..., lo:hi] time-major ->
+                        action decoder.  Needs a GPU model and the vision modality in front of the language ones.
+          fork          the step's independent branches run on a side stream eagerly and as branches of the captured graph in replay; autograd
+                        runs each branch's backward on the stream of its forward, so the backward forks the same way.  HULC_FORK=0: one
+                        after the other.
+          fork_post     round 6: the posterior (transformer trunk + its head) does not depend on the goal encoders and the prior
+                        (hulc2.py:228-233): it is the first branch.  Both sides are cooperative launches that own a CU per workgroup: each
+                        keeps to half of the device (kernels.coop_share_scope -> coop_share of the launches' descriptors,
+                        include/hulc2_amd.h).  A RECURRENT posterior (plan_recognition=birnn) is no branch: its persistent sweeps own every
+                        CU behind a device-wide barrier, and spinning beside the prior's cooperative chain on a side stream they would time
+                        out.  It runs on the main stream, after the prior, outside coop_share_scope(2).
+          stacked_head  the contrastive head sees the stacked rows when the language modality is the last segment: rows below row0 are masked
+                        out inside the loss kernel (their gradient is exactly zero) — no slice of the pooled features / goals, no gradient
+                        scatter on the way back
+          fork_clip     round 6: the contrastive head (two projections + the loss, forward and backward ~0.15 ms of small launches) needs
+                        the pooled posterior features and the goals only — it is the second branch, beside sample / KL / the decoder's input
+                        projections, and its backward beside the start of the decoder's.  The recurrent sweeps take every CU while they run,
+                        so nothing in this branch may be a cooperative launch (coop_share_scope(0): the projections' chains fall back to
+                        GEMMs — a chain spinning on some CUs while the sweep waits for all of them would never finish)."""
+        lang_ix = [i for i, (sc, _) in enumerate(mods) if "lang" in sc]
+        vis_first = "lang" not in mods[0][0] and all("lang" in sc for sc, _ in mods[1:])
+        fan = vis_first and next(self.parameters()).is_cuda
+        fork = fan and kn.fork_branches()
+        fork_post = fork and not getattr(self.plan_recognition, "recurrent", False)
+        stacked_head = fan and lang_ix == [len(mods) - 1] and self.use_clip_auxiliary_loss and len(mods) * B <= 128
+        fork_clip = fork and self.use_clip_auxiliary_loss and bool(lang_ix)
+        return fan, fork, fork_post, stacked_head, fork_clip
+
+    def _step_stacked(self, mods):
+        """all modalities stacked on the batch axis: -> (parts, kl (n,), action losses (n,), contrastive loss or None)"""
+        n, B = len(mods), mods[0][1]["actions"].shape[0]
+        fan, fork, fork_post, stacked_head, fork_clip = self._stacked_forks(mods, B)
+        with kn.site_scope("enc"):
+            emb_all = self.perceptual_encoder([db["rgb_obs"] for _, db in mods], None, None)
+        # (vis_in, what the visual goal encoder reads: the leading modality's last frame from the fan-out, else every modality's own rows)
+        if fan:
+            emb0, vis_in, emb_rec, emb_dec = HF.EmbFanoutFn.apply(emb_all, B, *self.action_decoder.perceptual_emb_slice)
         else:
-            for self.modality_scope, db in mods:
-                with kn.site_scope("enc"):
-                    emb = self._encode_modality(db)
-                with self._goal_site("lang" in self.modality_scope):
-                    latent_goal = self.language_goal(db["lang"]) if "lang" in self.modality_scope else self.visual_goal(emb[:, -1])
-                with kn.site_scope("prior"):
-                    pp_state = self.plan_proposal(emb[:, 0], latent_goal)
-                pr_state, seq_feat = self.plan_recognition(emb, seed=trunk_site(self.modality_scope))
-                site = 0xA11CE if "lang" in self.modality_scope else 0xB0B
-                plan, _ = self.dist.rsample_plan(pr_state, seed=site, idx=db.get("plan_idx"), eps=db.get("plan_eps"))
-                per.append((self.modality_scope, db, emb, latent_goal, seq_feat, plan, self.compute_kl_loss(pp_state, pr_state)))
-            # the action decoder sees all modalities at once (shared weights, independent sequences); it returns one loss per
-            # modality, each the mean over that modality's own tokens as in the reference (hulc2.py:239-241)
-            act_losses = self.action_decoder.loss_segments([p[5] for p in per], [p[2] for p in per], [p[3] for p in per],
-                                                           [p[1]["actions"] for p in per], [p[1]["state_info"]["robot_obs"] for p in per],
-                                                           scopes=[p[0] for p in per])
-        # the scalar tail (hulc2.py:400-430) is one launch per direction: total = (sum act + sum kl) / n + beta * clip
-        for i, (self.modality_scope, db, emb, latent_goal, seq_feat, plan, kl) in enumerate(per):
-            if "lang" in self.modality_scope:
-                batch_size["aux_lang"] = 1
-                if self.use_clip_auxiliary_loss:
-                    if not clip_forked:
-                        row0 = plan if (kl_stacked is not None and isinstance(plan, int)) else 0    # (stacked rows: see `stacked_head` above)
-                        lang_clip_loss = acc(lang_clip_loss, self.clip_auxiliary_loss(seq_feat, latent_goal, db["use_for_aux_lang_loss"], row0=row0))
-                    # hulc2.py:391-394: the epoch mean of train/lang_clip_loss is weighted by the number of masked-in rows (1 when there are
-                    # none) — counted by the loss kernel, a device value (no torch.any / torch.sum host round trip)
-                    batch_size["aux_lang"] = self._aux_lang_rows
-            bs = db["actions"].shape[0]
-            batch_size[self.modality_scope] = bs
-            total_bs += bs
-        n = len(batch)
-        if clip_forked:
-            cur.wait_stream(side)
-            lang_clip_loss.record_stream(cur)
-        kl_vec = kl_stacked if kl_stacked is not None else torch.stack([p[6].reshape(()) for p in per])
+            vis_in = [emb_all[i * B:(i + 1) * B] for i in range(n)]
+            emb0, emb_rec, emb_dec = emb_all[:, 0], emb_all, emb_all
+        cur, side = (torch.cuda.current_stream(emb_all.device), kn.branch_stream(emb_all.device)) if fork else (None, None)
+        if fork_post:
+            with kn.fork(cur, side, share=2):
+                pr_all, seq_all = self.plan_recognition(emb_rec)
+        with kn.coop_share_scope(2 if fork_post else 1):      # (the prior branch's chain launches: half of the device next to the posterior's)
+            if fan:
+                goal_all, goals = self._stacked_goals(mods, vis_in), None
+            else:
+                goals = self._separate_goals(mods, vis_in)
+                goal_all = torch.cat(goals, dim=0)
+            with kn.site_scope("prior"):
+                pp_all = self.plan_proposal(emb0, goal_all)
+        if fork_post:
+            kn.join(cur, side, self.dist.state_tensor(pr_all), seq_all)       # sample + KL consume both branches
+        else:
+            pr_all, seq_all = self.plan_recognition(emb_rec)
+        parts = []
+        for i, (self.modality_scope, db) in enumerate(mods):
+            if stacked_head and "lang" in self.modality_scope:
+                parts.append(_Part(self.modality_scope, db, goal_all, seq_all, row0=i * B))
+            else:
+                parts.append(_Part(self.modality_scope, db, goals[i] if goals is not None else goal_all[i * B:(i + 1) * B],
+                                   seq_all[i * B:(i + 1) * B]))
+        if fork_clip:
+            with kn.fork(cur, side, share=0):
+                clip = self._contrastive_loss(parts)
+        # sample, KL and decoder once over the stacked rows; the KL / decoder kernels return one mean per modality.  Sample + KL are ONE
+        # autograd node (both consume the posterior's logits: their gradients meet inside the kernels, not in a fan-in add)
+        # (injected sample, parity tests: class indices for the categorical plan, Gaussian noise for the continuous one)
+        cont = self.dist.dist == "continuous"
+        inj = [db.get("plan_eps" if cont else "plan_idx") for _, db in mods]
+        inj_all = torch.cat(inj, dim=0) if all(i is not None for i in inj) else None
+        plan_all, _, kls = self.dist.rsample_plan_and_kl(pp_all, pr_all, 0xA11CE, None if cont else inj_all, self._kl_beta_arg(),
+                                                         self.kl_balancing_mix, n, eps=inj_all if cont else None)
+        act_losses = self.action_decoder.loss_stacked(plan_all, emb_dec, goal_all, [db["actions"] for _, db in mods],
+                                                      [db["state_info"]["robot_obs"] for _, db in mods], n, emb_tm=fan)
+        if fork_clip:
+            kn.join(cur, side, clip)
+        else:
+            clip = self._contrastive_loss(parts)
+        return parts, kls, act_losses, clip
+
+    def _stacked_goals(self, mods, emb_last):
+        """The goal encoders of the stacked step behind the fan-out -> the stacked goal tensor (n * B, latent_goal_features).  The encoders stop in
+        front of their LayerNorms, which then write the rows of the stacked tensor directly (one layer_norm_cat launch: no concatenation, no
+        strided gradient slices on the way back).  What runs in front of it:
+          * a bf16 step with site "goal" and two modalities (selective precision, DESIGN §5: of the goal encoders only the LANGUAGE one is
+            upstream of the contrastive head): both encoders in ONE dual_mlp launch, the language one from split operands (three MFMAs per
+            product: fp32-class values) while the visual one stays on bf16 operands ...
+          * ... or, where the pair does not fit that launch: the visual encoder's own bf16 chain launch and the language encoder on the
+            exact-fp32 GEMMs
+          * any other step with two modalities: the two MLPs (same hidden widths, their own weights) as one plain dual_mlp launch each way
+          * more than two modalities: every encoder's own launches"""
+        vis, lang = self.visual_goal, self.language_goal
+        if kn.base_mode() == "bf16" and kn.get_compute() == "bf16" and "goal" in kn.fp32_sites() and len(mods) == 2:
+            pre = HF.dual_mlp(emb_last, vis.mlp_layers(), lang.embed(mods[1][1]["lang"]), lang.mlp_layers(), exact_b=True)
+            if pre is None:
+                pre_v = vis(emb_last, pre_ln=True)
+                with kn.site_scope("goal"):
+                    pre = (pre_v, lang(mods[1][1]["lang"], pre_ln=True))
+        elif len(mods) == 2:
+            with kn.site_scope("goal"):
+                pre = HF.dual_mlp(emb_last, vis.mlp_layers(), lang.embed(mods[1][1]["lang"]), lang.mlp_layers())
+        else:
+            with kn.site_scope("goal"):
+                pre = [lang(db["lang"], pre_ln=True) if "lang" in scope else vis(emb_last, pre_ln=True) for scope, db in mods]
+        encs = [lang if "lang" in scope else vis for scope, _ in mods]
+        with kn.site_scope("goal"):
+            return HF.layer_norm_cat(list(pre), [g.ln for g in encs], dim=0, l2=[g.l2_normalize_output for g in encs])
+
+    def _separate_goals(self, mods, embs):
+        """the goal encoders of the stacked step without the fan-out: each whole, on its own modality's rows -> one goal tensor per modality"""
+        goals = []
+        for (scope, db), emb in zip(mods, embs):
+            with self._goal_site("lang" in scope):
+                goals.append(self.language_goal(db["lang"]) if "lang" in scope else self.visual_goal(emb[:, -1]))
+        return goals
+
+    def _step_per_modality(self, mods):
+        """one modality after the other through the encoders, the prior and the posterior (a single modality, shapes that differ,
+        HULC_NO_MODALITY_BATCHING=1): -> (parts, kl (n,), action losses (n,), contrastive loss or None)"""
+        parts, embs, plans, kls = [], [], [], []
+        for self.modality_scope, db in mods:
+            is_lang = "lang" in self.modality_scope
+            with kn.site_scope("enc"):
+                emb = self._encode_modality(db)
+            with self._goal_site(is_lang):
+                latent_goal = self.language_goal(db["lang"]) if is_lang else self.visual_goal(emb[:, -1])
+            with kn.site_scope("prior"):
+                pp_state = self.plan_proposal(emb[:, 0], latent_goal)
+            pr_state, seq_feat = self.plan_recognition(emb, seed=trunk_site(self.modality_scope))
+            plan, _ = self.dist.rsample_plan(pr_state, seed=0xA11CE if is_lang else 0xB0B, idx=db.get("plan_idx"), eps=db.get("plan_eps"))
+            kls.append(self.compute_kl_loss(pp_state, pr_state))
+            parts.append(_Part(self.modality_scope, db, latent_goal, seq_feat))
+            embs.append(emb)
+            plans.append(plan)
+        # the action decoder sees all modalities at once (shared weights, independent sequences); it returns one loss per
+        # modality, each the mean over that modality's own tokens as in the reference (hulc2.py:239-241)
+        act_losses = self.action_decoder.loss_segments(plans, embs, [p.goal for p in parts], [p.db["actions"] for p in parts],
+                                                       [p.db["state_info"]["robot_obs"] for p in parts], scopes=[p.scope for p in parts])
+        clip = self._contrastive_loss(parts)
+        return parts, torch.stack([kl.reshape(()) for kl in kls]), act_losses, clip
+
+    def _contrastive_loss(self, parts):
+        """clip_auxiliary_loss summed over the language modalities; None when the loss is off or the batch has no language modality"""
+        loss = None
+        if self.use_clip_auxiliary_loss:
+            for p in parts:
+                if "lang" in p.scope:
+                    term = self.clip_auxiliary_loss(p.seq_feat, p.goal, p.db["use_for_aux_lang_loss"], row0=p.row0 or 0)
+                    loss = term if loss is None else loss + term
+        return loss
+
+    def _step_tail(self, parts, kl_vec, act_losses, clip):
+        """the scalar tail (hulc2.py:400-430), one launch per direction: total = (sum act + sum kl) / n + beta * clip; and what the step logs"""
         act_vec = act_losses if act_losses.dim() == 1 else act_losses.reshape(-1)
-        clip_term = lang_clip_loss if (self.use_clip_auxiliary_loss and lang_clip_loss is not None) else None
-        total_loss, logs = HF.LossCombineFn.apply(kl_vec, act_vec, clip_term, float(self.clip_auxiliary_loss_beta))
+        total_loss, logs = HF.LossCombineFn.apply(kl_vec, act_vec, clip, float(self.clip_auxiliary_loss_beta))
         kl_d, act_d = kl_vec.detach(), act_vec.detach()
         logged = []
-        for i, (scope, db, *_rest) in enumerate(per):
-            bs = db["actions"].shape[0]
-            logged.append((f"train/kl_loss_scaled_{scope}", kl_d[i], dict(on_step=False, on_epoch=True, batch_size=bs)))
-            logged.append((f"train/action_loss_{scope}", act_d[i], dict(on_step=False, on_epoch=True, batch_size=bs)))
-            logged.append((f"train/total_loss_{scope}", logs[3 + i], dict(on_step=False, on_epoch=True, batch_size=bs)))
-        if clip_term is not None:
-            logged.append(("train/lang_clip_loss", logs[2], dict(on_step=False, on_epoch=True, batch_size=batch_size.get("aux_lang", 1), sync_dist=True)))
+        total_bs = 0
+        for i, p in enumerate(parts):
+            bs = p.db["actions"].shape[0]
+            total_bs += bs
+            logged.append((f"train/kl_loss_scaled_{p.scope}", kl_d[i], dict(on_step=False, on_epoch=True, batch_size=bs)))
+            logged.append((f"train/action_loss_{p.scope}", act_d[i], dict(on_step=False, on_epoch=True, batch_size=bs)))
+            logged.append((f"train/total_loss_{p.scope}", logs[3 + i], dict(on_step=False, on_epoch=True, batch_size=bs)))
+        if clip is not None:
+            # hulc2.py:391-394: the epoch mean of train/lang_clip_loss is weighted by the number of masked-in rows (1 when there are none) —
+            # counted by the loss kernel, a device value (no torch.any / torch.sum host round trip)
+            logged.append(("train/lang_clip_loss", logs[2], dict(on_step=False, on_epoch=True, batch_size=self._aux_lang_rows, sync_dist=True)))
         logged.append(("train/kl_loss", logs[0], dict(on_step=False, on_epoch=True, batch_size=total_bs)))
         logged.append(("train/action_loss", logs[1], dict(on_step=False, on_epoch=True, batch_size=total_bs)))
         logged.append(("train/total_loss", total_loss, dict(on_step=False, on_epoch=True, batch_size=total_bs)))
@@ -430,7 +456,6 @@ class Hulc2(LightningModule):
     def _encode_modality(self, db):
         """the perceptual encoder on ONE modality's frames (rows restart at 0 per call): ConcatEncoders hands the camera heads' fc dropout
         the modality's own RNG site, so vis and lang draw different masks; other encoder classes take the reference's three arguments"""
-        from hulc2_amd.models.perceptual_encoders.concat_encoders import ConcatEncoders
         if isinstance(self.perceptual_encoder, ConcatEncoders):
             return self.perceptual_encoder(db["rgb_obs"], db["depth_obs"], db["robot_obs"], modality_scope=self.modality_scope)
         return self.perceptual_encoder(db["rgb_obs"], db["depth_obs"], db["robot_obs"])

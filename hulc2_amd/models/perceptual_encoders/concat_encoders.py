@@ -9,6 +9,7 @@ from typing import Dict, Optional
 import torch
 import torch.nn as nn
 
+from hulc2_amd import kernels as kn
 from hulc2_amd import switches
 from hulc2_amd.compat import instantiate
 
@@ -19,7 +20,6 @@ _side_streams = {}
 def _encoder_side_stream(device):
     st = _side_streams.get(device)
     if st is None:
-        from hulc2_amd import kernels as kn
         st = _side_streams[device] = kn.capture_stream(device)       # (none of the other cached streams: kernels.capture_stream)
     return st
 
@@ -115,13 +115,11 @@ class ConcatEncoders(nn.Module):
         if two:
             cur = torch.cuda.current_stream(fr[0][0].device)
             side = _encoder_side_stream(fr[0][0].device)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
+            with kn.fork(cur, side):
                 g = run_g()
         enc = self.rgb_static_encoder([f[0] for f in fr], [f[1] for f in fr], self.aug_pad["rgb_static"], [f[2] for f in fr], **kw).reshape(len(fr) * b, s, -1)
         if two:
-            cur.wait_stream(side)
-            g.record_stream(cur)
+            kn.join(cur, side, g)
         elif has_gripper:
             g = run_g()
         if fuse_ln:

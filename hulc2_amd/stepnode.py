@@ -7,7 +7,8 @@ forward / backward bodies and ctypes launches made the loop host-bound: 7.3 ms p
 
 Here the whole step is ONE node whose inputs are the parameters:
 
-  forward   runs the step's forward (`Hulc2._training_step_impl`) under `torch.enable_grad()` and keeps the inner loss,
+  forward   runs the step's forward (`Hulc2._training_step_impl`: its stacked or per-modality arrangement, then the scalar tail) under
+            `torch.enable_grad()` and keeps the inner loss,
   backward  runs the inner backward with the incoming gradient as its root — under a GradScaler that is the loss scale, a device scalar the
             first backward kernel multiplies by (a power of two: exact through every kernel) — while the keeper's gradient sinks are live
             (arena.WeightKeeper(model, step_node=True)): the backward kernels write the weight gradients straight into one
@@ -457,16 +458,15 @@ class StepNode:
                 and t.data_ptr() % 16 == 0}
         kn._frame_slots, kn._frame_slots_probe = (cand or None), True
         kn._frame_slots_used = set()
-        side.wait_stream(cur)
         try:
-            with torch.cuda.stream(side):
+            with kn.fork(cur, side):
                 loss, _ = self._inner_forward(batch, batch_idx)
                 self._inner_backward(loss, one)
                 del loss
                 kn.step_state(dev).copy_(words)
         finally:
             kn._frame_slots, kn._frame_slots_probe = None, False
-        cur.wait_stream(side)
+        kn.join(cur, side)
         torch.cuda.synchronize(dev)
         slot_idx = sorted(cand[p] for p in kn._frame_slots_used if p in cand)
         # the graphs' input buffers: the caller's own tensors (a resident batch then costs nothing), except the slot-read frame tensors — private

@@ -1,5 +1,6 @@
-"""Round 6: the step's independent branches as branches of one graph (hulc2_amd/models/hulc2.py `_training_step_impl`, kernels.coop_share_scope,
-include/hulc2_amd.h "Cooperative launches": coop_share of the chain's and the trunk's descriptor).
+"""Round 6: the step's independent branches as branches of one graph (hulc2_amd/models/hulc2.py `_step_stacked`, whose `_stacked_forks` decides
+them; kernels.fork / kernels.join and kernels.coop_share_scope; include/hulc2_amd.h "Cooperative launches": coop_share of the chain's and the
+trunk's descriptor).
 
 reference: hulc2/models/hulc2.py:228-233 — the prior (goal encoders -> plan proposal) and the posterior (plan recognition) are computed from the
 same perceptual embedding and do not depend on each other; the contrastive head (hulc2.py:472-508) needs the pooled posterior features and the

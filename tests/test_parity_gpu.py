@@ -570,6 +570,43 @@ def test_training_step_arrangements_at_full_size(dev, variant, monkeypatch):
     assert errs[len(errs) // 2] <= bar["med"] and errs[-1] <= bar["worst"], (errs[len(errs) // 2], errs[-5:])
 
 
+def test_unequal_batches_equal_the_single_modality_steps(dev, model):
+    """Modalities of unequal batch size (vision B = 2, language B = 3, S = 8): `_batchable` is false because of the shapes, the step runs one
+    modality after the other and the decoder's loss_segments falls back to separate passes.  Every modality's logged KL, action loss and
+    total then is what a step on that modality alone logs — bit for bit (fp32 compute, dropout 0, injected plan: measured equal on the
+    commit before the step was split into stages, asserted with torch.equal) — and train/total_loss is the scalar tail's
+    (sum of the per-modality totals) / 2 + beta * clip, rebuilt in float64 from the logged fp32 values.  Bar of the rebuild: the tail sums
+    four fp32 terms, halves and adds the fifth in fp32, in another association than the rebuild from the two ROUNDED per-modality totals —
+    at most eight roundings of 2^-24, each relative to no more than the sum of the terms' magnitudes, between the two."""
+    from hulc2_amd import kernels as kn
+
+    kn.set_compute("fp32")
+    try:
+        vis = syn.make_modality_batch(55, "vis", 2, 8, lang=False, device=dev)
+        lang = syn.make_modality_batch(55, "lang", 3, 8, lang=True, device=dev)
+
+        def step(batch):
+            model.logged.clear()
+            model.training_step(batch, 0)
+            torch.cuda.synchronize()
+            kn.check_faults(dev)
+            return {k: v.detach().clone() for k, v in model.logged.items() if k.startswith("train/")}
+
+        both, singles = step({"vis": vis, "lang": lang}), (step({"vis": vis}), step({"lang": lang}))
+    finally:
+        kn.set_compute("bf16")
+    for scope, single in zip(("vis", "lang"), singles):
+        names = [k for k in single if k.endswith("_" + scope)]
+        assert sorted(names) == sorted(f"train/{what}_{scope}" for what in ("kl_loss_scaled", "action_loss", "total_loss")), names
+        for k in names:
+            print(f"{k}: both {float(both[k]):.9g}  alone {float(single[k]):.9g}")
+            assert torch.equal(both[k], single[k]), (k, float(both[k]), float(single[k]))
+    terms = [both["train/total_loss_vis"].double(), both["train/total_loss_lang"].double(), both["train/lang_clip_loss"].double()]
+    rebuilt = (terms[0] + terms[1]) / 2 + terms[2]              # (train/lang_clip_loss is logged as beta * clip, the tail's third term)
+    print(f"train/total_loss {float(both['train/total_loss']):.9g}  rebuilt {float(rebuilt):.9g}")
+    assert abs(float(both["train/total_loss"]) - float(rebuilt)) <= 8 * 2.0 ** -24 * sum(abs(float(t)) for t in terms)
+
+
 def test_world_to_tcp_matches_oracle(dev):
     from hulc2_amd import functional as HF
     from oracle import hulc2_oracle as O
